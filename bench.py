@@ -2,7 +2,11 @@
 """bench.py -- frame-pairs/s of the DeFlow training step (deflowLoss, Adam lr=2e-4, bs=16 per GPU, 512x512 BEV,
 80 000-point clouds, 4 GRU iterations, fp32) on N MI355X of one node.  One process per GPU, RCCL over xGMI.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when --dump-outputs is given, and
+prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, config incl. the loss).  Everything
+else it can measure or check runs only with --full (the list below).
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in
 the environment) or started bare -- then this file re-launches itself under torch.distributed.run (127.0.0.1 rendezvous,
@@ -10,15 +14,21 @@ free port) and rank 0's JSON line is the output.
 
 A "step" = one full training pass over one synthetic, HBM-resident batch: ego-motion, pillarise both clouds, UNet
 forward, GRU decoder, gt gather + deflowLoss, complete backward, gradient all-reduce (N > 1), Adam.  Nothing is
-skipped or cached between steps.  Prints ONE JSON line on rank 0 (contract in the round prompt), including
+skipped or cached between steps.  Prints ONE JSON line on rank 0 (contract in the round prompt); with --full also
   roofline        live HIP-event timing of the dominant kernel (fp32 MFMA implicit-GEMM conv) vs the 157.3 TFLOP/s peak
   roofline_hbm    the HBM-bound stages (pillarise, BatchNorm+GELU passes) and the GRU kernels: algorithmic bytes / time / 8 TB/s
   forward_only    BASELINE configs[1] (B=1 inference), timed AFTER the training region
   bf16_inference  BASELINE configs[4] shape (1024x1024, 160k points, 8 iterations, bf16 MFMA), after the training region
   cpu_baseline    the CPU oracle (oracle/ref_torch.py, a PyTorch port of the reference algorithm) timed on this host:
                   median of 5 after 2 warm-ups, training step and forward only
-  (N > 1) rccl_ranks, per-rank step times, bf16_training over all ranks, allreduce_exposed_ms (steps with vs without the
-          gradient collectives).
+  (N > 1) the RCCL self-check, bf16_training over all ranks, allreduce_exposed_ms (steps with vs without the gradient
+          collectives), the per-bucket trace and the one-bucket leg.
+  The per-launch HIP events behind `roofline` / `roofline_hbm` run inside the timed steps, so they are --full only too.
+
+--dump-outputs DIR: right after the timed steps, what the last one handed back, as DIR/<name>.npy (float32 / float64,
+~50 MB at the default shape): loss, the valid points' flow and their indices (as DeFlow.forward returns them: rows
+0 .. counts0[b] of every sample, concatenated), counts0, and the model state the step left (every floating-point
+state_dict entry after Adam, flattened in state_dict order).  Inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -50,14 +60,19 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="per-GPU batch (the metric is quoted at 16)")
     ap.add_argument("--rotate", type=int, default=4, help="distinct HBM-resident batches the timed steps rotate over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-samples", type=int, default=5, help="timed CPU-oracle repetitions per leg (after 2 warm-ups)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every extra measurement and check (per-launch events / roofline, forward-only, bf16, HIP graph, "
+                         "precision ladder, loader, CPU baseline; N > 1: self-check and collective legs); off: the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--cpu-samples", type=int, default=5, help="(--full) timed CPU-oracle repetitions per leg (after 2 warm-ups)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip forward_only / bf16_inference / allreduce_exposed (e.g. for a rocprofv3 trace that should hold "
+                    help="(--full) skip forward_only / bf16_inference / allreduce_exposed (e.g. for a rocprofv3 trace that should hold "
                          "the training launches only)")
-    ap.add_argument("--forward-only", action="store_true", help="(kept for compatibility: the forward-only leg now always runs)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-launch HIP events")
-    ap.add_argument("--no-loader", action="store_true", help="skip the loader_fed extra (scene files written at run time; ~1 min)")
+    ap.add_argument("--forward-only", action="store_true", help="(kept for compatibility: the forward-only leg runs with --full)")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) skip the per-launch HIP events")
+    ap.add_argument("--no-loader", action="store_true", help="(--full) skip the loader_fed extra (scene files written at run time; ~1 min)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective plumbing only: gloo, no GPU, no kernels (CPU test of the N > 1 start-up)")
     return ap.parse_args()
@@ -176,6 +191,48 @@ def cpu_baseline(samples: int):
             "forward_only": {"value": 1.0 / fw[0], "unit": "frame-pairs/s",
                              "sample": f"eval-mode forward of the same pair: median of {samples} after 2 warm-ups = {fw[0]:.2f} s "
                                        f"(min {fw[1]:.2f}, max {fw[2]:.2f})"}}
+
+
+def dump_outputs(out_dir: str, model, loss) -> None:
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy.  Only the rows the engine wrote: a sample's flow rows at
+    and beyond counts0[b] are never written (their content is whatever the allocator held), so they are not part of the output."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    st = model.last_state
+    m0 = st["counts0"].tolist()
+    arrays = {
+        "loss": loss.detach().double().reshape(1),
+        "counts0": st["counts0"].double(),
+        "flow": torch.cat([st["flow"][b, :m0[b]] for b in range(len(m0))]).float(),
+        "pc0_valid_point_idxes": torch.cat([st["idx_c0"][b, :m0[b]] for b in range(len(m0))]).double(),
+        "model_state": torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()]),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
+def headline_line(args, world, dt, loss, n_batches) -> dict:
+    """the headline JSON line of the timed steps (a plain run prints this; --full adds its extras to it)"""
+    out = {
+        "metric": METRIC,
+        "value": world * args.batch * args.steps / dt, "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        # every tensor, accumulator, statistic and the optimizer are fp32; what the GEMMs multiply with (round 3): the 3x3 stride-1
+        # convs and weight gradients as two scaled fp16 planes per operand (22 significant bits, three MFMAs: <= 2e-6 vs float64),
+        # the GRU decoder's GEMMs as two bf16 planes (16 bits, three MFMAs: <= 2.9e-5 vs float64), everything else fp32 MFMA.
+        # DF_CONV_X3=0 DF_WGRAD_X3=0 DF_GRU_X2=0 put every GEMM back on the fp32 MFMA (107 pairs/s, round 2's step)
+        "dtype_note": ("f32 tensors and accumulation; GEMM operands: 3x3 convs fp16x2 (2 scaled fp16 planes, 3 MFMAs; between 3x3 layers the "
+                       "activations / gradients are STORED as those planes, 4 bytes per element), GRU decoder bf16x2 "
+                       "(2 bf16 planes, 3 MFMAs), other layers fp32 MFMA or fp16x2 on fragments; strict_fp32 / gru_fp32 = the same step with those forms off" if (os.environ.get("DF_CONV_X3", "1") != "0" or os.environ.get("DF_GRU_X2", "1") != "0")
+                       else "f32 tensors, accumulation and MFMA operands"),
+        "config": {"workload": WORKLOAD, "per_gpu_batch": args.batch,
+                   "global_batch": world * args.batch, "points_per_cloud": N_POINTS, "bev": [GRID, GRID], "gru_iters": NUM_ITERS,
+                   "parallelism": f"dp{world}", "loss": float(loss)},
+    }
+    out["config"]["distinct_batches_rotated"] = n_batches
+    return out
 
 
 def bind_to_gpu_numa_node(local_rank: int):
@@ -304,7 +361,7 @@ def main():
     for _ in range(args.warmup):
         trainer.step(next_batch())
     selfcheck = None
-    if use_dist:
+    if use_dist and args.full:
         # RCCL self-check before the timed region: after the arena broadcast and the warm-up steps (each rank on its OWN shard, the
         # gradients all-reduced) the parameter arena must be BIT-IDENTICAL on every rank -- a wrong scaling curve is then diagnosable
         # from the one line.  Two 64-bit digests of the arena's bit pattern per rank, all-gathered.
@@ -314,7 +371,7 @@ def main():
         dist.all_gather(alld, dgst)
         selfcheck = {"params_bit_identical_across_ranks_after_warmup": bool(all(torch.equal(a, alld[0]) for a in alld)),
                      "steps_checked": args.warmup, "numa_node": numa}
-    prof = None if args.no_profile else ops.KernelProfiler()
+    prof = None if (args.no_profile or not args.full) else ops.KernelProfiler()
     ops.PROFILER = prof
     dt, dt_local, loss = timed_steps(args.steps)       # THE timed region: exactly --steps steps between barriers
     ops.PROFILER = None
@@ -326,6 +383,20 @@ def main():
         per_rank = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(per_rank, mine)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
+    if not args.full:       # a plain run: the headline only
+        if rank == 0:
+            out = headline_line(args, world, dt, loss, len(batches))
+            if per_rank is not None:
+                out["rccl_ranks"] = [int(x[1].item()) for x in per_rank]
+                out["per_rank_ms_per_step"] = {"min": min(float(x[0]) for x in per_rank), "max": max(float(x[0]) for x in per_rank)}
+            if share_gpu:
+                out["collective_backend"] = "gloo, all ranks on cuda:0 (DF_BENCH_SHARE_GPU test hook: not a measurement)"
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # ---- everything below the timed region is an EXTRA.  At N > 1 each extra leg runs under a wall-clock budget (DF_BENCH_LEG_BUDGET
     # seconds per leg, default 240): a leg that hangs -- a collective one rank never joins, a capture that deadlocks on first contact with
@@ -478,24 +549,7 @@ def main():
         return
 
     ms = dt / args.steps * 1e3
-    out = {
-        "metric": METRIC,
-        "value": world * args.batch * args.steps / dt, "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        # every tensor, accumulator, statistic and the optimizer are fp32; what the GEMMs multiply with (round 3): the 3x3 stride-1
-        # convs and weight gradients as two scaled fp16 planes per operand (22 significant bits, three MFMAs: <= 2e-6 vs float64),
-        # the GRU decoder's GEMMs as two bf16 planes (16 bits, three MFMAs: <= 2.9e-5 vs float64), everything else fp32 MFMA.
-        # DF_CONV_X3=0 DF_WGRAD_X3=0 DF_GRU_X2=0 put every GEMM back on the fp32 MFMA (107 pairs/s, round 2's step)
-        "dtype_note": ("f32 tensors and accumulation; GEMM operands: 3x3 convs fp16x2 (2 scaled fp16 planes, 3 MFMAs; between 3x3 layers the "
-                       "activations / gradients are STORED as those planes, 4 bytes per element), GRU decoder bf16x2 "
-                       "(2 bf16 planes, 3 MFMAs), other layers fp32 MFMA or fp16x2 on fragments; strict_fp32 / gru_fp32 = the same step with those forms off" if (os.environ.get("DF_CONV_X3", "1") != "0" or os.environ.get("DF_GRU_X2", "1") != "0")
-                       else "f32 tensors, accumulation and MFMA operands"),
-        "config": {"workload": WORKLOAD, "per_gpu_batch": args.batch,
-                   "global_batch": world * args.batch, "points_per_cloud": N_POINTS, "bev": [GRID, GRID], "gru_iters": NUM_ITERS,
-                   "parallelism": f"dp{world}", "loss": float(loss)},
-    }
-    out["config"]["distinct_batches_rotated"] = len(batches)
+    out = headline_line(args, world, dt, loss, len(batches))
     try:
         # what the persistent BEV canvas saved / paid between two consecutive (different) batches: cells occupied now, cells that had
         # to be re-zeroed because they were occupied by the previous batch only -- read off the band kernels' occupancy words

@@ -1603,14 +1603,14 @@ def test_resume_continues_the_run_exactly(dev, tmp_path, capsys):
 
 
 def test_bench_line_contract(dev):
-    """`python bench.py` (2 steps) prints ONE JSON line carrying what the round contract and the verdict ask for: metric /
+    """`python bench.py --full` (2 steps) prints ONE JSON line carrying what the round contract and the verdict ask for: metric /
     value / n_gpus / steps / warmup / ms_per_step consistent with each other, `roofline` with a frac in (0, 1], the
     HBM-bound stages, the forward-only and bf16 blocks -- so a broken bench is caught by the test run, not by the driver."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-loader"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-loader"],
                        capture_output=True, text=True, cwd=root, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1641,6 +1641,33 @@ def test_bench_line_contract(dev):
     assert "cpu_baseline" not in d   # --no-cpu-baseline
 
 
+def test_bench_plain_line_and_dumped_outputs(dev, tmp_path):
+    """a plain `python bench.py` (no --full) times exactly --steps steps and prints the headline only; --dump-outputs writes the
+    last timed step's results as float32 / float64 .npy files (64 MB at most) that agree with the line"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, cwd=root, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frame-pairs/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_hbm", "forward_only", "bf16_training", "hip_graph", "strict_fp32", "cpu_baseline", "pillar_canvas"):
+        assert k not in d, k
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path) if f.endswith(".npy")}
+    assert set(files) == {"loss", "counts0", "flow", "pc0_valid_point_idxes", "model_state"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 2 ** 20
+    assert float(files["loss"][0]) == pytest.approx(d["config"]["loss"], rel=1e-6)
+    n = int(files["counts0"].sum())
+    assert files["counts0"].shape == (16,) and files["flow"].shape == (n, 3) and files["pc0_valid_point_idxes"].shape == (n,)
+    assert np.isfinite(files["flow"]).all() and np.isfinite(files["model_state"]).all()
+
+
 @pytest.mark.slow
 def test_bench_hung_extra_leg_still_prints_the_headline(dev):
     """at N > 1 every extra leg behind the timed region runs under a wall-clock budget; a leg that hangs (test hook:
@@ -1651,7 +1678,7 @@ def test_bench_hung_extra_leg_still_prints_the_headline(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DF_BENCH_SHARE_GPU="1", DF_BENCH_TEST_HANG="one_bucket", DF_BENCH_LEG_BUDGET="20")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2"],
                        capture_output=True, text=True, cwd=root, timeout=600, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:] + r.stderr[-2500:]
@@ -1672,7 +1699,7 @@ def test_bench_two_ranks_share_the_gpu(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DF_BENCH_SHARE_GPU="1")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, cwd=root, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,8 +1,8 @@
 # Round profile artefacts on the GPU box (run through gpurun; results land in gpurun_out/<TAG>_*; copy what is to be judged
 # into profiles/).  usage: bash tools/prof_round.sh r02
-#   1. rocprofv3 --kernel-trace --stats of `python bench.py` (the DEFAULT command: training region + the forward-only /
+#   1. rocprofv3 --kernel-trace --stats of `python bench.py --full` (training region + the forward-only /
 #      bf16 extras) -> <TAG>_full_kernel_stats.txt, <TAG>_bench.json (the JSON line printed under the profiler)
-#   2. the same with --no-extras --no-cpu-baseline: training launches only -> <TAG>_train_kernel_stats.txt (this is the table
+#   2. the same with --full --no-extras --no-cpu-baseline: training launches only -> <TAG>_train_kernel_stats.txt (this is the table
 #      whose per-kernel averages must agree with the HIP-event figures in the bench line's `roofline`)
 #   3. the training step with dtype=bf16 only -> <TAG>_bf16_train_kernel_stats.txt
 #   4. two separate PMC passes (FETCH_SIZE, WRITE_SIZE; kernel-trace only, as the pool requires) -> HBM bytes per launch
@@ -12,10 +12,10 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 stats() { python $R/tools/rocpd_stats.py $(find $1 -name "*.db" | head -1); }
-DF_BENCH_NO_SUBPROC=1 rocprofv3 --kernel-trace --stats -d /tmp/kt_full -o kt -- python $R/bench.py --no-loader > /tmp/kt_full.log 2>&1   # (the fresh-process legs -- strict_fp32, gru_fp32, loader_fed, the MFMA probe -- are not traced)
+DF_BENCH_NO_SUBPROC=1 rocprofv3 --kernel-trace --stats -d $TMPDIR/kt_full -o kt -- python $R/bench.py --full --no-loader > $TMPDIR/kt_full.log 2>&1   # (the fresh-process legs -- strict_fp32, gru_fp32, loader_fed, the MFMA probe -- are not traced)
 stats /tmp/kt_full > $O/${TAG}_full_kernel_stats.txt 2>&1
 grep "^{\"metric\"" /tmp/kt_full.log | tail -1 > $O/${TAG}_bench.json
-rocprofv3 --kernel-trace --stats -d /tmp/kt_train -o kt -- python $R/bench.py --no-extras --no-cpu-baseline > /tmp/kt_train.log 2>&1
+rocprofv3 --kernel-trace --stats -d $TMPDIR/kt_train -o kt -- python $R/bench.py --full --no-extras --no-cpu-baseline > $TMPDIR/kt_train.log 2>&1
 stats /tmp/kt_train > $O/${TAG}_train_kernel_stats.txt 2>&1
 grep "^{\"metric\"" /tmp/kt_train.log | tail -1 > $O/${TAG}_train_bench.json
 cat > /tmp/bf16_train.py <<'PY'
