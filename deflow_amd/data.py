@@ -86,6 +86,9 @@ class HDF5Dataset:
                         flow_category_indices=t(g0["flow_category_indices"]))
         if "ego_motion" in g0:
             item["ego_motion"] = t(g0["ego_motion"])
+        if "label" in g0 and "label" in g1:      # cluster labels of the self-supervised mode (upstream's process.py: DUFO + HDBSCAN; 0 = static)
+            item["label0"] = t(g0["label"]).reshape(-1).long()
+            item["label1"] = t(g1["label"]).reshape(-1).long()
         if "eval_mask" in g0:          # the benchmark's point mask of the official validation split
             item["eval_mask"] = t(g0["eval_mask"]).reshape(-1).bool()
         return item
@@ -113,6 +116,12 @@ def collate_fn_pad(batch: List[Dict[str, object]]) -> Dict[str, object]:
         res["flow"] = _pad([b["flow"][k].float() for b, k in zip(batch, keep0)], float("nan"))
         res["flow_is_valid"] = _pad([b["flow_is_valid"][k] for b, k in zip(batch, keep0)], False)
         res["flow_category_indices"] = _pad([b["flow_category_indices"][k] for b, k in zip(batch, keep0)], 0)
+    if all("label0" in b and "label1" in b for b in batch):
+        # seflowLoss's batch keys (upstream's names, recalled): ground rows dropped like the points, padded rows 0; max_label (a Python
+        # int, known here for free) sizes the loss's per-label tables without a device read-back
+        res["pc0_dynamic"] = _pad([b["label0"][k].long() for b, k in zip(batch, keep0)], 0)
+        res["pc1_dynamic"] = _pad([b["label1"][k].long() for b, k in zip(batch, keep1)], 0)
+        res["max_label"] = int(max(int(res["pc0_dynamic"].max()), int(res["pc1_dynamic"].max()), 0))
     if "ego_motion" in batch[0]:
         res["ego_motion"] = torch.stack([b["ego_motion"].float() for b in batch])
     if any("eval_mask" in b for b in batch):

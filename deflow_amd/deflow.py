@@ -110,6 +110,7 @@ class DeFlow(nn.Module):
         super().__init__()
         self.embedder = DynamicEmbedder(voxel_size=voxel_size, pseudo_image_dims=grid_feature_size,
                                         point_cloud_range=point_cloud_range, feat_channels=32)
+        self.point_cloud_range = [float(v) for v in point_cloud_range]   # (the grid of the seflowLoss searches is laid over it)
         self.backbone = FastFlow3DUNet(align_corners=align_corners)
         if decoder_option == "gru":
             self.head = ConvGRUDecoder(num_iters=num_iters)

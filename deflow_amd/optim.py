@@ -13,6 +13,7 @@ Semantics = torch.optim.Adam(params, lr) defaults (no weight decay, no amsgrad) 
 """
 from __future__ import annotations
 
+import functools
 import os
 
 from typing import Dict, List, Optional
@@ -271,12 +272,24 @@ class FlatAdam:
 
 class Trainer:
     """One data-parallel DeFlow training step: forward (HIP) -> gt gather + deflowLoss (HIP) -> backward (HIP) ->
-    all-reduce of the gradient arena (RCCL over xGMI via torch.distributed, or gloo in CPU tests) -> Adam (HIP)."""
+    all-reduce of the gradient arena (RCCL over xGMI via torch.distributed, or gloo in CPU tests) -> Adam (HIP).
+    loss_fn="seflowLoss": the self-supervised loss instead (no ground-truth flow: cluster labels in batch["pc0_dynamic"] /
+    ["pc1_dynamic"]; losses.seflow_loss over the HIP nearest-neighbour searches of csrc/chamfer.hip)."""
 
     def __init__(self, model: nn.Module, lr: float = 2e-4, process_group=None, loss_fn: str = "deflowLoss",
-                 gradient_clip_val: float = 0.0, sync_bn: bool = False, dtype: str = "fp32"):
-        if loss_fn not in ("deflowLoss", "ff3dLoss", "zeroflowLoss"):
+                 gradient_clip_val: float = 0.0, sync_bn: bool = False, dtype: str = "fp32", loss_args: Optional[dict] = None):
+        if loss_fn not in ("deflowLoss", "ff3dLoss", "zeroflowLoss", "seflowLoss"):
             raise ValueError(f"unknown loss_fn {loss_fn!r}")
+        # seflowLoss (self-supervised: labels of dynamic clusters instead of ground-truth flow, losses.seflow_loss): its constants --
+        # weights (4-tuple), min_dynamic, truncate_dist, max_label (table size when the batch does not carry one) -- default to upstream's
+        self.loss_args = dict(loss_args or {})
+        unknown = set(self.loss_args) - {"weights", "min_dynamic", "truncate_dist", "max_label"}
+        if unknown:
+            raise ValueError(f"unknown loss_args {sorted(unknown)} (weights, min_dynamic, truncate_dist, max_label)")
+        if self.loss_args and loss_fn != "seflowLoss":
+            raise ValueError("loss_args are the constants of loss_fn='seflowLoss'")
+        self.last_loss_terms: Optional[torch.Tensor] = None      # [B,4] terms of the last seflowLoss step, on the device
+        self.last_label_overflow: Optional[torch.Tensor] = None  # i32[1]: rows of that step whose label exceeded max_label
         if dtype not in ("fp32", "bf16"):
             raise ValueError(f"unknown dtype {dtype!r} (fp32, bf16)")
         # dtype="bf16" (BASELINE configs[4] "bf16 MFMA"; Lightning's precision="bf16-mixed"): every GEMM-shaped kernel -- the
@@ -308,10 +321,38 @@ class Trainer:
         self.sink = GradSink(self.flat, self.dist, process_group, self.world, self.collective)
         model._grad_sink = self.sink
 
+    def _seflow(self, batch, st, flow) -> torch.Tensor:
+        """seflowLoss on the state of the last forward (sync-free): labels gathered to the compact order of the two clouds, the grid
+        of the searches laid over the model's own range"""
+        from . import losses
+        from .chamfer import chamfer_nn
+        l0, l1 = batch.get("pc0_dynamic"), batch.get("pc1_dynamic")
+        if l0 is None or l1 is None:
+            raise ValueError("loss_fn=seflowLoss needs batch['pc0_dynamic'] and batch['pc1_dynamic'] (cluster labels per point; "
+                             "0 = static): scene files with a per-sweep 'label' dataset, or synth.synth_cluster_labels")
+        p0, p1 = st["p0"], st["p1"]
+        dev = flow.device
+        gather = lambda l, ix: torch.gather(l.to(device=dev, dtype=torch.int64), 1, ix.clamp(0, l.shape[1] - 1))
+        lab0, lab1 = gather(l0, p0.idx_c), gather(l1, p1.idx_c)
+        args = dict(self.loss_args)
+        max_label = batch.get("max_label", args.pop("max_label", 1024))
+        nn_fn = chamfer_nn
+        rg = getattr(self.model, "point_cloud_range", None)
+        if rg is not None and len(rg) == 6:
+            nn_fn = functools.partial(chamfer_nn, grid_range=(float(rg[0]), float(rg[1]), float(rg[3]), float(rg[4])))
+        stats: dict = {}
+        loss, terms = losses.seflow_loss(p0.points_c, p1.points_c, flow, p0.counts, p1.counts, lab0, lab1, nn_fn=nn_fn,
+                                         max_label=int(max_label), stats=stats, **args)
+        self.last_loss_terms = terms.detach()
+        self.last_label_overflow = stats["label_overflow"]
+        return loss
+
     def loss_on_last_forward(self, batch) -> torch.Tensor:
         from .autograd import DeflowLossFn
         st = self.model.last_state
         flow = st["flow"]
+        if self.loss_fn == "seflowLoss":
+            return self._seflow(batch, st, flow)
         B, N, _ = flow.shape
         gt = torch.empty(B, N, 3, dtype=torch.float32, device=flow.device)
         gtf = batch["flow"].contiguous().float()
@@ -515,6 +556,15 @@ class Trainer:
             flow = st["flow"]
             B, N, _ = flow.shape
             dev = flow.device
+            if self.loss_fn == "seflowLoss":
+                # no ground truth: the loss is losses.seflow_loss (HIP searches, sync-free reductions) and d(flow) its gradient, taken
+                # right here -- the same operations, in the same order, as the autograd route's loss.backward()
+                with torch.enable_grad():
+                    leaf = flow.detach().requires_grad_(True)
+                    loss = self._seflow(batch, st, leaf)
+                    dflow, = torch.autograd.grad(loss, leaf)
+                deflow_backward(model, st.pop("engine"), dflow.contiguous(), self.flat.params, self.sink)
+                return loss.detach()
             gt = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
             gtf = batch["flow"].contiguous().float()
             call("df_gather_gt", ptr(gtf), ptr(st["pose_flow"]), ptr(st["idx_c0"]), ptr(st["counts0"]), B, N, ptr(gt), 64, stream())

@@ -123,3 +123,31 @@ def synth_batch(batch_size: int, n: int, seed: int = 20240116, grid_hw=(512, 512
         "ego_motion": torch.stack([p[2] for p in pairs]).to(device),
         "flow": torch.stack([p[3] for p in pairs]).to(device),
     }
+
+
+def synth_cluster_labels(batch: Dict[str, torch.Tensor], tile: float = 12.8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Cluster labels for the self-supervised loss (losses.seflow_loss) on a synth_batch: -> pc0_dynamic, pc1_dynamic [B,N] int64.
+    A row is dynamic when its ground-truth flow minus the ego motion's share is longer than 0.05 m; a dynamic row's label is 1 + the
+    index of the `tile`-metre xy tile its pc0 point lies in (tiles counted row-major from the most negative corner of the smallest
+    square of whole tiles around the origin that holds every finite pc0 row of +-51.2 m; rows outside go to the border tiles); static,
+    padded and NaN rows get 0.  pc1 row i takes pc0 row i's label: the generator makes the rows correspond.  The largest possible
+    label is synth_max_label(tile).  Pure elementwise arithmetic on the batch's own device: deterministic per seed."""
+    pc0, flow = batch["pc0"], batch["flow"]
+    T = batch["ego_motion"].to(pc0.dtype)
+    moved = pc0 @ T[:, :3, :3].transpose(1, 2) + T[:, None, :3, 3]
+    resid = flow - (moved - pc0)
+    ok = torch.isfinite(pc0).all(-1) & torch.isfinite(batch["pc1"]).all(-1) & torch.isfinite(resid).all(-1)
+    dyn = ok & (torch.linalg.vector_norm(torch.where(ok[..., None], resid, torch.zeros_like(resid)), dim=-1) > 0.05)
+    n = _tiles_per_side(tile)
+    xy = torch.where(ok[..., None], pc0[..., :2], torch.zeros_like(pc0[..., :2]))
+    t = torch.floor(xy / tile + n / 2).clamp(0, n - 1).long()
+    lab = torch.where(dyn, 1 + t[..., 1] * n + t[..., 0], torch.zeros_like(t[..., 0]))
+    return lab, lab.clone()
+
+
+def _tiles_per_side(tile: float) -> int:
+    return 2 * int(math.ceil(51.2 / tile - 1e-9))
+
+
+def synth_max_label(tile: float = 12.8) -> int:
+    return _tiles_per_side(tile) ** 2

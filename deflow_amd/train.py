@@ -94,8 +94,8 @@ def parse_overrides(argv: List[str]) -> Dict[str, Any]:
         raise SystemExit(f"unknown model {cfg['model']!r}")
     if cfg["model"] == "fastflow3d":
         cfg["model.target.decoder_option"] = "linear"
-    if cfg["loss_fn"] not in ("deflowLoss", "ff3dLoss", "zeroflowLoss"):
-        raise SystemExit(f"unknown loss_fn {cfg['loss_fn']!r} (deflowLoss, ff3dLoss, zeroflowLoss)")
+    if cfg["loss_fn"] not in ("deflowLoss", "ff3dLoss", "zeroflowLoss", "seflowLoss"):
+        raise SystemExit(f"unknown loss_fn {cfg['loss_fn']!r} (deflowLoss, ff3dLoss, zeroflowLoss, seflowLoss)")
     gfs = cfg.pop("_grid_feature_size", None)
     if gfs is not None and list(gfs) != grid_from(cfg):
         raise SystemExit(f"model.target.grid_feature_size={gfs} does not match voxel_size / point_cloud_range ({grid_from(cfg)})")
@@ -138,7 +138,7 @@ def main(argv=None):
             dist.init_process_group(str(cfg["dist_backend"]), rank=rank, world_size=world)
     from deflow_amd.metrics import evaluate_batch
     from deflow_amd.optim import Trainer
-    from deflow_amd.synth import synth_batch
+    from deflow_amd.synth import synth_batch, synth_cluster_labels
 
     torch.manual_seed(int(cfg["seed"]))
     model = build_model(cfg).to(dev)
@@ -175,7 +175,10 @@ def main(argv=None):
     def synthetic_epoch(epoch):
         for it in range(steps_per_epoch):
             seed = Trainer.shard_seed(int(cfg["seed"]) + (epoch * steps_per_epoch + it) * B * world, rank, B)
-            yield synth_batch(B, N, seed=seed, grid_hw=(H, H), device=dev)
+            sb = synth_batch(B, N, seed=seed, grid_hw=(H, H), device=dev)
+            if cfg["loss_fn"] == "seflowLoss":      # self-supervised: cluster labels instead of the ground-truth flow
+                sb["pc0_dynamic"], sb["pc1_dynamic"] = synth_cluster_labels(sb)
+            yield sb
 
     steps_per_epoch = max(1, int(cfg["pairs_per_epoch"]) // (B * world))
     train_loader = val_loader = None
@@ -212,8 +215,12 @@ def main(argv=None):
             if rank == 0 and gstep % int(cfg["log_every"]) == 0:
                 lv = float(loss)  # reads the loss back: the only host sync of the loop, so the rate below is a true one
                 now = time.perf_counter()
-                print(json.dumps({"epoch": epoch, "step": gstep, "trainer/loss": lv / B,
-                                  "pairs_per_s": B * world * (gstep - log_step) / (now - log_t)}), flush=True)
+                line = {"epoch": epoch, "step": gstep, "trainer/loss": lv / B,
+                        "pairs_per_s": B * world * (gstep - log_step) / (now - log_t)}
+                if trainer.last_loss_terms is not None:      # seflowLoss: its four terms, mean over the batch
+                    names = ("chamfer_dis", "dynamic_chamfer_dis", "static_flow_loss", "cluster_flow_loss")
+                    line.update({"trainer/" + k: v for k, v in zip(names, trainer.last_loss_terms.mean(0).tolist())})
+                print(json.dumps(line), flush=True)
                 log_t, log_step = now, gstep
         trainer.sync_buffers()         # every rank validates (and rank 0 saves) rank 0's BatchNorm statistics, as DDP does
         model.eval()

@@ -559,6 +559,33 @@ int df_wloss_bwd(const float* est, const float* gt, const int32_t* counts, int B
 int df_gather_gt(const float* flow, const float* pose_flow, const int64_t* idx_c, const int32_t* counts,
                  int B, int N, float* gt, int nblk, void* stream);
 
+/* ------------------------------------------------------------------ chamfer nearest neighbour (SeFlow losses) ----
+ * The counterpart of the reference's chamfer3D extension [REF README.md:39] (UNPINNED: its source is in the absent submodule), as a
+ * grid search instead of upstream's all-pairs kernel.  Batched and padded: query [B,Nq,3] f32 with qcount [B] i32 valid leading rows,
+ * ref [B,Nr,3] f32 with rcount [B]; optional row labels (i32, [B,Nq] / [B,Nr]): when given only rows with label > 0 take part.
+ * Non-finite rows do not take part.
+ * df_nn_grid_build: the participating ref rows in a uniform xy grid of G x G cells of `cell` metres from (minx, miny) per sample (rows
+ *   outside go to the clamped border cells; z is not binned): cell_rng [B*G*G, 2] i32 = [start, end) of each cell in `sorted`
+ *   [B*Nr, 4] f32 = (x, y, z, bits of the row index), rows of a cell in ascending row order.  ws: df_nn_grid_ws_bytes(B, Nr, G).
+ * df_chamfer_nn: d2 [B,Nq] f32 = smallest squared distance (differences formed in fp32) from each participating query row to a
+ *   participating ref row of its sample, idx [B,Nq] i32 = that row (lowest index on equal distances); d2 = +inf, idx = -1 where that
+ *   distance exceeds max_dist2 (+inf allowed: exact unbounded search), no ref row participates or the query row does not.
+ *   far_count (nullable, i32[1], integer atomic add): queries whose search went past the 3 x 3 cells around their own.
+ * df_chamfer_bwd: for d2[i] = |query_i - ref[idx_i]|^2 and g [B,Nq] = d loss / d d2 (rows with idx < 0 are skipped):
+ *   dquery [B,Nq,3] += 2 g_i (query_i - ref[idx_i]);  dref [B,Nr,3] += sum over i with idx_i == k of 2 g_i (ref_k - query_i), the
+ *   pairs segmented by k and summed in ascending i (no float atomics: repeated calls are bit-identical).  Either output may be
+ *   NULL; ws (needed for dref): df_chamfer_bwd_ws_bytes(B, Nq, Nr).
+ * B * Nq, B * Nr, B * G * G < 2^30 (32-bit keys and sorted positions), G <= 4096, B <= 65535; violations return DF_E_SHAPE. */
+int64_t df_nn_grid_ws_bytes(int B, int Nr, int G);
+int df_nn_grid_build(const float* ref, const int32_t* rcount, const int32_t* rlabel /*nullable*/, int B, int Nr, float minx, float miny,
+                     float cell, int G, int32_t* cell_rng, float* sorted, void* ws, void* stream);
+int df_chamfer_nn(const float* query, const int32_t* qcount, const int32_t* qlabel /*nullable*/, int B, int Nq, const int32_t* cell_rng,
+                  const float* sorted, float minx, float miny, float cell, int G, float max_dist2, float* d2, int32_t* idx,
+                  int32_t* far_count /*nullable*/, void* stream);
+int64_t df_chamfer_bwd_ws_bytes(int B, int Nq, int Nr);
+int df_chamfer_bwd(const float* query, const float* ref, const int32_t* idx, const float* g, int B, int Nq, int Nr, float* dquery,
+                   float* dref, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
