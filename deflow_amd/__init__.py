@@ -4,3 +4,4 @@ from .encoder import DynamicEmbedder  # noqa: F401
 from .unet import ConvWithNorms, FastFlow3DUNet  # noqa: F401
 from .decoder import ConvGRU, ConvGRUDecoder, LinearDecoder  # noqa: F401
 from .timer import Timing  # noqa: F401
+from .cluster import dbscan, dynamic_cluster_labels  # noqa: F401

@@ -1,0 +1,111 @@
+"""DBSCAN on the GPU and, on top of it, the cluster labels of the self-supervised SeFlow mode (``pc0_dynamic`` / ``pc1_dynamic``) from a
+per-point dynamic flag alone.
+
+UNPINNED: upstream produces these labels offline on the CPU ([REF assets/slurm/dufolabel_sbatch.py]; process.py: DUFO dynamic flags, then
+HDBSCAN, whose source is in the absent submodule).  What runs here is plain DBSCAN with every choice fixed -- the definition is in
+include/deflow_amd.h and DESIGN.md section 6b -- so the labels are a pure function of the input and bit-reproducible.  Of the defaults,
+``eps = 0.7`` and ``min_cluster_size = 20`` are the recalled arguments of upstream's HDBSCAN call; ``min_points = 4`` and
+``min_dynamic_frac = 0.3`` are this project's own choices.  All four are arguments.  The DUFO flags themselves stay out of scope.
+
+CUDA tensors only, like the rest of the library: there is no CPU fallback.  Nothing here reads a device value back."""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from ._lib import call, ptr, stream
+from .chamfer import GRID_RANGE, _grid
+
+# cell = max(CELL_SLACK * eps, extent / 4096): with cell >= eps the 3 x 3 cells around a row hold every row within eps.  The slack covers
+# the rounding of the cell coordinates (< 1e-3 cell at G <= 4096, the bound csrc/chamfer.hip's search uses): two rows eps apart in x never
+# land two cells apart.  The range and the cell only decide the speed, never the result.
+CELL_SLACK = 1.0025
+
+
+def _check(name: str, t: torch.Tensor, shape, dtype):
+    if not t.is_cuda:
+        raise TypeError(f"dbscan: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"dbscan: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def _flags(name: str, f: Optional[torch.Tensor], shape) -> Optional[torch.Tensor]:
+    """a per-row flag (bool or integer, non-zero = set) as the i32 0 / 1 tensor the kernels read"""
+    if f is None:
+        return None
+    if not f.is_cuda:
+        raise TypeError(f"dbscan: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    if tuple(f.shape) != tuple(shape) or f.dtype.is_floating_point:
+        raise ValueError(f"dbscan: {name} must be a bool or integer CUDA tensor of shape {tuple(shape)}")
+    return (f != 0).to(torch.int32).contiguous()
+
+
+def _run(points: torch.Tensor, count: torch.Tensor, mask, dynamic, eps: float, min_points: int, min_cluster_size: int,
+         min_dynamic_frac: float, grid_range, status: Optional[torch.Tensor]):
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise ValueError(f"dbscan: points [B,N,3] expected, got {tuple(points.shape)}")
+    B, N, _ = points.shape
+    if B == 0 or N == 0:
+        raise ValueError("dbscan: empty batch or zero padded rows")
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"dbscan: eps must be a positive finite radius, got {eps}")
+    if int(min_points) < 1 or int(min_cluster_size) < 1:
+        raise ValueError(f"dbscan: min_points and min_cluster_size must be >= 1, got {min_points} and {min_cluster_size}")
+    if not (min_dynamic_frac >= 0 and math.isfinite(min_dynamic_frac)):
+        raise ValueError(f"dbscan: min_dynamic_frac must be a finite fraction >= 0, got {min_dynamic_frac}")
+    _check("points", points, (B, N, 3), torch.float32)
+    _check("count", count, (B,), torch.int32)
+    if status is not None:
+        _check("status", status, (1,), torch.int32)
+    points = points.detach().contiguous()
+    m, d = _flags("mask", mask, (B, N)), _flags("dynamic", dynamic, (B, N))
+    rg = GRID_RANGE if grid_range is None else grid_range
+    xmin, ymin, xmax, ymax = (float(v) for v in rg)
+    cell = max(CELL_SLACK * float(eps), max(xmax - xmin, ymax - ymin) / 4096.0)
+    minx, miny, G = _grid(B, rg, cell)
+    dev = points.device
+    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
+    rows = torch.empty(B * N, 4, dtype=torch.float32, device=dev)
+    gws = torch.empty(call("df_nn_grid_ws_bytes", B, N, G), dtype=torch.uint8, device=dev)
+    ws = torch.empty(call("df_dbscan_ws_bytes", B, N), dtype=torch.uint8, device=dev)
+    labels = torch.empty(B, N, dtype=torch.int32, device=dev)
+    n_clusters = torch.empty(B, dtype=torch.int32, device=dev)
+    s = stream()
+    call("df_nn_grid_build", ptr(points), ptr(count), ptr(m), B, N, minx, miny, cell, G, ptr(cell_rng), ptr(rows), ptr(gws), s)
+    call("df_dbscan_core", ptr(cell_rng), ptr(rows), B, N, minx, miny, cell, G, float(eps), int(min_points), ptr(ws), s)
+    call("df_dbscan_link", ptr(cell_rng), B, N, minx, miny, cell, G, float(eps), ptr(status), ptr(ws), s)
+    call("df_dbscan_finish", ptr(cell_rng), ptr(d), B, N, minx, miny, cell, G, float(eps), int(min_cluster_size), float(min_dynamic_frac),
+         ptr(labels), ptr(n_clusters), ptr(status), ptr(ws), s)
+    return labels, n_clusters
+
+
+def dbscan(points: torch.Tensor, count: torch.Tensor, mask: Optional[torch.Tensor] = None, *, eps: float = 0.7, min_points: int = 4,
+           min_cluster_size: int = 1, grid_range: Optional[Sequence[float]] = None, status: Optional[torch.Tensor] = None
+           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """points [B,N,3] f32 with count [B] i32 valid leading rows; optional mask [B,N] (bool or integer): only rows with mask != 0 take
+    part; non-finite rows never take part.
+    -> labels [B,N] i32 (0 = noise or not participating, clusters 1..K per sample in ascending order of their lowest core row),
+    n_clusters [B] i32.  A row is core with >= min_points rows within eps (itself included); border rows join the cluster of their
+    nearest core row (the lowest row on equal distances); clusters of fewer than min_cluster_size members are dropped to 0.
+    grid_range (xmin, ymin, xmax, ymax): where the rows are expected, default the +-51.2 m of the model; it decides only the speed.
+    status: optional i32[1] the kernels add to when one of their bounded loops reaches its bound (never, on a sane input).
+    No host synchronisation; two calls are bit-identical."""
+    return _run(points, count, mask, None, eps, min_points, min_cluster_size, 0.0, grid_range, status)
+
+
+def dynamic_cluster_labels(points: torch.Tensor, count: torch.Tensor, dynamic: torch.Tensor, *, eps: float = 0.7, min_points: int = 4,
+                           min_cluster_size: int = 20, min_dynamic_frac: float = 0.3, grid_range: Optional[Sequence[float]] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The labels seflowLoss wants from a per-point dynamic flag [B,N] (bool or integer, e.g. upstream's DUFO flag): ALL participating
+    rows are clustered (dbscan above), and a cluster is kept when it has >= min_cluster_size members of which at least
+    min_dynamic_frac are flagged (flagged < min_dynamic_frac * members, in float64, drops it).
+    -> labels [B,N] i32, n_clusters [B] i32, status i32[1] (see dbscan; left on the device)."""
+    if dynamic is None:
+        raise ValueError("dynamic_cluster_labels: the per-row dynamic flag is required (dbscan clusters without one)")
+    if not points.is_cuda:
+        raise TypeError("dbscan: points must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    status = torch.zeros(1, dtype=torch.int32, device=points.device)
+    labels, n_clusters = _run(points, count, None, dynamic, eps, min_points, min_cluster_size, min_dynamic_frac, grid_range, status)
+    return labels, n_clusters, status

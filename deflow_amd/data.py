@@ -33,11 +33,16 @@ from .h5scene import H5File
 
 
 class HDF5Dataset:
-    def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False):
-        """``eval=True`` (the evaluation entry): read ``index_eval.pkl`` -- the frames of the official validation benchmark, the ones
+    def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False, dynamic_key: str = "dufo_label"):
+        """``dynamic_key``: the per-sweep dataset holding the per-point dynamic flag (non-zero = dynamic) that online cluster labels
+        start from (``Trainer(cluster_labels=...)``).  UNPINNED: ``dufo_label`` is the name recalled from upstream's process.py (the
+        DUFO pass writes it before HDBSCAN turns it into ``label``), hence an argument.  When both sweeps of a pair hold it, the item
+        carries ``dufo0`` / ``dufo1``; files without it give the items they always gave.
+        ``eval=True`` (the evaluation entry): read ``index_eval.pkl`` -- the frames of the official validation benchmark, the ones
         that carry an ``eval_mask`` -- when the directory has one, as upstream's dataset does for ``av2_mode=val`` (recalled: the
         module is in the absent submodule); ``index_total.pkl`` lists every sweep of every scene."""
         self.directory = directory
+        self.dynamic_key = dynamic_key
         name = "index_total.pkl"
         if eval and os.path.exists(os.path.join(directory, "index_eval.pkl")):
             name = "index_eval.pkl"
@@ -89,6 +94,10 @@ class HDF5Dataset:
         if "label" in g0 and "label" in g1:      # cluster labels of the self-supervised mode (upstream's process.py: DUFO + HDBSCAN; 0 = static)
             item["label0"] = t(g0["label"]).reshape(-1).long()
             item["label1"] = t(g1["label"]).reshape(-1).long()
+        dk = self.dynamic_key
+        if dk and dk in g0 and dk in g1:         # per-point dynamic flags: the input of the online cluster labels (cluster.py)
+            item["dufo0"] = t(g0[dk]).reshape(-1) != 0
+            item["dufo1"] = t(g1[dk]).reshape(-1) != 0
         if "eval_mask" in g0:          # the benchmark's point mask of the official validation split
             item["eval_mask"] = t(g0["eval_mask"]).reshape(-1).bool()
         return item
@@ -122,6 +131,10 @@ def collate_fn_pad(batch: List[Dict[str, object]]) -> Dict[str, object]:
         res["pc0_dynamic"] = _pad([b["label0"][k].long() for b, k in zip(batch, keep0)], 0)
         res["pc1_dynamic"] = _pad([b["label1"][k].long() for b, k in zip(batch, keep1)], 0)
         res["max_label"] = int(max(int(res["pc0_dynamic"].max()), int(res["pc1_dynamic"].max()), 0))
+    if all("dufo0" in b and "dufo1" in b for b in batch):
+        # dynamic flags for Trainer(cluster_labels=...): ground rows dropped and padded rows 0, exactly like the labels
+        res["pc0_dufo"] = _pad([(b["dufo0"][k] != 0).long() for b, k in zip(batch, keep0)], 0)
+        res["pc1_dufo"] = _pad([(b["dufo1"][k] != 0).long() for b, k in zip(batch, keep1)], 0)
     if "ego_motion" in batch[0]:
         res["ego_motion"] = torch.stack([b["ego_motion"].float() for b in batch])
     if any("eval_mask" in b for b in batch):

@@ -274,10 +274,14 @@ class Trainer:
     """One data-parallel DeFlow training step: forward (HIP) -> gt gather + deflowLoss (HIP) -> backward (HIP) ->
     all-reduce of the gradient arena (RCCL over xGMI via torch.distributed, or gloo in CPU tests) -> Adam (HIP).
     loss_fn="seflowLoss": the self-supervised loss instead (no ground-truth flow: cluster labels in batch["pc0_dynamic"] /
-    ["pc1_dynamic"]; losses.seflow_loss over the HIP nearest-neighbour searches of csrc/chamfer.hip)."""
+    ["pc1_dynamic"]; losses.seflow_loss over the HIP nearest-neighbour searches of csrc/chamfer.hip).
+    cluster_labels=dict(...) (opt-in, seflowLoss only): a batch without those labels but with per-point dynamic flags
+    batch["pc0_dufo"] / ["pc1_dufo"] gets its labels inside the step from cluster.dynamic_cluster_labels (csrc/cluster.hip); the
+    dict holds that call's keyword arguments (eps, min_points, min_cluster_size, min_dynamic_frac; {} = its defaults)."""
 
     def __init__(self, model: nn.Module, lr: float = 2e-4, process_group=None, loss_fn: str = "deflowLoss",
-                 gradient_clip_val: float = 0.0, sync_bn: bool = False, dtype: str = "fp32", loss_args: Optional[dict] = None):
+                 gradient_clip_val: float = 0.0, sync_bn: bool = False, dtype: str = "fp32", loss_args: Optional[dict] = None,
+                 cluster_labels: Optional[dict] = None):
         if loss_fn not in ("deflowLoss", "ff3dLoss", "zeroflowLoss", "seflowLoss"):
             raise ValueError(f"unknown loss_fn {loss_fn!r}")
         # seflowLoss (self-supervised: labels of dynamic clusters instead of ground-truth flow, losses.seflow_loss): its constants --
@@ -290,6 +294,17 @@ class Trainer:
             raise ValueError("loss_args are the constants of loss_fn='seflowLoss'")
         self.last_loss_terms: Optional[torch.Tensor] = None      # [B,4] terms of the last seflowLoss step, on the device
         self.last_label_overflow: Optional[torch.Tensor] = None  # i32[1]: rows of that step whose label exceeded max_label
+        # online cluster labels (cluster.dynamic_cluster_labels): None = off; labels in the batch always win over flags
+        if cluster_labels is not None:
+            if not isinstance(cluster_labels, dict):
+                raise ValueError("cluster_labels must be None or a dict of dynamic_cluster_labels arguments")
+            unknown = set(cluster_labels) - {"eps", "min_points", "min_cluster_size", "min_dynamic_frac"}
+            if unknown:
+                raise ValueError(f"unknown cluster_labels arguments {sorted(unknown)} (eps, min_points, min_cluster_size, min_dynamic_frac)")
+            if loss_fn != "seflowLoss":
+                raise ValueError("cluster_labels are the online labels of loss_fn='seflowLoss'")
+        self.cluster_labels = None if cluster_labels is None else dict(cluster_labels)
+        self.last_cluster_status: Optional[torch.Tensor] = None  # i32[1]: bounded loops of the clustering kernels that hit their bound (0)
         if dtype not in ("fp32", "bf16"):
             raise ValueError(f"unknown dtype {dtype!r} (fp32, bf16)")
         # dtype="bf16" (BASELINE configs[4] "bf16 MFMA"; Lightning's precision="bf16-mixed"): every GEMM-shaped kernel -- the
@@ -327,19 +342,33 @@ class Trainer:
         from . import losses
         from .chamfer import chamfer_nn
         l0, l1 = batch.get("pc0_dynamic"), batch.get("pc1_dynamic")
-        if l0 is None or l1 is None:
+        f0, f1 = batch.get("pc0_dufo"), batch.get("pc1_dufo")
+        online = (l0 is None or l1 is None) and self.cluster_labels is not None and f0 is not None and f1 is not None
+        if (l0 is None or l1 is None) and not online:
             raise ValueError("loss_fn=seflowLoss needs batch['pc0_dynamic'] and batch['pc1_dynamic'] (cluster labels per point; "
                              "0 = static): scene files with a per-sweep 'label' dataset, or synth.synth_cluster_labels")
         p0, p1 = st["p0"], st["p1"]
         dev = flow.device
         gather = lambda l, ix: torch.gather(l.to(device=dev, dtype=torch.int64), 1, ix.clamp(0, l.shape[1] - 1))
-        lab0, lab1 = gather(l0, p0.idx_c), gather(l1, p1.idx_c)
         args = dict(self.loss_args)
-        max_label = batch.get("max_label", args.pop("max_label", 1024))
         nn_fn = chamfer_nn
         rg = getattr(self.model, "point_cloud_range", None)
+        grid = None
         if rg is not None and len(rg) == 6:
-            nn_fn = functools.partial(chamfer_nn, grid_range=(float(rg[0]), float(rg[1]), float(rg[3]), float(rg[4])))
+            grid = (float(rg[0]), float(rg[1]), float(rg[3]), float(rg[4]))
+            nn_fn = functools.partial(chamfer_nn, grid_range=grid)
+        if online:
+            # the flags gathered to compact order like labels, then clustered per compact cloud; the table size comes from loss_args
+            # (no read-back: rows of a cluster numbered past it are counted in last_label_overflow)
+            from .cluster import dynamic_cluster_labels
+            c0 = dynamic_cluster_labels(p0.points_c, p0.counts, gather(f0, p0.idx_c), grid_range=grid, **self.cluster_labels)
+            c1 = dynamic_cluster_labels(p1.points_c, p1.counts, gather(f1, p1.idx_c), grid_range=grid, **self.cluster_labels)
+            lab0, lab1 = c0[0].to(torch.int64), c1[0].to(torch.int64)
+            self.last_cluster_status = c0[2] + c1[2]
+            max_label = args.pop("max_label", 1024)
+        else:
+            lab0, lab1 = gather(l0, p0.idx_c), gather(l1, p1.idx_c)
+            max_label = batch.get("max_label", args.pop("max_label", 1024))
         stats: dict = {}
         loss, terms = losses.seflow_loss(p0.points_c, p1.points_c, flow, p0.counts, p1.counts, lab0, lab1, nn_fn=nn_fn,
                                          max_label=int(max_label), stats=stats, **args)

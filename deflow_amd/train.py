@@ -27,6 +27,9 @@ DEFAULTS: Dict[str, Any] = {
     "voxel_size": [0.2, 0.2, 6], "point_cloud_range": [-51.2, -51.2, -3, 51.2, 51.2, 3],
     "model.target.num_iters": 4, "model.target.decoder_option": "gru", "gradient_clip_val": 0.0, "sync_bn": False, "dtype": "fp32", "graph": False, "dist_backend": "nccl", "resume": False,
     "train_data": "synthetic", "val_data": "synthetic", "pairs_per_epoch": 64, "points_per_cloud": 80000,
+    # online cluster labels for loss_fn=seflowLoss (cluster.dynamic_cluster_labels): cluster_labels=online computes pc0_dynamic /
+    # pc1_dynamic inside the step from the per-point dynamic flag; the other four keys are that call's arguments (its defaults)
+    "cluster_labels": "", "cluster_eps": 0.7, "cluster_min_points": 4, "cluster_min_size": 20, "cluster_min_dynamic_frac": 0.3,
     "stage_dir": "", "checkpoint": "", "save_checkpoint": "", "seed": 20240116, "wandb_mode": "disabled", "slurm_id": "", "log_every": 50,   # Lightning's log_every_n_steps default; each log line syncs
 }
 
@@ -96,6 +99,10 @@ def parse_overrides(argv: List[str]) -> Dict[str, Any]:
         cfg["model.target.decoder_option"] = "linear"
     if cfg["loss_fn"] not in ("deflowLoss", "ff3dLoss", "zeroflowLoss", "seflowLoss"):
         raise SystemExit(f"unknown loss_fn {cfg['loss_fn']!r} (deflowLoss, ff3dLoss, zeroflowLoss, seflowLoss)")
+    if cfg["cluster_labels"] not in ("", None, "online"):
+        raise SystemExit(f"unknown cluster_labels {cfg['cluster_labels']!r} (online)")
+    if cfg["cluster_labels"] == "online" and cfg["loss_fn"] != "seflowLoss":
+        raise SystemExit("cluster_labels=online computes the labels of loss_fn=seflowLoss: set loss_fn=seflowLoss")
     gfs = cfg.pop("_grid_feature_size", None)
     if gfs is not None and list(gfs) != grid_from(cfg):
         raise SystemExit(f"model.target.grid_feature_size={gfs} does not match voxel_size / point_cloud_range ({grid_from(cfg)})")
@@ -105,6 +112,14 @@ def parse_overrides(argv: List[str]) -> Dict[str, Any]:
 def grid_from(cfg) -> List[int]:
     vs, rg = cfg["voxel_size"], cfg["point_cloud_range"]
     return [int(round((rg[4] - rg[1]) / vs[1])), int(round((rg[3] - rg[0]) / vs[0]))]
+
+
+def cluster_args(cfg):
+    """the Trainer's cluster_labels keyword from the command line's keys: None unless cluster_labels=online"""
+    if cfg.get("cluster_labels") != "online":
+        return None
+    return {"eps": float(cfg["cluster_eps"]), "min_points": int(cfg["cluster_min_points"]),
+            "min_cluster_size": int(cfg["cluster_min_size"]), "min_dynamic_frac": float(cfg["cluster_min_dynamic_frac"])}
 
 
 def build_model(cfg):
@@ -146,7 +161,7 @@ def main(argv=None):
         model.load_from_checkpoint(cfg["checkpoint"])
     model.train()
     trainer = Trainer(model, lr=float(cfg["lr"]), loss_fn=str(cfg["loss_fn"]), gradient_clip_val=float(cfg["gradient_clip_val"]),
-                      sync_bn=str(cfg["sync_bn"]).lower() in ("1", "true"), dtype=str(cfg["dtype"]))
+                      sync_bn=str(cfg["sync_bn"]).lower() in ("1", "true"), dtype=str(cfg["dtype"]), cluster_labels=cluster_args(cfg))
     start_epoch, gstep0 = 0, 0
     if cfg["checkpoint"] and str(cfg["resume"]).lower() in ("1", "true"):
         # "checkpoints also include parameters and status of that epoch" [REF README.md:76-77]: continue where it stopped --
@@ -177,7 +192,11 @@ def main(argv=None):
             seed = Trainer.shard_seed(int(cfg["seed"]) + (epoch * steps_per_epoch + it) * B * world, rank, B)
             sb = synth_batch(B, N, seed=seed, grid_hw=(H, H), device=dev)
             if cfg["loss_fn"] == "seflowLoss":      # self-supervised: cluster labels instead of the ground-truth flow
-                sb["pc0_dynamic"], sb["pc1_dynamic"] = synth_cluster_labels(sb)
+                l0, l1 = synth_cluster_labels(sb)
+                if cfg["cluster_labels"] == "online":       # only the dynamic flag: the step clusters it itself
+                    sb["pc0_dufo"], sb["pc1_dufo"] = l0 > 0, l1 > 0
+                else:
+                    sb["pc0_dynamic"], sb["pc1_dynamic"] = l0, l1
             yield sb
 
     steps_per_epoch = max(1, int(cfg["pairs_per_epoch"]) // (B * world))

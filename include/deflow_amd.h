@@ -586,6 +586,42 @@ int64_t df_chamfer_bwd_ws_bytes(int B, int Nq, int Nr);
 int df_chamfer_bwd(const float* query, const float* ref, const int32_t* idx, const float* g, int B, int Nq, int Nr, float* dquery,
                    float* dref, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ DBSCAN cluster labels (SeFlow mode) ----
+ * The cluster labels of the self-supervised mode, computed on the GPU.  UNPINNED: upstream clusters offline on the CPU (process.py:
+ * DUFO dynamic flags, then HDBSCAN, whose source is in the absent submodule); this is plain DBSCAN with every choice fixed, so that the
+ * result is a pure function of the input.  Per sample of a padded batch points [B,N,3] f32 with count [B] i32:
+ *   participating rows  i < count[b], all three coordinates finite, and mask[b,i] != 0 when a mask is given (the grid build's rlabel > 0)
+ *   neighbourhood       N(i) = the participating j with |p_i - p_j|^2 <= eps^2, i itself included; differences are formed first and then
+ *                       squared, in fp32, as df_chamfer_nn does
+ *   core rows           |N(i)| >= min_points
+ *   clusters            two core rows within eps are linked; a cluster is a connected component of core rows plus its border rows
+ *   border rows         a non-core row with a core row in N(i) joins the cluster of its nearest core row, the lowest row index on equal
+ *                       distances (df_chamfer_nn's tie rule)
+ *   noise               every other row: label 0, like the rows that do not participate
+ *   filters             a cluster of fewer than min_cluster_size members is dropped to 0; with a per-row `dynamic` flag [B,N] i32 a cluster
+ *                       is dropped too when flagged members < min_dynamic_frac * members (compared in float64)
+ *   numbering           the surviving clusters are 1..K per sample, in ascending order of their lowest core row index
+ * Defaults of the Python layer: eps = 0.7 and min_cluster_size = 20 are the recalled arguments of upstream's HDBSCAN call; min_points = 4
+ * and min_dynamic_frac = 0.3 are this project's own choices.  All four are arguments.
+ * The stages run in this order on one stream and share ws (df_dbscan_ws_bytes(B, N)), after df_nn_grid_build has filed the participating
+ * rows (ref = points, rcount = count, rlabel = mask) under a grid with cell >= eps -- the 3 x 3 cells around a row then hold its whole
+ * neighbourhood, rows outside the range included (clamping to the border cells is a contraction per coordinate):
+ * df_dbscan_core: the core flags.   df_dbscan_link: union-find over the core rows (integer compare-and-swap / min; a root is always the
+ *   lowest row of its tree, so the forest's roots do not depend on the launch order).   df_dbscan_finish: border rows, member counts
+ *   (integer atomic adds), filters, numbering: labels [B,N] i32 and n_clusters [B] i32, both written completely.
+ * status (nullable, i32[1]): every loop of the kernels is bounded (by N or 2 N); a loop that reaches its bound adds 1 here and the
+ *   kernel carries on.  It stays 0 on every input the bounds were derived for; the host never waits on it.
+ * No float atomics; repeated calls are bit-identical.  Limits as for the chamfer entries (B * N, B * G * G < 2^30, G <= 4096,
+ * B <= 65535): violations return DF_E_SHAPE; cell < eps, eps <= 0, min_points < 1, min_cluster_size < 1 return DF_E_ARG.  No launch then. */
+int64_t df_dbscan_ws_bytes(int B, int N);
+int df_dbscan_core(const int32_t* cell_rng, const float* sorted, int B, int N, float minx, float miny, float cell, int G, float eps,
+                   int min_points, void* ws, void* stream);
+int df_dbscan_link(const int32_t* cell_rng, int B, int N, float minx, float miny, float cell, int G, float eps,
+                   int32_t* status /*nullable*/, void* ws, void* stream);
+int df_dbscan_finish(const int32_t* cell_rng, const int32_t* dynamic /*nullable*/, int B, int N, float minx, float miny, float cell, int G,
+                     float eps, int min_cluster_size, double min_dynamic_frac, int32_t* labels, int32_t* n_clusters,
+                     int32_t* status /*nullable*/, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
