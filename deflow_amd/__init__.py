@@ -5,3 +5,4 @@ from .unet import ConvWithNorms, FastFlow3DUNet  # noqa: F401
 from .decoder import ConvGRU, ConvGRUDecoder, LinearDecoder  # noqa: F401
 from .timer import Timing  # noqa: F401
 from .cluster import dbscan, dynamic_cluster_labels  # noqa: F401
+from .voidmap import VoidMap, label_scene  # noqa: F401

@@ -164,6 +164,10 @@ _SIGS = {
     "df_dbscan_core": [P, P, I, I, F, F, F, I, F, I, P, P],
     "df_dbscan_link": [P, I, I, F, F, F, I, F, P, P, P],
     "df_dbscan_finish": [P, P, I, I, F, F, F, I, F, I, C.c_double, P, P, P, P, P],
+    "df_void_cast": [P, P, P, I, I, F, F, F, F, I, I, I, I, I, P, P, P, P],
+    "df_void_cast_probe": [P, P, P, I, I, F, F, F, F, I, I, I, I, I, P, P, P, P, I, P],
+    "df_void_merge": [P, P, P, I, I, I, I, I, P],
+    "df_void_query": [P, P, I, I, F, F, F, F, I, I, I, P, P, P],
     "df_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
     "df_adam_step_dev": [P, P, P, P, L, F, F, F, F, P, F, P],
 }

@@ -5,7 +5,8 @@ UNPINNED: upstream produces these labels offline on the CPU ([REF assets/slurm/d
 HDBSCAN, whose source is in the absent submodule).  What runs here is plain DBSCAN with every choice fixed -- the definition is in
 include/deflow_amd.h and DESIGN.md section 6b -- so the labels are a pure function of the input and bit-reproducible.  Of the defaults,
 ``eps = 0.7`` and ``min_cluster_size = 20`` are the recalled arguments of upstream's HDBSCAN call; ``min_points = 4`` and
-``min_dynamic_frac = 0.3`` are this project's own choices.  All four are arguments.  The DUFO flags themselves stay out of scope.
+``min_dynamic_frac = 0.3`` are this project's own choices.  All four are arguments.  The flags themselves: upstream's ``dufo_label`` dataset when the scene files
+hold one, otherwise the void map of ``voidmap.py`` (UNPINNED as well).
 
 CUDA tensors only, like the rest of the library: there is no CPU fallback.  Nothing here reads a device value back."""
 from __future__ import annotations

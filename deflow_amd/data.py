@@ -33,16 +33,23 @@ from .h5scene import H5File
 
 
 class HDF5Dataset:
-    def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False, dynamic_key: str = "dufo_label"):
+    def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False, dynamic_key: str = "dufo_label",
+                 dynamic_sidecar: Optional[str] = ".dufo.npz"):
         """``dynamic_key``: the per-sweep dataset holding the per-point dynamic flag (non-zero = dynamic) that online cluster labels
         start from (``Trainer(cluster_labels=...)``).  UNPINNED: ``dufo_label`` is the name recalled from upstream's process.py (the
         DUFO pass writes it before HDBSCAN turns it into ``label``), hence an argument.  When both sweeps of a pair hold it, the item
         carries ``dufo0`` / ``dufo1``; files without it give the items they always gave.
+        ``dynamic_sidecar``: when a pair's groups lack ``dynamic_key`` and ``<directory>/<scene_id><dynamic_sidecar>`` exists -- the file
+        ``python -m deflow_amd.voidmap data_dir=<directory>`` writes: one 0 / 1 array per timestamp, computed on the GPU by the void map
+        of DESIGN.md section 6c (UNPINNED) -- ``dufo0`` / ``dufo1`` come from it.  An array whose length differs from the sweep's rows
+        is a ValueError; a directory without sidecars gives the items it always gave.  None or "" switches the lookup off.
         ``eval=True`` (the evaluation entry): read ``index_eval.pkl`` -- the frames of the official validation benchmark, the ones
         that carry an ``eval_mask`` -- when the directory has one, as upstream's dataset does for ``av2_mode=val`` (recalled: the
         module is in the absent submodule); ``index_total.pkl`` lists every sweep of every scene."""
         self.directory = directory
         self.dynamic_key = dynamic_key
+        self.dynamic_sidecar = dynamic_sidecar
+        self._sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()       # cached per scene like the open files (None: no file)
         name = "index_total.pkl"
         if eval and os.path.exists(os.path.join(directory, "index_eval.pkl")):
             name = "index_eval.pkl"
@@ -69,6 +76,23 @@ class HDF5Dataset:
             else:
                 self._files.move_to_end(scene_id)
             return f
+
+    def _sidecar(self, scene_id: str) -> Optional[dict]:
+        with self._lock:
+            if scene_id in self._sidecars:
+                self._sidecars.move_to_end(scene_id)
+                return self._sidecars[scene_id]
+        path = os.path.join(self.directory, f"{scene_id}{self.dynamic_sidecar}")
+        side = None
+        if os.path.exists(path):
+            import numpy as np
+            with np.load(path, allow_pickle=False) as z:
+                side = {k: z[k] for k in z.files if k != "meta"}
+        with self._lock:
+            self._sidecars[scene_id] = side
+            while len(self._sidecars) > self._max_open:
+                self._sidecars.popitem(last=False)
+        return side
 
     def __getitem__(self, index: int) -> Dict[str, object]:
         scene_id, timestamp = self.data_index[index][0], str(self.data_index[index][1])
@@ -98,6 +122,16 @@ class HDF5Dataset:
         if dk and dk in g0 and dk in g1:         # per-point dynamic flags: the input of the online cluster labels (cluster.py)
             item["dufo0"] = t(g0[dk]).reshape(-1) != 0
             item["dufo1"] = t(g1[dk]).reshape(-1) != 0
+        elif self.dynamic_sidecar:
+            side = self._sidecar(scene_id)
+            t1 = f.sweeps[k + 1]
+            if side is not None and timestamp in side and t1 in side:
+                for key, ts, pc in (("dufo0", timestamp, "pc0"), ("dufo1", t1, "pc1")):
+                    flags = torch.from_numpy(side[ts]).reshape(-1)
+                    if flags.shape[0] != item[pc].shape[0]:
+                        raise ValueError(f"{scene_id}{self.dynamic_sidecar}: {flags.shape[0]} flags for sweep {ts}, which has "
+                                         f"{item[pc].shape[0]} rows: the sidecar belongs to another version of the scene file")
+                    item[key] = flags != 0
         if "eval_mask" in g0:          # the benchmark's point mask of the official validation split
             item["eval_mask"] = t(g0["eval_mask"]).reshape(-1).bool()
         return item

@@ -622,6 +622,50 @@ int df_dbscan_finish(const int32_t* cell_rng, const int32_t* dynamic /*nullable*
                      float eps, int min_cluster_size, double min_dynamic_frac, int32_t* labels, int32_t* n_clusters,
                      int32_t* status /*nullable*/, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ void map: ray-cast dynamic flags (SeFlow mode) ----
+ * The per-point dynamic flag the online cluster labels start from, computed on the GPU.  UNPINNED: upstream writes `dufo_label` offline
+ * on the CPU with DUFOMap (process.py; Duberg et al., RA-L 2024; absent submodule).  This is a DUFOMap-style void map with every choice
+ * fixed, so that the map and the flags are a pure integer function of the input; parity with upstream's flags is not claimed.  Space that
+ * some sweep has seen through is void; a return that lies in void space is dynamic.
+ *   grid            gmin (three fp32), voxel size `voxel`, dims (Gx, Gy, Gz) with Gx % 32 == 0 and Gx * Gy * Gz < 2^31; SUB = 256 sub-voxel
+ *                   units per voxel; k = fp32(256 / voxel) is computed on the host and passed as a float
+ *   quantisation    the only floating-point step: for a coordinate p, u = fp32(fp32(p - gmin) * k), two separately rounded fp32
+ *                   operations, and q = floor(u); the voxel of q is q >> 8 (arithmetic shift: floor).  A row takes part when
+ *                   i < count[b], its three coordinates are finite and |u| < 2^30 on every axis.  If a sample's origin fails that rule,
+ *                   none of its rays is cast (its rows still mark O)
+ *   ray walk        from A (the origin) to E (a participating row), in 64-bit integers.  d = E - A, m = max_k |d_k|.  With
+ *                   R = round(max_range / voxel * 256) a ray is truncated when m > R: E <- A + floor_div(d * R, m) per axis and d is
+ *                   recomputed (a Chebyshev range cut).  c = A >> 8, e = E >> 8; per axis step_k = sign(d_k), den_k = |d_k|,
+ *                   rem_k = |e_k - c_k|, num_k = ((c_k + 1) << 8) - A_k if d_k > 0, else A_k - (c_k << 8).  Visit c; then sum(rem)
+ *                   times: among the axes with rem_k > 0 take the one with the smallest num_k / den_k (compared by cross-multiplication;
+ *                   on equality the lower axis wins, x before y before z), c_k += step_k, num_k += 256, rem_k -= 1, visit c.  A
+ *                   6-connected walk that ends in e.  The loop is bounded by 3 * (R / 256 + 1) steps; a ray that would exceed the bound
+ *                   adds 1 to status and stops there (never, for 1 <= R <= 2^24, which the entry requires)
+ *   free bits F     a visited voxel inside the grid is set when the ray is truncated, or when its Chebyshev voxel distance to e exceeds
+ *                   hit_margin; e is the voxel of the ray's end after any truncation
+ *   occupied bits O the voxel of every participating row's ORIGINAL endpoint, when inside the grid, truncated or not
+ *   void map V      V |= erode(F & ~O, r): the AND over the (2r+1)^3 Chebyshev neighbourhood, r in {0, 1, 2}; voxels outside the grid
+ *                   count as not free.  V persists over any number of sweeps until the caller clears it
+ *   flag            1 when the row takes part, its voxel is inside the grid and its bit of V is set; every other row 0
+ *   bit layout      u32 words, x fastest: bit = (z * Gy + y) * Gx + x, word bit >> 5, bit bit & 31; F, O, V are [B, Gx*Gy*Gz/32]
+ * df_void_cast: points [B,N,3] f32, count [B] i32, origin [B,3] f32 -> F and O of this sweep.  The entry ZEROES F and O itself (an async
+ *   memset on the stream) before the rays are cast: the caller only provides the storage.  Bits are set with 32-bit integer atomic OR
+ *   after a plain test of the word; the result does not depend on the launch order.  status (nullable, i32[1]) as for DBSCAN.
+ * df_void_cast_probe: the same cast for measuring (tools/voidmap_bench.py): attempts (nullable, u64[1]) is increased by the number of
+ *   free-bit sets the rays asked for; always_atomic != 0 drops the test before the atomic.  The bits it leaves are df_void_cast's.
+ * df_void_merge: V |= erode(F & ~O, erode).   df_void_query: flags [B,N] i32, written completely.
+ * B * N < 2^30, B <= 65535, the grid limits above: violations return DF_E_SHAPE; a non-finite gmin, k <= 0, hit_margin < 0, R outside
+ * [1, 2^24], erode outside {0, 1, 2} and NULL buffers return DF_E_ARG.  No launch then. */
+int df_void_cast(const float* points, const int32_t* count, const float* origin, int B, int N, float gminx, float gminy, float gminz,
+                 float k, int Gx, int Gy, int Gz, int hit_margin, int R, uint32_t* F, uint32_t* O, int32_t* status /*nullable*/,
+                 void* stream);
+int df_void_cast_probe(const float* points, const int32_t* count, const float* origin, int B, int N, float gminx, float gminy,
+                       float gminz, float k, int Gx, int Gy, int Gz, int hit_margin, int R, uint32_t* F, uint32_t* O,
+                       int32_t* status /*nullable*/, uint64_t* attempts /*nullable*/, int always_atomic, void* stream);
+int df_void_merge(const uint32_t* F, const uint32_t* O, uint32_t* V, int B, int Gx, int Gy, int Gz, int erode, void* stream);
+int df_void_query(const float* points, const int32_t* count, int B, int N, float gminx, float gminy, float gminz, float k, int Gx, int Gy,
+                  int Gz, const uint32_t* V, int32_t* flags, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
