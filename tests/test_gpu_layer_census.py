@@ -51,16 +51,31 @@ ALLOW = {
     **{k: "test_gpu_kernels.py::test_pillar_bands_vs_oracle, ::test_pillarize_backward" for k in (
         "df_pillar2_hist", "df_pillar2_scan", "df_pillar2_scatter", "df_pillar2_band", "df_pillar2_band_sp", "df_pfn_bn_finalize",
         "df_pfn_bn_finalize2", "df_pfn_bwd_stats", "df_pfn_bwd_finalize", "df_pfn_bwd_weights", "df_cell_sort")},
-    # GRU trio (and the decoder's gather / bias-sum / weight-plane helpers) -> tests/test_gpu_kernels.py::test_gru_decoder_golden
-    **{k: "test_gpu_kernels.py::test_gru_decoder_golden" for k in (
-        "df_gru_decoder_fwd", "df_gru_decoder_fwd_mp", "df_gru_decoder_bwd_mp", "df_gru_wgrad_mp", "df_gru_decoder_fwd_bf16",
-        "df_gru_decoder_bwd", "df_gru_xtab", "df_gru_lean_fwd", "df_gru_lean_bwd", "df_gru_lean_wgrad", "df_gru_lean_head_wgrad",
-        "df_gru_lean_finalize", "df_gru_head_wgrad", "df_gru_wgrad", "df_gather_bwd", "df_gather_bwd_m", "df_split_bf16x2_rows",
-        "df_colsum_stage", "df_colsum_finalize", "df_conv2d_wgrad_reduce")},
-    # loss / Adam (and the ego-motion transform in front of the loss) -> tests/test_gpu_kernels.py::test_ego_transform_loss_adam
-    **{k: "test_gpu_kernels.py::test_ego_transform_loss_adam" for k in (
-        "df_ego_transform", "df_deflow_loss_fwd", "df_deflow_loss_finalize", "df_deflow_loss_bwd", "df_wloss_fwd", "df_wloss_finalize",
-        "df_wloss_bwd", "df_gather_gt", "df_adam_step", "df_adam_step_dev")},
+    # GRU trio (and the decoder's bias-sum / weight-plane helpers): one golden input (B = 3, rows 333 / 0 / 1) at 1 - 16 iterations, and
+    # the cases built for the row tiles and split-K walks (tests/helpers/decoder_cases.py), lean / lean_fp32 / full forms
+    **{k: "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64" for k in (
+        "df_gru_decoder_fwd_mp", "df_gru_decoder_bwd_mp", "df_gru_wgrad_mp", "df_gru_xtab", "df_gru_lean_fwd", "df_gru_lean_bwd",
+        "df_gru_lean_wgrad", "df_gru_lean_head_wgrad", "df_gru_lean_finalize", "df_gru_head_wgrad", "df_split_bf16x2_rows",
+        "df_colsum_finalize", "df_conv2d_wgrad_reduce")},
+    # the two-stage column sum runs from B ceil(N / 64) >= 2048 only: the `blocks` case
+    "df_colsum_stage": "test_gpu_decoder_cases.py::test_decoder_case_vs_float64[blocks-*]",
+    # the segmented gather backward: against float64 above, and to the bit against the sequential fp32 sum (both lane forms, accumulate,
+    # the measured maximum)
+    **{k: "test_gpu_decoder_cases.py::test_gather_backward_forms_bit_exact, ::test_decoder_case_vs_float64" for k in (
+        "df_gather_bwd", "df_gather_bwd_m")},
+    # the fp32 C-ABI wrappers of the _mp entries (no Python caller; the first-generation kernels behind them run under DF_GRU_V1)
+    **{k: "test_gpu_model.py::test_alternate_kernel_paths (through the _mp entry)" for k in (
+        "df_gru_decoder_fwd", "df_gru_decoder_bwd", "df_gru_wgrad")},
+    # the bf16 inference forward of the head (DeFlow.inference_dtype = "bf16")
+    "df_gru_decoder_fwd_bf16": "test_gpu_model.py::test_bf16_inference_path_vs_oracle",
+    # ego-motion transform, deflowLoss through DeflowLossFn, host-step Adam at n = 4096
+    **{k: "test_gpu_kernels.py::test_ego_transform_loss_adam" for k in ("df_ego_transform", "df_adam_step")},
+    # the loss trios, the ground-truth gather and the device-step Adam, each against a float64 restatement
+    **{k: "test_gpu_loss_optim_kernels.py::test_deflow_loss_kernels_vs_float64, test_gpu_kernels.py::test_ego_transform_loss_adam" for k in (
+        "df_deflow_loss_fwd", "df_deflow_loss_finalize", "df_deflow_loss_bwd")},
+    **{k: "test_gpu_loss_optim_kernels.py::test_wloss_kernels_vs_float64" for k in ("df_wloss_fwd", "df_wloss_finalize", "df_wloss_bwd")},
+    "df_gather_gt": "test_gpu_loss_optim_kernels.py::test_gather_gt_exact",
+    "df_adam_step_dev": "test_gpu_loss_optim_kernels.py::test_adam_step_dev_matches_host_step_form",
 }
 # entries outside the seams whose products every checked layer reads: the step's weight forms (transposes, fp16 planes, row L1
 # norms: each convolution check runs on the fp32 weights the forms were made from) and the weight arena's max |w| (the planes' scale)
