@@ -37,6 +37,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline bool df_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// a 64-channel image set the decoder forwards gather from: B images, 16-byte aligned rows and image offsets
+static inline bool df_img64_ok(const df_img& d, int B) {
+  return d.ptr && df_aligned16(d.ptr) && d.n == B && d.c == 64 && (d.ld % 4) == 0 && (d.img_stride % 4) == 0 &&
+         (d.grp_off % 4) == 0 && d.grp_size > 0;
+}
+
 // element offset of image n inside an image set (see include/deflow_amd.h)
 __device__ __forceinline__ int64_t df_img_base(const df_img& d, int n) {
   return (int64_t)(n % d.grp_size) * d.img_stride + (int64_t)(n / d.grp_size) * d.grp_off;

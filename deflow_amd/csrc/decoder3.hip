@@ -4,7 +4,7 @@
 // gates is computed ONCE per point (registers, 3 x 32 per lane in MFMA C layout) and each iteration only multiplies
 // the 128 h / r*h columns: 54 instead of 72 weight chunks for 4 iterations (-25 % MFMA work; only the fp32 summation
 // order changes -- x part first, then the h part).  Layout: two workgroups per CU (70 KB LDS, <= 256 VGPRs each),
-// 16 points per wave, wave-private LDS A operand), except that weight chunks now go L2 -> LDS by DMA
+// 16 points per wave with a wave-private LDS A operand; weight chunks go L2 -> LDS by DMA
 // (buffer_load ... lds): no staging registers, which is what makes room for the 96 hoisted ones.  The DMA writes
 // each wave's 64 x 16 B linearly, so weight tiles are unpadded [rows][32] with the XOR slot swizzle of the conv
 // kernels applied to the SOURCE column (physical slot = logical slot ^ ((row >> 1) & 7)).
@@ -230,9 +230,21 @@ __global__ __launch_bounds__(256, DF_GRU_LB) DF_GRU_ATTR void gru_fwd3_kernel(Gr
 
 }  // namespace
 
-// Arguments are validated by the C-ABI entry (df_gru_decoder_fwd in decoder.hip), which dispatches here.
-int df_launch_gru_fwd3(df_img before, df_img after, const int32_t* coords, const float* offs, const int32_t* counts,
-                       int B, int N, int num_iters, df_gru_weights wts, float* flow, float* save, int mfma_bf16, void* stream) {
+extern "C" int df_gru_decoder_fwd(df_img before, df_img after, const int32_t* coords, const float* offs,
+                                  const int32_t* counts, int B, int N, int num_iters, df_gru_weights wts, float* flow,
+                                  float* save, void* stream) {
+  return df_gru_decoder_fwd_mp(before, after, coords, offs, counts, B, N, num_iters, wts, flow, save, 0, stream);
+}
+
+extern "C" int df_gru_decoder_fwd_mp(df_img before, df_img after, const int32_t* coords, const float* offs,
+                                     const int32_t* counts, int B, int N, int num_iters, df_gru_weights wts, float* flow,
+                                     float* save, int mfma_bf16, void* stream) {
+  DF_REQUIRE(df_img64_ok(before, B) && df_img64_ok(after, B), DF_E_SHAPE);
+  DF_REQUIRE(before.h == after.h && before.w == after.w, DF_E_SHAPE);
+  DF_REQUIRE(coords && offs && counts && flow && B > 0 && N > 0 && num_iters >= 1, DF_E_ARG);
+  DF_REQUIRE(wts.w_off && wts.b_off && wts.w_zr && wts.b_zr && wts.w_q && wts.b_q && wts.w_1 && wts.b_1 && wts.w_2 &&
+                 wts.b_2 && df_aligned16(wts.w_zr) && df_aligned16(wts.w_q) && df_aligned16(wts.w_1),
+             DF_E_ARG);
   Gru3Params p;
   p.before = before; p.after = after; p.coords = coords; p.offs = offs; p.counts = counts;
   p.N = N; p.T = num_iters; p.w = wts; p.flow = flow; p.save = save;

@@ -1,5 +1,5 @@
 // Backward of the ConvGRU decoder ([REF decoder.py:123-183] differentiated), two workgroups per CU; the forward is
-// decoder3.hip, the first generation (one workgroup per CU, DF_GRU_V1=1) is decoder_bwd.hip.
+// decoder3.hip.  (decoder_bwd.hip holds what follows this kernel: the gather backward and the small reductions.)
 //
 //   * dh is accumulated IN PLACE: dh <- dh (1 - z), then the transposed-weight GEMMs add W_z^T dz_pre, r * (W_q^T dq_pre)
 //     and W_r^T dr_pre into the same registers -- at most four 32-register planes are live at any point;
@@ -44,7 +44,7 @@ struct GruBwd3Params {
   float* dx;
   float* dpre1;
   float* xout;
-  float* bias_partial;  // [blocks][772], layout as in decoder_bwd.hip
+  float* bias_partial;  // [blocks][772], layout at the end of the kernel
 };
 
 // W16 (with BF): p.w.w_1 and p.wt.{wt_zr, wt_q, wt_1} point at bf16 copies (gemm_dma.h, WStreamT<2>)
@@ -362,10 +362,22 @@ __global__ __launch_bounds__(256, 2) void gru_bwd3_kernel(GruBwd3Params p) {
 
 }  // namespace
 
-// Arguments are validated by the C-ABI entry (df_gru_decoder_bwd in decoder_bwd.hip), which dispatches here.
-int df_launch_gru_bwd3(const float* dflow, const float* offs, const int32_t* counts, int B, int N, int num_iters,
-                       df_gru_weights wts, df_gru_weights_t wtt, float* save, float* dh0, float* dx, float* dpre1,
-                       float* xout, float* bias_partial, int mfma_bf16, void* stream) {
+extern "C" int df_gru_decoder_bwd(const float* dflow, const float* offs, const int32_t* counts, int B, int N,
+                                  int num_iters, df_gru_weights wts, df_gru_weights_t wtt, float* save, float* dh0,
+                                  float* dx, float* dpre1, float* xout, float* bias_partial, void* stream) {
+  return df_gru_decoder_bwd_mp(dflow, offs, counts, B, N, num_iters, wts, wtt, save, dh0, dx, dpre1, xout, bias_partial, 0, stream);
+}
+
+extern "C" int df_gru_decoder_bwd_mp(const float* dflow, const float* offs, const int32_t* counts, int B, int N,
+                                     int num_iters, df_gru_weights wts, df_gru_weights_t wtt, float* save, float* dh0,
+                                     float* dx, float* dpre1, float* xout, float* bias_partial, int mfma_bf16, void* stream) {
+  DF_REQUIRE(dflow && offs && counts && save && dh0 && dx && dpre1 && xout && bias_partial && B > 0 && N > 0 &&
+                 num_iters >= 1,
+             DF_E_ARG);
+  DF_REQUIRE(wts.w_off && wts.b_off && wts.w_1 && wts.b_1 && wts.w_2 && wtt.wt_zr && wtt.wt_q && wtt.wt_1, DF_E_ARG);
+  DF_REQUIRE(df_aligned16(wts.w_1) && df_aligned16(wtt.wt_zr) && df_aligned16(wtt.wt_q) && df_aligned16(wtt.wt_1) &&
+                 df_aligned16(save) && df_aligned16(dh0) && df_aligned16(dx),
+             DF_E_ALIGN);
   GruBwd3Params p;
   p.dflow = dflow; p.offs = offs; p.counts = counts; p.N = N; p.T = num_iters; p.w = wts; p.wt = wtt; p.save = save;
   p.iter_stride = (int64_t)B * N * 128;

@@ -666,11 +666,6 @@ int gru_waves() {
   return (e && atoi(e) == 4) ? 4 : 8;
 }
 
-bool img64_ok4(const df_img& d, int B) {
-  return d.ptr && df_aligned16(d.ptr) && d.n == B && d.c == 64 && (d.ld % 4) == 0 && (d.img_stride % 4) == 0 &&
-         (d.grp_off % 4) == 0 && d.grp_size > 0;
-}
-
 }  // namespace
 
 extern "C" int df_gru_xtab(df_gru_weights wts, float* xtab, void* stream) {
@@ -687,7 +682,7 @@ extern "C" int df_gru_lean_partial_width(void) { return PW4; }
 extern "C" int df_gru_lean_fwd(df_img before, df_img after, const int32_t* coords, const float* offs, const int32_t* counts, int B,
                                int N, int num_iters, df_gru_weights wts, const float* xtab, float* flow, float* hsave, int mfma_bf16,
                                void* stream) {
-  DF_REQUIRE(img64_ok4(before, B) && img64_ok4(after, B), DF_E_SHAPE);
+  DF_REQUIRE(df_img64_ok(before, B) && df_img64_ok(after, B), DF_E_SHAPE);
   DF_REQUIRE(before.h == after.h && before.w == after.w, DF_E_SHAPE);
   DF_REQUIRE(coords && offs && counts && flow && xtab && B > 0 && N > 0 && num_iters >= 1, DF_E_ARG);
   DF_REQUIRE(mfma_bf16 >= 0 && mfma_bf16 <= 3, DF_E_ARG);

@@ -1,13 +1,10 @@
-// Backward of the point decoder ([REF decoder.py:123-199] differentiated).
+// Backward of the point decoders: everything but the ConvGRU data-gradient kernels (decoder4.hip lean, decoder3_bwd.hip full).
 //
-//   gru_bwd_kernel    data gradients of MLP head + num_iters GRU steps for 64 points per workgroup; same
-//                     structure as the forward (state in C-layout registers, wave-private LDS A operand,
-//                     streamed TRANSPOSED weights).  Gate pre-activation gradients overwrite the saved
-//                     z / r / q planes in place; the weight gradients are then plain split-K GEMMs over
-//                     those planes (df_conv2d_wgrad, 1x1 mode).
+//   linear_bwd_kernel LinearDecoder ([REF decoder.py:72-120] differentiated): recomputes the gather and the hidden layer.
 //   gather_bwd_kernel the reference's backward of img[:, y, x] is an atomic scatter-add with duplicate
 //                     indices; here each BEV cell sums the rows of its own points (the pillar sort already
 //                     made them contiguous) -- deterministic, every gradient pixel written exactly once.
+//                     gather_bwd_batched_kernel: the same sums with several cells in flight per lane group.
 //   small_outer       tiny [na x nb] outer-product reductions over valid rows (offset encoder, last Linear,
 //                     bias gradients).
 #include "common.h"
@@ -18,297 +15,6 @@ namespace {
 using namespace gs;
 
 constexpr int LDA_B = 260;          // [256 | pad] floats; 65 slots of 16 B, 65 mod 16 = 1
-constexpr int BS_B = 192 * LDB;     // B buffer: 192 weight rows
-
-struct GruBwdParams {
-  const float* dflow;
-  const float* offs;
-  const int32_t* counts;
-  int N, T;
-  df_gru_weights w;
-  df_gru_weights_t wt;
-  float* save;
-  int64_t plane_stride, iter_stride;
-  float* dh0;
-  float* dx;
-  float* dpre1;
-  float* xout;
-  float* bias_partial;  // [blocks][772]: per-workgroup partial sums of all small gradients (layout at the end of the kernel)
-};
-
-__global__ __launch_bounds__(256) void gru_bwd_kernel(GruBwdParams p) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* Bs = lds;                 // [2][192][36]
-  float* As = lds + 2 * BS_B;      // [4][16][LDA_B]
-  const int b = blockIdx.y;
-  const int cnt = p.counts[b];
-  const int p0 = blockIdx.x * 64;
-  if (p0 >= cnt) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 15, lq = lane >> 4;
-  float* Aw = As + wave * 16 * LDA_B;
-  const int wp0 = p0 + wave * 16;
-  const int64_t grow0 = (int64_t)b * p.N + wp0;
-  const float* a_lane = Aw + li * LDA_B + lq * 4;
-
-  Stager stg;
-  int par = 0;
-  stage_load<32>(stg, p.w.w_1, 192, 0);
-
-  // coalesced 16 x 128 block copies between global rows and LDS columns [col0, col0 + 128)
-  auto rows_to_lds = [&](const float* src, int col0) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int f = lane + 64 * j;
-      const int pt = f >> 5, c4 = f & 31;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (wp0 + pt < cnt) v = ld4(src + (grow0 + pt) * 128 + c4 * 4);
-      st4(Aw + pt * LDA_B + col0 + c4 * 4, v);
-    }
-  };
-  auto lds_to_rows = [&](float* dst, int col0) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int f = lane + 64 * j;
-      const int pt = f >> 5, c4 = f & 31;
-      if (wp0 + pt < cnt) st4(dst + (grow0 + pt) * 128 + c4 * 4, ld4(Aw + pt * LDA_B + col0 + c4 * 4));
-    }
-  };
-  auto lds_to_c = [&](f32x4 (&v)[8], int col0) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[t][r] = Aw[(4 * lq + r) * LDA_B + col0 + 16 * t + li];
-  };
-  auto c_to_lds = [&](const f32x4 (&v)[8], int col0) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Aw[(4 * lq + r) * LDA_B + col0 + 16 * t + li] = v[t][r];
-  };
-
-  // ---- [h_T | x] -> A region; x also to global for the weight-gradient GEMMs -------------------
-  rows_to_lds(p.save + 5 * p.plane_stride, 0);
-  {
-    const float w0 = p.w.w_off[lane * 3 + 0], w1 = p.w.w_off[lane * 3 + 1], w2 = p.w.w_off[lane * 3 + 2];
-    const float bo = p.w.b_off[lane];
-    for (int pt = 0; pt < 16; ++pt) {
-      float x = 0.f;
-      if (wp0 + pt < cnt) {
-        const float* o = p.offs + (grow0 + pt) * 3;
-        x = fmaf(w2, o[2], fmaf(w1, o[1], fmaf(w0, o[0], bo)));
-        p.xout[(grow0 + pt) * 64 + lane] = x;
-      }
-      Aw[pt * LDA_B + 128 + lane] = x;
-    }
-  }
-  stage_store<32>(stg, Bs);
-  __syncthreads();
-
-  float sb[3][8], sb1[2] = {0.f, 0.f};
-  float sw2[2][3], sdf[3];  // partials of dW2[o][col] = sum_rows dflow[row][o] hid[row][col] and db2[o]
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int t = 0; t < 8; ++t) sb[g][t] = 0.f;
-  // ---- MLP head backward -----------------------------------------------------------------------
-  f32x4 pre1[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const float bia = p.w.b_1[16 * t + li];
-    pre1[t] = f32x4{bia, bia, bia, bia};
-  }
-  gemm_stream<32, 192, BS_B>(p.w.w_1, 192, 6, p.wt.wt_1, 32, a_lane, Bs, par, pre1, stg);
-  {
-    float df[4][3];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int o = 0; o < 3; ++o) df[r][o] = (wp0 + 4 * lq + r < cnt) ? p.dflow[(grow0 + 4 * lq + r) * 3 + o] : 0.f;
-#pragma unroll
-    for (int o = 0; o < 3; ++o) sdf[o] = df[0][o] + df[1][o] + df[2][o] + df[3][o];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int col = 16 * t + li;
-      const float w20 = p.w.w_2[0 * 32 + col], w21 = p.w.w_2[1 * 32 + col], w22 = p.w.w_2[2 * 32 + col];
-      sw2[t][0] = sw2[t][1] = sw2[t][2] = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pre = pre1[t][r];
-        const float dhid = df[r][0] * w20 + df[r][1] * w21 + df[r][2] * w22;
-        const float dp = dhid * df_gelu_grad(pre);
-        const float hv = df_gelu(pre);
-        if (wp0 + 4 * lq + r < cnt) p.dpre1[(grow0 + 4 * lq + r) * 32 + col] = dp;
-#pragma unroll
-        for (int o = 0; o < 3; ++o) sw2[t][o] += df[r][o] * hv;  // df is 0 on invalid rows
-        Aw[(4 * lq + r) * LDA_B + col] = dp;  // A operand of the next GEMM (cols 0..31)
-        if (r == 0) sb1[t] = dp; else sb1[t] += dp;
-      }
-    }
-  }
-  __syncthreads();
-  f32x4 dh[8], dxa[4];
-  {
-    f32x4 acc[12];
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    gemm_stream<192, 192, BS_B>(p.wt.wt_1, 32, 1, p.wt.wt_q, 128, a_lane, Bs, par, acc, stg);
-#pragma unroll
-    for (int t = 0; t < 8; ++t) dh[t] = acc[t];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) dxa[t] = acc[8 + t];
-  }
-
-  // ---- GRU steps in reverse --------------------------------------------------------------------
-  for (int it = p.T - 1; it >= 0; --it) {
-    float* pl_h = p.save + 0 * p.plane_stride + it * p.iter_stride;
-    float* pl_z = p.save + 1 * p.plane_stride + it * p.iter_stride;
-    float* pl_r = p.save + 2 * p.plane_stride + it * p.iter_stride;
-    float* pl_q = p.save + 3 * p.plane_stride + it * p.iter_stride;
-    f32x4 h[8], z[8], r[8], q[8];
-    rows_to_lds(pl_h, 0);
-    rows_to_lds(pl_z, 128);
-    __syncthreads();
-    lds_to_c(h, 0);
-    lds_to_c(z, 128);
-    __syncthreads();
-    rows_to_lds(pl_r, 0);
-    rows_to_lds(pl_q, 128);
-    __syncthreads();
-    lds_to_c(r, 0);
-    lds_to_c(q, 128);
-    __syncthreads();
-    // h' = (1 - z) h + z q
-    f32x4 dzp[8], dhc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float d = dh[t][k];
-        dzp[t][k] = d * (q[t][k] - h[t][k]) * z[t][k] * (1.f - z[t][k]);  // dz_pre
-        dhc[t][k] = d * (1.f - z[t][k]);
-        q[t][k] = d * z[t][k] * (1.f - q[t][k] * q[t][k]);                 // dq_pre (q no longer needed)
-        sb[0][t] += dzp[t][k];
-        sb[2][t] += q[t][k];
-      }
-    c_to_lds(q, 0);
-    __syncthreads();
-    lds_to_rows(pl_q, 0);  // dq_pre replaces q
-    f32x4 acc[12];
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    gemm_stream<192, 192, BS_B>(p.wt.wt_q, 128, 4, p.wt.wt_zr, 256, a_lane, Bs, par, acc, stg);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) dxa[t] += acc[8 + t];
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float drh = acc[t][k];
-        dhc[t][k] += drh * r[t][k];
-        r[t][k] = drh * h[t][k] * r[t][k] * (1.f - r[t][k]);  // dr_pre
-        sb[1][t] += r[t][k];
-      }
-    c_to_lds(dzp, 0);
-    c_to_lds(r, 128);
-    __syncthreads();
-    lds_to_rows(pl_z, 0);    // dz_pre replaces z
-    lds_to_rows(pl_r, 128);  // dr_pre replaces r
-#pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (it > 0) gemm_stream<192, 192, BS_B>(p.wt.wt_zr, 256, 8, p.wt.wt_q, 128, a_lane, Bs, par, acc, stg);
-    else gemm_stream<192, 192, BS_B>(p.wt.wt_zr, 256, 8, nullptr, 0, a_lane, Bs, par, acc, stg);
-#pragma unroll
-    for (int t = 0; t < 8; ++t) dh[t] = dhc[t] + acc[t];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) dxa[t] += acc[8 + t];
-  }
-  // ---- outputs: dh0 [rows,128], dx [rows,64] -----------------------------------------------------
-  c_to_lds(dh, 0);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) Aw[(4 * lq + k) * LDA_B + 128 + 16 * t + li] = dxa[t][k];
-  __syncthreads();
-  lds_to_rows(p.dh0, 0);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int f = lane + 64 * j;
-    const int pt = f >> 4, c4 = f & 15;
-    if (wp0 + pt < cnt) st4(p.dx + (grow0 + pt) * 64 + c4 * 4, ld4(Aw + pt * LDA_B + 128 + c4 * 4));
-  }
-  // ---- per-workgroup partial sums of every small gradient (rows beyond cnt contributed exact zeros) ------
-  // layout (PW columns): [0,384) d b_z|b_r|b_q, [384,416) d b_1, [416,608) dW_off[c][d], [608,672) d b_off[c],
-  // [672,768) dW_2[o][col], [768,771) d b_2[o]
-  constexpr int PW = 772;
-  float* red = Bs;  // the weight buffers are idle now: [4 waves][PW]
-  {
-    float off[4][3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int d = 0; d < 3; ++d) off[k][d] = (wp0 + 4 * lq + k < cnt) ? p.offs[(grow0 + 4 * lq + k) * 3 + d] : 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) v[d] += dxa[t][k] * off[k][d];
-        v[3] += dxa[t][k];
-      }
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        v[d] += __shfl_xor(v[d], 16);
-        v[d] += __shfl_xor(v[d], 32);
-      }
-      if (lq == 0) {
-        const int c = 16 * t + li;
-        red[wave * PW + 416 + c * 3 + 0] = v[0];
-        red[wave * PW + 416 + c * 3 + 1] = v[1];
-        red[wave * PW + 416 + c * 3 + 2] = v[2];
-        red[wave * PW + 608 + c] = v[3];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int o = 0; o < 3; ++o) {
-        float v = sw2[t][o];
-        v += __shfl_xor(v, 16);
-        v += __shfl_xor(v, 32);
-        if (lq == 0) red[wave * PW + 672 + o * 32 + 16 * t + li] = v;
-      }
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-      float v = sdf[o];  // identical on the 16 lanes of a row group: reduce over the 4 row groups only
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      if (lane == 0) red[wave * PW + 768 + o] = v;
-    }
-    if (lane == 0) red[wave * PW + 771] = 0.f;
-  }
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      float v = sb[g][t];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      if (lq == 0) red[wave * PW + g * 128 + 16 * t + li] = v;
-    }
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    float v = sb1[t];
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    if (lq == 0) red[wave * PW + 384 + 16 * t + li] = v;
-  }
-  __syncthreads();
-  for (int o = tid; o < PW; o += 256)
-    p.bias_partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * PW + o] =
-        red[o] + red[PW + o] + red[2 * PW + o] + red[3 * PW + o];
-}
 
 // ------------------------------------------------------------------------------ LinearDecoder bwd ---
 // [REF decoder.py:72-120] differentiated: flow = W2 gelu(W1 [before | after | offset_enc(128)] + b1) + b2.  Recomputes the
@@ -497,42 +203,6 @@ __global__ __launch_bounds__(256) void small_outer_kernel(const float* __restric
 
 }  // namespace
 
-int df_launch_gru_bwd3(const float* dflow, const float* offs, const int32_t* counts, int B, int N, int num_iters,
-                       df_gru_weights wts, df_gru_weights_t wtt, float* save, float* dh0, float* dx, float* dpre1,
-                       float* xout, float* bias_partial, int mfma_bf16, void* stream);
-
-extern "C" int df_gru_decoder_bwd(const float* dflow, const float* offs, const int32_t* counts, int B, int N,
-                                  int num_iters, df_gru_weights wts, df_gru_weights_t wtt, float* save, float* dh0,
-                                  float* dx, float* dpre1, float* xout, float* bias_partial, void* stream) {
-  return df_gru_decoder_bwd_mp(dflow, offs, counts, B, N, num_iters, wts, wtt, save, dh0, dx, dpre1, xout, bias_partial, 0, stream);
-}
-
-extern "C" int df_gru_decoder_bwd_mp(const float* dflow, const float* offs, const int32_t* counts, int B, int N,
-                                     int num_iters, df_gru_weights wts, df_gru_weights_t wtt, float* save, float* dh0,
-                                     float* dx, float* dpre1, float* xout, float* bias_partial, int mfma_bf16, void* stream) {
-  DF_REQUIRE(dflow && offs && counts && save && dh0 && dx && dpre1 && xout && bias_partial && B > 0 && N > 0 &&
-                 num_iters >= 1,
-             DF_E_ARG);
-  DF_REQUIRE(wts.w_off && wts.b_off && wts.w_1 && wts.b_1 && wts.w_2 && wtt.wt_zr && wtt.wt_q && wtt.wt_1, DF_E_ARG);
-  DF_REQUIRE(df_aligned16(wts.w_1) && df_aligned16(wtt.wt_zr) && df_aligned16(wtt.wt_q) && df_aligned16(wtt.wt_1) &&
-                 df_aligned16(save) && df_aligned16(dh0) && df_aligned16(dx),
-             DF_E_ALIGN);
-  static const bool use_v1 = getenv("DF_GRU_V1") != nullptr;  // first-generation kernel (1 workgroup / CU), for A/B
-  if (!use_v1)
-    return df_launch_gru_bwd3(dflow, offs, counts, B, N, num_iters, wts, wtt, save, dh0, dx, dpre1, xout, bias_partial, mfma_bf16, stream);
-  GruBwdParams p;
-  p.dflow = dflow; p.offs = offs; p.counts = counts; p.N = N; p.T = num_iters; p.w = wts; p.wt = wtt; p.save = save;
-  p.iter_stride = (int64_t)B * N * 128;
-  p.plane_stride = p.iter_stride * num_iters;
-  p.dh0 = dh0; p.dx = dx; p.dpre1 = dpre1; p.xout = xout; p.bias_partial = bias_partial;
-  const size_t lds_bytes = (size_t)(2 * BS_B + 4 * 16 * LDA_B) * sizeof(float);
-  DF_SET_LDS_ONCE((gru_bwd_kernel), (int)lds_bytes);
-  hipLaunchKernelGGL(gru_bwd_kernel, dim3((N + 63) / 64, B), dim3(256), lds_bytes,
-                     reinterpret_cast<hipStream_t>(stream), p);
-  DF_CHECK_LAUNCH();
-  return DF_OK;
-}
-
 // Batched form (round 4, second session).  The kernel above walks its cells one at a time through FOUR dependent global round
 // trips each (cell range -> point index -> compact position -> dh0 row): 0.74 ms per step at B = 16 for 2.8 GB.  Here a lane
 // group (32 lanes: `before` | `after` halves, or 16 lanes when only d(after) is wanted) takes U cells per pass with all their
@@ -640,10 +310,10 @@ static int gather_bwd_impl(const float* dh0, const uint32_t* idx_sorted, const i
   if (dbefore.ptr)
     DF_REQUIRE(dbefore.n == B && dbefore.c == 64 && dbefore.h == dafter.h && dbefore.w == dafter.w && (dbefore.ld % 4) == 0,
                DF_E_SHAPE);
-  static const int batched = getenv("DF_GATHER_BWD_V1") ? 0 : 1;   // A/B: the one-cell-at-a-time kernel
-  DF_REQUIRE(!amax_after || (batched && (int64_t)B * N < (1 << 29) && (int64_t)dafter.h * dafter.w < (1 << 28)), DF_E_SHAPE);   // (the batched kernel measures)
   const int64_t ncell = (int64_t)dafter.h * dafter.w;
-  if (batched && (int64_t)B * N < (1 << 29) && ncell < (1 << 28)) {   // (32-bit byte offsets of the buffer loads)
+  const bool batched = (int64_t)B * N < (1 << 29) && ncell < (1 << 28);   // (32-bit byte offsets of the buffer loads)
+  DF_REQUIRE(!amax_after || batched, DF_E_SHAPE);   // (only the batched kernel measures)
+  if (batched) {
     constexpr int U = 4;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dbefore.ptr) {

@@ -1,7 +1,7 @@
 """Point decoders with the reference's module trees ([REF decoder.py:72-199]): ConvGRU, ConvGRUDecoder,
 LinearDecoder.  state_dict keys are identical to the reference classes (offset_encoder.*, gru.conv{z,r,q}.*,
-decoder.{0,2}.*) so ``deflow_best.ckpt`` loads [REF deflow.py:41-47].  Compute: csrc/decoder.hip,
-csrc/decoder_bwd.hip."""
+decoder.{0,2}.*) so ``deflow_best.ckpt`` loads [REF deflow.py:41-47].  Compute: csrc/decoder4.hip + decoder_wgrad.hip (lean ConvGRU
+decoder), csrc/decoder3.hip + decoder3_bwd.hip (its full form), csrc/decoder.hip + decoder_bwd.hip (LinearDecoder, gather backward)."""
 from __future__ import annotations
 
 import contextlib
@@ -75,6 +75,60 @@ def _adjacent(a: torch.Tensor, b: torch.Tensor) -> bool:
     return sa.data_ptr() == sb.data_ptr()  # same arena: a strided view over both stays inside the storage
 
 
+def _colsum(partial: torch.Tensor, s) -> torch.Tensor:
+    """[rows, width] per-workgroup partial sums -> [width]"""
+    rows, width = partial.shape
+    out = torch.empty(width, dtype=torch.float32, device=partial.device)
+    if rows >= 2048:  # tens of thousands of per-workgroup rows: two-stage column sum
+        staged = torch.empty(64, width, dtype=torch.float32, device=partial.device)
+        call("df_colsum_stage", ptr(partial), rows, width, 64, ptr(staged), s)
+        call("df_colsum_finalize", ptr(staged), 64, width, 1, ptr(out), 0, s)
+    else:
+        call("df_colsum_finalize", ptr(partial), rows, width, 1, ptr(out), 0, s)
+    return out
+
+
+def _gather_bwd(dh0: torch.Tensor, ps: PointSet, dbefore: Optional[DfImg], dafter: DfImg, acc_before: bool, acc_after: bool, s,
+                measure: bool = False):
+    """image gradients of the gather: per-cell segmented sum of the dh0 rows (no atomics).  measure: where d(after) feeds an fp16x2
+    consumer and the batched kernel applies, the kernel also leaves max |d(after)| (round 5: the UNet backward's first data gradient
+    asked for it with a df_absmax pass over the whole image)."""
+    B, N, _ = ps.coords.shape
+    ncell = dafter.h * dafter.w
+    nblk = max(1, min(4096, ncell // 8))
+    if dbefore is None:   # the caller evaluates d(before) sparsely from dh0 (df_pillar_input_grad)
+        dbefore = DfImg(0, 0, 0, 0, 0, 0, 1, 0, 0)
+    src = getattr(dafter, "_src", None) if measure else None
+    if src is not None and not acc_after and ops.h2_active() and B * N < (1 << 29) and ncell < (1 << 28):
+        am = ops.amax_slot(dh0.device)
+        call("df_gather_bwd_m", ptr(dh0), ptr(ps.idx_sorted), ptr(ps.cell_rng), ptr(ps.cpos), B, N, dbefore, dafter,
+             int(acc_before), nblk, ptr(am), s)
+        src._df_amax = (am, ver(src))
+    else:
+        call("df_gather_bwd", ptr(dh0), ptr(ps.idx_sorted), ptr(ps.cell_rng), ptr(ps.cpos), B, N, dbefore, dafter,
+             int(acc_before), int(acc_after), nblk, s)
+
+
+def _decoder_forward(self, before_pseudoimages: torch.Tensor, after_pseudoimages: torch.Tensor,
+                     voxelizer_infos: List[Dict[str, torch.Tensor]]) -> List[torch.Tensor]:
+    """NCHW images + list of {"point_offsets", "voxel_coords"} -> list of [N_b,3] flows.  Differentiable w.r.t. the
+    images and the parameters (autograd.Function over the HIP forward/backward).  The reference-compatible call of both decoders."""
+    from .autograd import GruHeadFn
+    H, W = before_pseudoimages.shape[2:]
+    need_bwd = torch.is_grad_enabled() and (before_pseudoimages.requires_grad or after_pseudoimages.requires_grad or
+                                            any(p.requires_grad for p in self.parameters()))
+    ps = pack_infos(voxelizer_infos, H, W, before_pseudoimages.device, need_bwd)
+    ns = [int(i["voxel_coords"].shape[0]) for i in voxelizer_infos]
+    if need_bwd:
+        flow = GruHeadFn.apply(self, ps, before_pseudoimages, after_pseudoimages, *self.parameters())
+    else:
+        bh = before_pseudoimages.detach().permute(0, 2, 3, 1).contiguous()
+        ah = after_pseudoimages.detach().permute(0, 2, 3, 1).contiguous()
+        with torch.no_grad():
+            flow, _ = self.run(img(bh), img(ah), ps, False)
+    return [flow[b, :n] for b, n in enumerate(ns)]
+
+
 class ConvGRUDecoder(nn.Module):
     def __init__(self, pseudoimage_channels: int = 64, num_iters: int = 4):
         super().__init__()
@@ -121,12 +175,12 @@ class ConvGRUDecoder(nn.Module):
     def _x2_on() -> bool:
         """fp32 mode: the gate / head GEMMs of the forward and backward kernels as bf16x2 (two bf16 planes per operand, three
         MFMAs; csrc/gemm_dma.h WStreamT<3>) instead of fp32 MFMA.  DF_GRU_X2=0: the fp32-MFMA form."""
-        return os.environ.get("DF_GRU_X2", "1") != "0" and not os.environ.get("DF_GRU_V1")
+        return os.environ.get("DF_GRU_X2", "1") != "0"
 
     @staticmethod
     def _lean_on() -> bool:
-        """round 5: the lean decoder kernels (csrc/decoder4.hip).  DF_GRU_LEAN=0: the round-3/4 kernels (all planes saved), for A/B."""
-        return os.environ.get("DF_GRU_LEAN", "1") != "0" and not os.environ.get("DF_GRU_V1")
+        """round 5: the lean decoder kernels (csrc/decoder4.hip).  DF_GRU_LEAN=0: the full form (csrc/decoder3*.hip: all planes saved)."""
+        return os.environ.get("DF_GRU_LEAN", "1") != "0"
 
     def _xtab(self, W: DfGruWeights) -> torch.Tensor:
         """[416,4] fp32: (W[:, 128:] W_off | W[:, 128:] b_off + b) of the z, r, q gates and the head's first layer -- the whole
@@ -155,6 +209,30 @@ class ConvGRUDecoder(nn.Module):
         W2 = DfGruWeights(W.w_off, W.b_off, ptr(c[0]), W.b_zr, ptr(c[1]), W.b_q, ptr(c[2]), W.b_1, W.w_2, W.b_2)
         return W2, keep + c
 
+    def _mode(self, bf) -> Tuple[bool, bool, int]:
+        """-> bf16 mode, bf16x2 form, the kernels' mfma_bf16 argument (2 | 3 | 0: fp32 MFMA)"""
+        bf = bool(bf)
+        x2 = (not bf) and self._x2_on()
+        return bf, x2, 2 if bf else 3 if x2 else 0
+
+    def _mode_weights(self, W: DfGruWeights, keep: list, bf: bool, x2: bool) -> Tuple[DfGruWeights, list]:
+        """the GEMM weights in the form the mode's kernels read"""
+        return self._weights16(W, keep) if bf else self._weights_x2(W, keep) if x2 else (W, keep)
+
+    def _weights_bwd(self, bf: bool, x2: bool) -> Tuple[DfGruWeights, DfGruWeights, DfGruWeightsT, list]:
+        """-> the fp32 parameters, the mode's GEMM weights, their transposes in the same form (the data gradients are the forward's
+        GEMMs against the transposed weights), the tensors behind the pointers"""
+        W0, keep = self._weights()
+        w_zr, _, w_q = keep
+        wt = [ops.weight_transpose(w.view(rows, 1, 1, 192)).view(192, rows)
+              for w, rows in ((w_zr, 256), (w_q, 128), (self.decoder[0].weight.detach(), 32))]
+        W, keep = self._mode_weights(W0, keep, bf, x2)
+        if bf:   # the kernels' mfma_bf16 = 2 form: bf16 copies of the GEMM weights
+            wt = [t.to(torch.bfloat16) for t in wt]
+        elif x2:   # mfma_bf16 = 3: two-plane rows of the GEMM weights
+            wt = [self._split_x2(t) for t in wt]
+        return W0, W, DfGruWeightsT(ptr(wt[0]), ptr(wt[1]), ptr(wt[2])), keep + wt
+
     # -- engine ------------------------------------------------------------------------------------------
     def run(self, before: DfImg, after: DfImg, ps: PointSet, save: bool):
         """-> flow [B,N,3] (rows >= counts[b] are not written), save buffer or None."""
@@ -164,24 +242,20 @@ class ConvGRUDecoder(nn.Module):
         T = self.num_iters
         sv = torch.empty((5 * T + 1) * B * N * 128, dtype=torch.float32, device=dev) if save else None
         W, keep = self._weights()
-        bf = bool(ops.MFMA_BF16) and not os.environ.get("DF_GRU_V1")   # (the first-generation kernels are fp32 only)
-        x2 = (not bf) and self._x2_on()
+        bf, x2, mode = self._mode(ops.MFMA_BF16)
         # (the lean weight-gradient pass addresses a plane with 32-bit byte offsets: B * N * 512 < 2^31, ~4.19 M rows.  Beyond that a
-        #  SAVING forward takes the round-4 kernels, whose backward has the generic fallback -- not a DF_E_SHAPE in the backward after
-        #  the forward has kept only the lean planes)
+        #  SAVING forward takes the full form.  Its backward does not reach that size either: the data pass runs, then df_gru_wgrad_mp
+        #  and df_gru_head_wgrad answer DF_E_SHAPE -- the selection only decides which entry raises)
         lean = self._lean_on() and not (save and B * N * 512 >= (1 << 31))
         xtab = self._xtab(W) if lean else None
-        if bf:
-            W, keep = self._weights16(W, keep)
-        elif x2:
-            W, keep = self._weights_x2(W, keep)
+        W, keep = self._mode_weights(W, keep, bf, x2)
         if xtab is not None:
             # round 5 (csrc/decoder4.hip): x contributions from the [416,4] table, (T + 1) saved planes, gates recomputed backwards
             hs = torch.empty((T + 1) * B * N * 128, dtype=torch.float32, device=dev) if save else None
             with ops.timed("gru_fwd", flops=B * N * (589824.0 * T / 4 + 12870.0), bytes=B * N * (512.0 + 36.0), tag=f"T={T} save={save} lean",
                            moved=B * N * (512.0 * (1 + (T + 1 if save else 0)) + 36.0)):      # gather + (T + 1) hidden-state planes
                 call("df_gru_lean_fwd", before, after, ptr(ps.coords), ptr(ps.offs), ptr(ps.counts), B, N, T, W, ptr(xtab), ptr(flow),
-                     ptr(hs), 2 if bf else 3 if x2 else 0, stream())
+                     ptr(hs), mode, stream())
             if hs is not None:
                 hs.df_bf16, hs.df_lean, hs.df_xtab = bf, True, xtab
             return flow, hs
@@ -190,7 +264,7 @@ class ConvGRUDecoder(nn.Module):
         with ops.timed("gru_fwd", flops=B * N * (589824.0 * T / 4 + 12870.0), bytes=B * N * (512.0 + 36.0), tag=f"T={T} save={save}",
                        moved=B * N * (512.0 * (1 + (5 * T + 1 if save else 0)) + 36.0)):        # gather + 5 T + 1 planes
             call("df_gru_decoder_fwd_mp", before, after, ptr(ps.coords), ptr(ps.offs), ptr(ps.counts), B, N, T, W, ptr(flow),
-                 ptr(sv), 2 if bf else 3 if x2 else 0, stream())
+                 ptr(sv), mode, stream())
         if sv is not None:
             # in bf16 mode planes 0..4 hold bf16 half rows (csrc/decoder3.hip): the backward kernels must run in the mode the
             # forward ran in, whatever ops.MFMA_BF16 says by then
@@ -219,91 +293,43 @@ class ConvGRUDecoder(nn.Module):
 
     def run_backward(self, dflow: torch.Tensor, ps: PointSet, sv: torch.Tensor, dbefore: DfImg, dafter: DfImg,
                      acc_before: bool, acc_after: bool, grads: dict, before: DfImg = None, after: DfImg = None):
+        """backward of whichever form wrote sv (the lean planes carry df_lean); here the full form (csrc/decoder3_bwd.hip): sv = the
+        forward's 5 T + 1 planes, the data pass leaves the gate pre-activation gradients in the z / r / q planes."""
         if getattr(sv, "df_lean", False):
             return self._run_backward_lean(dflow, ps, sv, dbefore, dafter, acc_before, acc_after, grads)
         B, N, _ = ps.coords.shape
         dev, T, s = dflow.device, self.num_iters, stream()
         f32 = dict(dtype=torch.float32, device=dev)
         BN = B * N
-        bf = int(getattr(sv, "df_bf16", ops.MFMA_BF16))   # the mode the planes were written in
-        W, keep = self._weights()
-        w_zr, b_zr, w_q = keep
-        w1 = self.decoder[0].weight.detach()
-        wt_zr = ops.weight_transpose(w_zr.view(256, 1, 1, 192)).view(192, 256)
-        wt_q = ops.weight_transpose(w_q.view(128, 1, 1, 192)).view(192, 128)
-        wt_1 = ops.weight_transpose(w1.view(32, 1, 1, 192)).view(192, 32)
-        x2 = (not bf) and self._x2_on()
-        if bf:   # the kernels' mfma_bf16 = 2 form: bf16 copies of the GEMM weights
-            W, keep = self._weights16(W, keep)
-            wt_zr, wt_q, wt_1 = wt_zr.to(torch.bfloat16), wt_q.to(torch.bfloat16), wt_1.to(torch.bfloat16)
-        elif x2:   # mfma_bf16 = 3: two-plane rows of the GEMM weights (fp32 planes; the weight-gradient pass below is unchanged)
-            W, keep = self._weights_x2(W, keep)
-            wt_zr, wt_q, wt_1 = self._split_x2(wt_zr), self._split_x2(wt_q), self._split_x2(wt_1)
-        WT = DfGruWeightsT(ptr(wt_zr), ptr(wt_q), ptr(wt_1))
+        bf, x2, mode = self._mode(getattr(sv, "df_bf16", ops.MFMA_BF16))   # the mode the planes were written in
+        _, W, WT, keep = self._weights_bwd(bf, x2)       # keep: the tensors behind W and WT, alive until the launches are queued
         dh0, dx = torch.empty(BN, 128, **f32), torch.empty(BN, 64, **f32)
         dpre1, xbuf = torch.empty(BN, 32, **f32), torch.empty(BN, 64, **f32)
         dflow = dflow.contiguous()
-        nblocks = B * ((N + 63) // 64)
-        bias_partial = torch.zeros(nblocks, 772, **f32)
+        bias_partial = torch.zeros(B * ((N + 63) // 64), 772, **f32)
         # data gradients = the forward's GEMMs against the transposed weights: the same FLOP count (the weight gradients are
         # gru_wgrad's)
         with ops.timed("gru_bwd", flops=B * N * (589824.0 * T / 4 + 12870.0), bytes=B * N * (512.0 * 2 + 24.0),
                        moved=B * N * (512.0 * (4 * T + 1 + 3 * T + 1) + 24.0 + 256.0 + 384.0)):   # 4 T + 1 planes in, 3 T planes + dh0 (+ dx, x, dpre1) out
             call("df_gru_decoder_bwd_mp", ptr(dflow), ptr(ps.offs), ptr(ps.counts), B, N, T, W, WT, ptr(sv), ptr(dh0), ptr(dx),
-                 ptr(dpre1), ptr(xbuf), ptr(bias_partial), 2 if bf else 3 if x2 else 0, s)
-        bias_g = torch.empty(772, **f32)
-        if nblocks >= 2048:  # tens of thousands of per-workgroup rows: two-stage column sum
-            staged = torch.empty(64, 772, **f32)
-            call("df_colsum_stage", ptr(bias_partial), nblocks, 772, 64, ptr(staged), s)
-            call("df_colsum_finalize", ptr(staged), 64, 772, 1, ptr(bias_g), 0, s)
-        else:
-            call("df_colsum_finalize", ptr(bias_partial), nblocks, 772, 1, ptr(bias_g), 0, s)
-        # image gradients: per-cell segmented sum (no atomics)
-        ncell = dafter.h * dafter.w
-        if dbefore is None:   # the caller evaluates d(before) sparsely from dh0 (df_pillar_input_grad)
-            dbefore = DfImg(0, 0, 0, 0, 0, 0, 1, 0, 0)
-        call("df_gather_bwd", ptr(dh0), ptr(ps.idx_sorted), ptr(ps.cell_rng), ptr(ps.cpos), B, N, dbefore, dafter,
-             int(acc_before), int(acc_after), max(1, min(4096, ncell // 8)), s)
+                 ptr(dpre1), ptr(xbuf), ptr(bias_partial), mode, s)
+        bias_g = _colsum(bias_partial, s)
+        _gather_bwd(dh0, ps, dbefore, dafter, acc_before, acc_after, s)
         side = ops.SIDE
         if side is not None:
             side.keep.extend([sv, xbuf, dpre1, ps])
         with (side.fork() if side is not None else contextlib.nullcontext()):
             s = stream()  # the side stream inside the fork
-            # weight gradients: split-K GEMMs over the saved planes (now holding the gate pre-activation gradients)
+            # weight gradients: one fused streaming pass over the saved planes (now holding the gate pre-activation gradients)
             plane = T * BN * 128
-
-            def rows_img(t: torch.Tensor, off: int, n_img: int, c: int, ld: int, img_stride: int) -> DfImg:
-                return DfImg(t.data_ptr() + 4 * off, n_img, 1, BN, c, ld, n_img, img_stride, 0)
-
-            h_in = rows_img(sv, 0 * plane, T, 128, 128, BN * 128)
-            dz = rows_img(sv, 1 * plane, T, 128, 128, BN * 128)
-            dr = rows_img(sv, 2 * plane, T, 128, 128, BN * 128)
-            dq = rows_img(sv, 3 * plane, T, 128, 128, BN * 128)
-            rh = rows_img(sv, 4 * plane, T, 128, 128, BN * 128)
-            hT = rows_img(sv, 5 * plane, 1, 128, 128, BN * 128)
-            x_rep = rows_img(xbuf, 0, T, 64, 64, 0)          # the same x rows for every iteration
-            x_one = rows_img(xbuf, 0, 1, 64, 64, BN * 64)
-            kw = dict(row_counts=ps.counts, rows_per_seg=N)
-            if os.environ.get("DF_GRU_WGRAD_V1") and not bf:  # six generic 1x1 weight-gradient GEMMs (first generation), for A/B
-                # (fp32 planes only: in bf16 mode the planes are bf16 half rows that only the fused kernel reads)
-                dW_zr = torch.empty(256, 192, **f32)
-                dW_q = torch.empty(128, 192, **f32)
-                ops.conv2d_wgrad(h_in, dz, 1, 1, dW_zr, ld_co=192, dw_off=0, **kw)
-                ops.conv2d_wgrad(x_rep, dz, 1, 1, dW_zr, ld_co=192, dw_off=128, **kw)
-                ops.conv2d_wgrad(h_in, dr, 1, 1, dW_zr, ld_co=192, dw_off=128 * 192, **kw)
-                ops.conv2d_wgrad(x_rep, dr, 1, 1, dW_zr, ld_co=192, dw_off=128 * 192 + 128, **kw)
-                ops.conv2d_wgrad(rh, dq, 1, 1, dW_q, ld_co=192, dw_off=0, **kw)
-                ops.conv2d_wgrad(x_rep, dq, 1, 1, dW_q, ld_co=192, dw_off=128, **kw)
-            else:  # one fused streaming pass over the planes
-                nsplit = call("df_gru_wgrad_splits")
-                ws = torch.empty(nsplit, 384, 192, **f32)
-                with ops.timed("gru_wgrad", flops=2.0 * 384 * 192 * B * N * T, bytes=3.0 * 128 * 192 * 4,
-                               moved=B * N * T * 4.0 * (384 + 256 + 64)):     # 3 gate-gradient planes + h_in + r*h + x rows per step
-                    call("df_gru_wgrad_mp", ptr(sv), ptr(xbuf), ptr(ps.counts), B, N, T, ptr(ws), nsplit, 3 if x2 else bf, s)
-                dW_all = torch.empty(384, 192, **f32)
-                call("df_conv2d_wgrad_reduce", ptr(ws), nsplit, 384, 1, 192, ptr(dW_all), 192, 0, s)
-                dW_zr, dW_q = dW_all[:256], dW_all[256:]
-            if x2 and os.environ.get("DF_GRU_HEAD_WGRAD", "1") != "0":
+            nsplit = call("df_gru_wgrad_splits")
+            ws = torch.empty(nsplit, 384, 192, **f32)
+            with ops.timed("gru_wgrad", flops=2.0 * 384 * 192 * B * N * T, bytes=3.0 * 128 * 192 * 4,
+                           moved=B * N * T * 4.0 * (384 + 256 + 64)):     # 3 gate-gradient planes + h_in + r*h + x rows per step
+                call("df_gru_wgrad_mp", ptr(sv), ptr(xbuf), ptr(ps.counts), B, N, T, ptr(ws), nsplit, 3 if x2 else int(bf), s)
+            dW_all = torch.empty(384, 192, **f32)
+            call("df_conv2d_wgrad_reduce", ptr(ws), nsplit, 384, 1, 192, ptr(dW_all), 192, 0, s)
+            if x2:
                 # dW_1 [32,192] = dpre1^T [hT | x] in one streaming pass (round 4: gru_head_wgrad_kernel, bf16x2 products like the gate
                 # kernels; was two generic 1x1 weight-gradient GEMMs on the transposed problem + a transpose: 0.83 ms per step)
                 nsp1 = 128
@@ -313,17 +339,22 @@ class ConvGRUDecoder(nn.Module):
                 dW1 = torch.empty(32, 192, **f32)
                 call("df_conv2d_wgrad_reduce", ptr(ws1), nsp1, 32, 1, 192, ptr(dW1), 192, 0, s)
             else:
+                # bf16 mode, DF_GRU_X2=0 (df_gru_head_wgrad has bf16x2 products only): the generic 1x1 weight gradient.
                 # dW_1^T [192,32] = [hT | x]^T dpre1  (output channels must be a multiple of 64 -> compute the transpose)
-                dpre_img = rows_img(dpre1, 0, 1, 32, 32, BN * 32)
+                def rows_img(t: torch.Tensor, off: int, c: int) -> DfImg:
+                    return DfImg(t.data_ptr() + 4 * off, 1, 1, BN, c, c, 1, BN * c, 0)
+
+                dpre_img = rows_img(dpre1, 0, 32)
+                kw = dict(row_counts=ps.counts, rows_per_seg=N)
                 dW1t = torch.empty(192, 32, **f32)
-                with ops.mfma_bf16(bool(bf)):   # the head's generic weight gradients follow the forward's mode too
-                    ops.conv2d_wgrad(dpre_img, hT, 1, 1, dW1t, ld_co=32, dw_off=0, **kw)
-                    ops.conv2d_wgrad(dpre_img, x_one, 1, 1, dW1t, ld_co=32, dw_off=128 * 32, **kw)
+                with ops.mfma_bf16(bf):   # the head's generic weight gradients follow the forward's mode too
+                    ops.conv2d_wgrad(dpre_img, rows_img(sv, 5 * plane, 128), 1, 1, dW1t, ld_co=32, dw_off=0, **kw)
+                    ops.conv2d_wgrad(dpre_img, rows_img(xbuf, 0, 64), 1, 1, dW1t, ld_co=32, dw_off=128 * 32, **kw)
                 dW1 = ops.weight_transpose(dW1t.view(192, 1, 1, 32)).view(32, 192)
         g = self.gru
-        grads[g.convz.weight] = dW_zr[:128].unsqueeze(2)
-        grads[g.convr.weight] = dW_zr[128:].unsqueeze(2)
-        grads[g.convq.weight] = dW_q.unsqueeze(2)
+        grads[g.convz.weight] = dW_all[:128].unsqueeze(2)
+        grads[g.convr.weight] = dW_all[128:256].unsqueeze(2)
+        grads[g.convq.weight] = dW_all[256:].unsqueeze(2)
         grads[self.decoder[0].weight] = dW1
         grads[g.convz.bias] = bias_g[0:128]
         grads[g.convr.bias] = bias_g[128:256]
@@ -344,56 +375,19 @@ class ConvGRUDecoder(nn.Module):
         dev, T, s = dflow.device, self.num_iters, stream()
         f32 = dict(dtype=torch.float32, device=dev)
         BN = B * N
-        bf = int(hs.df_bf16)
-        W0, keep = self._weights()                       # the fp32 parameters (finalize reads them)
-        w_zr, b_zr, w_q = keep
-        w1 = self.decoder[0].weight.detach()
-        wt_zr = ops.weight_transpose(w_zr.view(256, 1, 1, 192)).view(192, 256)
-        wt_q = ops.weight_transpose(w_q.view(128, 1, 1, 192)).view(192, 128)
-        wt_1 = ops.weight_transpose(w1.view(32, 1, 1, 192)).view(192, 32)
-        x2 = (not bf) and self._x2_on()
-        W = W0
-        if bf:
-            W, keep = self._weights16(W0, keep)
-            wt_zr, wt_q, wt_1 = wt_zr.to(torch.bfloat16), wt_q.to(torch.bfloat16), wt_1.to(torch.bfloat16)
-        elif x2:
-            W, keep = self._weights_x2(W0, keep)
-            wt_zr, wt_q, wt_1 = self._split_x2(wt_zr), self._split_x2(wt_q), self._split_x2(wt_1)
-        WT = DfGruWeightsT(ptr(wt_zr), ptr(wt_q), ptr(wt_1))
-        mode = 2 if bf else 3 if x2 else 0
+        bf, x2, mode = self._mode(hs.df_bf16)
+        W0, W, WT, keep = self._weights_bwd(bf, x2)      # W0: the fp32 parameters (finalize reads them)
         gpl = torch.empty(4 * T * BN * 128, **f32)
         dh0, dpre1 = torch.empty(BN, 128, **f32), torch.empty(BN, 32, **f32)
         dflow = dflow.contiguous()
-        nblocks = B * ((N + 63) // 64)
-        PW = call("df_gru_lean_partial_width")
-        partial = torch.zeros(nblocks, PW, **f32)
+        partial = torch.zeros(B * ((N + 63) // 64), call("df_gru_lean_partial_width"), **f32)
         # data gradients: the forward's h-side GEMMs against the transposed weights + the recompute of the three gates
         with ops.timed("gru_bwd", flops=B * N * (589824.0 * T / 4 + 12870.0), bytes=B * N * (512.0 * 2 + 24.0),
                        moved=B * N * (512.0 * (T + 1 + 4 * T + 1) + 24.0 + 128.0)):    # T + 1 planes in, 4 T planes + dh0 (+ dpre1) out
             call("df_gru_lean_bwd", ptr(dflow), ptr(ps.offs), ptr(ps.counts), B, N, T, W, WT, ptr(hs.df_xtab), ptr(hs), ptr(gpl),
                  ptr(dh0), ptr(dpre1), ptr(partial), mode, s)
-        sums = torch.empty(PW, **f32)
-        if nblocks >= 2048:
-            staged = torch.empty(64, PW, **f32)
-            call("df_colsum_stage", ptr(partial), nblocks, PW, 64, ptr(staged), s)
-            call("df_colsum_finalize", ptr(staged), 64, PW, 1, ptr(sums), 0, s)
-        else:
-            call("df_colsum_finalize", ptr(partial), nblocks, PW, 1, ptr(sums), 0, s)
-        ncell = dafter.h * dafter.w
-        if dbefore is None:   # the caller evaluates d(before) sparsely from dh0 (df_pillar_input_grad)
-            dbefore = DfImg(0, 0, 0, 0, 0, 0, 1, 0, 0)
-        src = getattr(dafter, "_src", None)
-        if (src is not None and not acc_after and ops.h2_active() and os.environ.get("DF_GATHER_BWD_V1") is None
-                and B * N < (1 << 29) and ncell < (1 << 28) and os.environ.get("DF_GATHER_AMAX", "1") != "0"):
-            # the kernel measures max |d(after)| as it writes (round 5): the UNet backward's first data gradient asked for it with a
-            # df_absmax pass over the whole image
-            am = ops.amax_slot(dh0.device)
-            call("df_gather_bwd_m", ptr(dh0), ptr(ps.idx_sorted), ptr(ps.cell_rng), ptr(ps.cpos), B, N, dbefore, dafter,
-                 int(acc_before), max(1, min(4096, ncell // 8)), ptr(am), s)
-            src._df_amax = (am, ver(src))
-        else:
-            call("df_gather_bwd", ptr(dh0), ptr(ps.idx_sorted), ptr(ps.cell_rng), ptr(ps.cpos), B, N, dbefore, dafter,
-                 int(acc_before), int(acc_after), max(1, min(4096, ncell // 8)), s)
+        sums = _colsum(partial, s)
+        _gather_bwd(dh0, ps, dbefore, dafter, acc_before, acc_after, s, measure=True)
         side = ops.SIDE
         if side is not None:
             side.keep.extend([hs, gpl, dpre1, sums, ps])
@@ -403,7 +397,7 @@ class ConvGRUDecoder(nn.Module):
             ws = torch.empty(nsplit, 384, 128, **f32)
             with ops.timed("gru_wgrad", flops=2.0 * 384 * 192 * B * N * T, bytes=3.0 * 128 * 192 * 4,
                            moved=B * N * T * 4.0 * (384 + 256)):      # 3 gate-gradient planes + h_in + r*h per step
-                call("df_gru_lean_wgrad", ptr(hs), ptr(gpl), ptr(ps.counts), B, N, T, ptr(ws), nsplit, 3 if x2 else (1 if bf else 0), s)
+                call("df_gru_lean_wgrad", ptr(hs), ptr(gpl), ptr(ps.counts), B, N, T, ptr(ws), nsplit, 3 if x2 else int(bf), s)
             dW_all = torch.empty(384, 192, **f32)
             call("df_conv2d_wgrad_reduce", ptr(ws), nsplit, 384, 1, 128, ptr(dW_all), 192, 0, s)
             # (round 5: 128 -> 1024 split-K workgroups -- 128 left half the CUs idle and 2.5 MB in flight: 0.42 ms for 0.8 GB of planes)
@@ -430,24 +424,7 @@ class ConvGRUDecoder(nn.Module):
         grads[self.decoder[2].bias] = sums[1760:1763]
         return dh0   # [B*N,128] gradient of the gathered rows (for a sparse d(before); see df_pillar_input_grad)
 
-    # -- reference-compatible call ------------------------------------------------------------------------------
-    def forward(self, before_pseudoimages: torch.Tensor, after_pseudoimages: torch.Tensor,
-                voxelizer_infos: List[Dict[str, torch.Tensor]]) -> List[torch.Tensor]:
-        """NCHW images + list of {"point_offsets", "voxel_coords"} -> list of [N_b,3] flows.  Differentiable w.r.t. the
-        images and the parameters (autograd.Function over the HIP forward/backward)."""
-        from .autograd import GruHeadFn
-        H, W = before_pseudoimages.shape[2:]
-        need_bwd = torch.is_grad_enabled() and (before_pseudoimages.requires_grad or after_pseudoimages.requires_grad or
-                                                any(p.requires_grad for p in self.parameters()))
-        ps = pack_infos(voxelizer_infos, H, W, before_pseudoimages.device, need_bwd)
-        ns = [int(i["voxel_coords"].shape[0]) for i in voxelizer_infos]
-        if need_bwd:
-            flow = GruHeadFn.apply(self, ps, before_pseudoimages, after_pseudoimages, *self.parameters())
-        else:
-            bh = before_pseudoimages.permute(0, 2, 3, 1).contiguous()
-            ah = after_pseudoimages.permute(0, 2, 3, 1).contiguous()
-            flow, _ = self.run(img(bh), img(ah), ps, False)
-        return [flow[b, :n] for b, n in enumerate(ns)]
+    forward = _decoder_forward
 
 
 class LinearDecoder(nn.Module):
@@ -483,11 +460,7 @@ class LinearDecoder(nn.Module):
              ptr(self.offset_encoder.weight.detach()), ptr(self.offset_encoder.bias.detach()), ptr(w1),
              ptr(d[0].bias.detach()), ptr(d[2].weight.detach()), ptr(wt_1), ptr(vx), ptr(dh0), ptr(dxe), ptr(dpre1),
              ptr(hid), s)
-        ncell = dafter.h * dafter.w
-        if dbefore is None:
-            dbefore = DfImg(0, 0, 0, 0, 0, 0, 1, 0, 0)
-        call("df_gather_bwd", ptr(dh0), ptr(ps.idx_sorted), ptr(ps.cell_rng), ptr(ps.cpos), B, N, dbefore, dafter,
-             int(acc_before), int(acc_after), max(1, min(4096, ncell // 8)), s)
+        _gather_bwd(dh0, ps, dbefore, dafter, acc_before, acc_after, s)
         # dW1^T [256,32] = vx^T dpre1 (row GEMM with the validity mask), then transpose back
         rows = lambda t, c: DfImg(t.data_ptr(), 1, 1, BN, c, c, 1, BN * c, 0)
         dW1t = torch.empty(256, 32, **f32)
@@ -503,18 +476,4 @@ class LinearDecoder(nn.Module):
         grads[self.offset_encoder.bias] = so(dxe, 128, 128, None, 0, 1).view(128)
         return dh0
 
-    def forward(self, before_pseudoimages, after_pseudoimages, voxelizer_infos):
-        from .autograd import GruHeadFn
-        H, W = before_pseudoimages.shape[2:]
-        need_bwd = torch.is_grad_enabled() and (before_pseudoimages.requires_grad or after_pseudoimages.requires_grad or
-                                                any(p.requires_grad for p in self.parameters()))
-        ps = pack_infos(voxelizer_infos, H, W, before_pseudoimages.device, need_bwd)
-        ns = [int(i["voxel_coords"].shape[0]) for i in voxelizer_infos]
-        if need_bwd:
-            flow = GruHeadFn.apply(self, ps, before_pseudoimages, after_pseudoimages, *self.parameters())
-        else:
-            bh = before_pseudoimages.detach().permute(0, 2, 3, 1).contiguous()
-            ah = after_pseudoimages.detach().permute(0, 2, 3, 1).contiguous()
-            with torch.no_grad():
-                flow, _ = self.run(img(bh), img(ah), ps, False)
-        return [flow[b, :n] for b, n in enumerate(ns)]
+    forward = _decoder_forward

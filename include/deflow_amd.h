@@ -470,7 +470,8 @@ int df_gru_wgrad(const float* save, const float* x, const int32_t* counts, int B
 int df_gru_wgrad_mp(const float* save, const float* x, const int32_t* counts, int B, int N, int num_iters, float* ws,
                     int nsplit, int mfma_bf16, void* stream);
 
-/* ---- round 5: the "lean" ConvGRU decoder (csrc/decoder4.hip) -- the engine's default; the entries above remain for A/B ----
+/* ---- round 5: the "lean" ConvGRU decoder (csrc/decoder4.hip) -- the engine's default; the entries above (the full form: every
+ * plane saved) remain as the tested alternate and for saving forwards of 2^31 bytes or more per plane ----
  * Same computation as df_gru_decoder_fwd_mp / _bwd_mp / df_gru_wgrad_mp ([REF decoder.py:123-199] and its derivative), two changes:
  *  (1) x = W_off o + b_off [REF decoder.py:172] is affine in the point's 3 offsets and enters every gate and the head linearly
  *      [REF decoder.py:126-139,151,182], so its contribution is evaluated from a [416][4] table (rows z | r | q | head layer 1:
@@ -506,7 +507,7 @@ int df_gather_bwd(const float* dh0, const uint32_t* idx_sorted, const int32_t* c
                   int nblk, void* stream);
 /* the same, and amax_after (a ZEROED device scalar) receives max |dafter| of what the call writes: the bound the UNet backward's first
  * fp16x2 data gradient scales dv by, without a pass over the image (round 5).  dafter is written, never added to.  Returns DF_E_SHAPE
- * where only the one-cell-at-a-time kernel applies (DF_GATHER_BWD_V1, > 2^29 points): call df_gather_bwd + df_absmax then. */
+ * where only the one-cell-at-a-time kernel applies (>= 2^29 points or >= 2^28 cells per image): call df_gather_bwd + df_absmax then. */
 int df_gather_bwd_m(const float* dh0, const uint32_t* idx_sorted, const int32_t* cell_rng, const int32_t* cpos,
                     int B, int N, df_img dbefore, df_img dafter, int accumulate_before, int nblk, float* amax_after, void* stream);
 /* partial[blk][i*nb+j] = sum over valid rows of a[row][i] * (b ? b[row][j] : 1); row r is valid iff

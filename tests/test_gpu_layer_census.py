@@ -63,7 +63,7 @@ ALLOW = {
     # the measured maximum)
     **{k: "test_gpu_decoder_cases.py::test_gather_backward_forms_bit_exact, ::test_decoder_case_vs_float64" for k in (
         "df_gather_bwd", "df_gather_bwd_m")},
-    # the fp32 C-ABI wrappers of the _mp entries (no Python caller; the first-generation kernels behind them run under DF_GRU_V1)
+    # the fp32 C-ABI wrappers of the _mp entries (thin forwarders with mfma_bf16 = 0; no Python caller)
     **{k: "test_gpu_model.py::test_alternate_kernel_paths (through the _mp entry)" for k in (
         "df_gru_decoder_fwd", "df_gru_decoder_bwd", "df_gru_wgrad")},
     # the bf16 inference forward of the head (DeFlow.inference_dtype = "bf16")
