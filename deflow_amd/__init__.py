@@ -6,3 +6,4 @@ from .decoder import ConvGRU, ConvGRUDecoder, LinearDecoder  # noqa: F401
 from .timer import Timing  # noqa: F401
 from .cluster import dbscan, dynamic_cluster_labels  # noqa: F401
 from .voidmap import VoidMap, label_scene  # noqa: F401
+from .ground import GroundSegmenter  # noqa: F401

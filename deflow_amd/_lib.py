@@ -168,6 +168,9 @@ _SIGS = {
     "df_void_cast_probe": [P, P, P, I, I, F, F, F, F, I, I, I, I, I, P, P, P, P, I, P],
     "df_void_merge": [P, P, P, I, I, I, I, I, P],
     "df_void_query": [P, P, I, I, F, F, F, F, I, I, I, P, P, P],
+    "df_ground_cells": [P, P, I, I, F, F, F, F, F, I, I, I, P, P],
+    "df_ground_height": [P, I, I, I, I, I, I, I, I, I, I, P, P, P],
+    "df_ground_mask": [P, P, I, I, F, F, F, F, F, I, I, I, P, I, P, P],
     "df_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
     "df_adam_step_dev": [P, P, P, P, L, F, F, F, F, P, F, P],
 }

@@ -34,7 +34,7 @@ from .h5scene import H5File
 
 class HDF5Dataset:
     def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False, dynamic_key: str = "dufo_label",
-                 dynamic_sidecar: Optional[str] = ".dufo.npz"):
+                 dynamic_sidecar: Optional[str] = ".dufo.npz", ground_sidecar: str = ".ground.npz", ground_source: str = "auto"):
         """``dynamic_key``: the per-sweep dataset holding the per-point dynamic flag (non-zero = dynamic) that online cluster labels
         start from (``Trainer(cluster_labels=...)``).  UNPINNED: ``dufo_label`` is the name recalled from upstream's process.py (the
         DUFO pass writes it before HDBSCAN turns it into ``label``), hence an argument.  When both sweeps of a pair hold it, the item
@@ -43,13 +43,26 @@ class HDF5Dataset:
         ``python -m deflow_amd.voidmap data_dir=<directory>`` writes: one 0 / 1 array per timestamp, computed on the GPU by the void map
         of DESIGN.md section 6c (UNPINNED) -- ``dufo0`` / ``dufo1`` come from it.  An array whose length differs from the sweep's rows
         is a ValueError; a directory without sidecars gives the items it always gave.  None or "" switches the lookup off.
+        ``ground_source`` / ``ground_sidecar``: where ``gm0`` / ``gm1`` come from.  "auto": a group's own ``ground_mask`` dataset wins; a
+        group without one takes its mask from ``<directory>/<scene_id><ground_sidecar>`` -- the file
+        ``python -m deflow_amd.ground data_dir=<directory>`` writes: one 0 / 1 array per timestamp, computed on the GPU by the ground
+        segmenter of DESIGN.md section 6d (UNPINNED) -- and when neither exists a KeyError names that command.  "file": the dataset only.
+        "sidecar": the sidecar only, which must exist; the datasets are ignored.  An array whose length differs from the sweep's rows is
+        a ValueError.  A directory whose files carry ``ground_mask`` gives the items it always gave.
         ``eval=True`` (the evaluation entry): read ``index_eval.pkl`` -- the frames of the official validation benchmark, the ones
         that carry an ``eval_mask`` -- when the directory has one, as upstream's dataset does for ``av2_mode=val`` (recalled: the
         module is in the absent submodule); ``index_total.pkl`` lists every sweep of every scene."""
         self.directory = directory
         self.dynamic_key = dynamic_key
         self.dynamic_sidecar = dynamic_sidecar
+        if ground_source not in ("auto", "file", "sidecar"):
+            raise ValueError(f"ground_source must be 'auto', 'file' or 'sidecar', got {ground_source!r}")
+        if ground_source == "sidecar" and not ground_sidecar:
+            raise ValueError("ground_source='sidecar' needs a ground_sidecar suffix")
+        self.ground_sidecar = ground_sidecar
+        self.ground_source = ground_source
         self._sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()       # cached per scene like the open files (None: no file)
+        self._ground_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
         name = "index_total.pkl"
         if eval and os.path.exists(os.path.join(directory, "index_eval.pkl")):
             name = "index_eval.pkl"
@@ -77,22 +90,38 @@ class HDF5Dataset:
                 self._files.move_to_end(scene_id)
             return f
 
-    def _sidecar(self, scene_id: str) -> Optional[dict]:
+    def _sidecar(self, scene_id: str, ground: bool = False) -> Optional[dict]:
+        cache, suffix = (self._ground_sidecars, self.ground_sidecar) if ground else (self._sidecars, self.dynamic_sidecar)
         with self._lock:
-            if scene_id in self._sidecars:
-                self._sidecars.move_to_end(scene_id)
-                return self._sidecars[scene_id]
-        path = os.path.join(self.directory, f"{scene_id}{self.dynamic_sidecar}")
+            if scene_id in cache:
+                cache.move_to_end(scene_id)
+                return cache[scene_id]
+        path = os.path.join(self.directory, f"{scene_id}{suffix}")
         side = None
         if os.path.exists(path):
             import numpy as np
             with np.load(path, allow_pickle=False) as z:
                 side = {k: z[k] for k in z.files if k != "meta"}
         with self._lock:
-            self._sidecars[scene_id] = side
-            while len(self._sidecars) > self._max_open:
-                self._sidecars.popitem(last=False)
+            cache[scene_id] = side
+            while len(cache) > self._max_open:
+                cache.popitem(last=False)
         return side
+
+    def _ground(self, scene_id: str, ts: str, group, rows: int) -> torch.Tensor:
+        """the ground mask of one sweep, by ``ground_source``"""
+        if self.ground_source == "file" or (self.ground_source == "auto" and "ground_mask" in group):
+            return torch.from_numpy(group["ground_mask"].read())
+        side = self._sidecar(scene_id, ground=True) if self.ground_sidecar else None
+        if side is None or ts not in side:
+            what = "does not exist" if side is None else f"has no entry for sweep {ts}"
+            raise KeyError(f"{scene_id}: no ground mask for sweep {ts} (ground_source={self.ground_source!r}): "
+                           f"{scene_id}{self.ground_sidecar} {what}; write it with  python -m deflow_amd.ground data_dir={self.directory}")
+        mask = torch.from_numpy(side[ts]).reshape(-1)
+        if mask.shape[0] != rows:
+            raise ValueError(f"{scene_id}{self.ground_sidecar}: {mask.shape[0]} ground flags for sweep {ts}, which has {rows} rows: "
+                             "the sidecar belongs to another version of the scene file")
+        return mask != 0
 
     def __getitem__(self, index: int) -> Dict[str, object]:
         scene_id, timestamp = self.data_index[index][0], str(self.data_index[index][1])
@@ -107,9 +136,10 @@ class HDF5Dataset:
             timestamp = f.sweeps[k]
         g0, g1 = f[timestamp], f[f.sweeps[k + 1]]
         t = lambda d: torch.from_numpy(d.read())
+        pc0, pc1 = t(g0["lidar"])[:, :3], t(g1["lidar"])[:, :3]
         item = {"scene_id": scene_id, "timestamp": int(timestamp),
-                "pc0": t(g0["lidar"])[:, :3], "gm0": t(g0["ground_mask"]), "pose0": t(g0["pose"]),
-                "pc1": t(g1["lidar"])[:, :3], "gm1": t(g1["ground_mask"]), "pose1": t(g1["pose"])}
+                "pc0": pc0, "gm0": self._ground(scene_id, timestamp, g0, pc0.shape[0]), "pose0": t(g0["pose"]),
+                "pc1": pc1, "gm1": self._ground(scene_id, f.sweeps[k + 1], g1, pc1.shape[0]), "pose1": t(g1["pose"])}
         if "flow" in g0:
             item.update(flow=t(g0["flow"]), flow_is_valid=t(g0["flow_is_valid"]),
                         flow_category_indices=t(g0["flow_category_indices"]))

@@ -667,6 +667,38 @@ int df_void_merge(const uint32_t* F, const uint32_t* O, uint32_t* V, int B, int 
 int df_void_query(const float* points, const int32_t* count, int B, int N, float gminx, float gminy, float gminz, float k, int Gx, int Gy,
                   int Gz, const uint32_t* V, int32_t* flags, void* stream);
 
+/* ------------------------------------------------------------------ ground segmentation: the per-point ground mask of a raw sweep ----
+ * The `ground_mask` the reader needs and collate_fn_pad drops, computed on the GPU.  UNPINNED: upstream writes it offline on the CPU with
+ * a line-fit ground segmenter (absent submodule).  This is a height-map segmenter with every choice fixed, so that the maps and the mask
+ * are a pure integer function of the input; parity with upstream's masks is not claimed.
+ *   grid            (xmin, ymin) fp32, cell size `cell`, dims (Gx, Gy); heights in H levels of z_unit from z_min.  kxy = fp32(1 / cell) and
+ *                   kz = fp32(1 / z_unit) are computed on the host and passed as floats
+ *   quantisation    the only floating-point step: ux = fp32(fp32(x - xmin) * kxy), uy likewise, uz = fp32(fp32(z - z_min) * kz): two
+ *                   separately rounded fp32 operations each; cx = floor(ux), cy = floor(uy), h = floor(uz)
+ *   participating   i < count[b], three finite coordinates, 0 <= ux < Gx, 0 <= uy < Gy, 0 <= uz < H (compared on the floats, before the
+ *                   floor).  Every other row gets mask 0
+ *   cell minima     zmin[b][cy][cx] = the minimum h over the cell's participating rows; EMPTY = 2^31 - 1 when it has none
+ *   height map      from the origin cell (ox, oy) (the caller quantises the origin the same way and clamps each index into the grid)
+ *                   and seed = floor(fp32(fp32(seed_z - z_min) * kz)).  A cell with offset (dx, dy) from the origin cell and
+ *                   r = max(|dx|, |dy|) has the ancestors a_k = (ox + clamp(dx, -k, k), oy + clamp(dy, -k, k)), k = 0 .. r (a_r is the
+ *                   cell itself).  Start with g = seed, miss = miss_cap; at step k, z = zmin[a_k], w = WIDEN * min(miss, miss_cap); a_k
+ *                   is accepted when z != EMPTY and g - DROP - w <= z <= g + RISE + w: then g = z, miss = 0; otherwise
+ *                   miss = min(miss + 1, miss_cap).  height = g after step r; observed = 1 when step r accepted, else 0
+ *   mask            a participating row is ground when h <= height[cell] + TOL
+ * df_ground_cells: points [B,N,3] f32, count [B] i32 -> zmin i32[B,Gy,Gx].  The entry fills zmin with EMPTY itself (an async 32-bit memset
+ *   on the stream): the caller only provides the storage.  32-bit integer atomic min after a plain test of the cell.
+ * df_ground_height: zmin -> height i32[B,Gy,Gx], observed u8[B,Gy,Gx], both written completely.
+ * df_ground_mask: -> mask u8[B,N], written completely.
+ * 1 <= Gx, Gy <= 4096, 1 <= B <= 65535, N >= 1, B * N < 2^30: violations return DF_E_SHAPE.  H outside [1, 2^20], a non-finite xmin /
+ * ymin / z_min, kxy or kz not positive and finite, (ox, oy) outside the grid, a negative threshold, miss_cap outside [0, 64] and NULL
+ * buffers return DF_E_ARG.  No launch then.  The entries never allocate or synchronise. */
+int df_ground_cells(const float* points, const int32_t* count, int B, int N, float xmin, float ymin, float kxy, float z_min, float kz,
+                    int Gx, int Gy, int H, int32_t* zmin, void* stream);
+int df_ground_height(const int32_t* zmin, int B, int Gx, int Gy, int ox, int oy, int seed, int rise, int drop, int widen, int miss_cap,
+                     int32_t* height, uint8_t* observed, void* stream);
+int df_ground_mask(const float* points, const int32_t* count, int B, int N, float xmin, float ymin, float kxy, float z_min, float kz,
+                   int Gx, int Gy, int H, const int32_t* height, int tol, uint8_t* mask, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
