@@ -50,13 +50,19 @@ ALLOW = {
     # pillar stage -> tests/test_gpu_kernels.py::test_pillar_bands_vs_oracle, ::test_pillarize_backward
     **{k: "test_gpu_kernels.py::test_pillar_bands_vs_oracle, ::test_pillarize_backward" for k in (
         "df_pillar2_hist", "df_pillar2_scan", "df_pillar2_scatter", "df_pillar2_band", "df_pillar2_band_sp", "df_pfn_bn_finalize",
-        "df_pfn_bn_finalize2", "df_pfn_bwd_stats", "df_pfn_bwd_finalize", "df_pfn_bwd_weights", "df_cell_sort")},
+        "df_pfn_bn_finalize2", "df_cell_sort")},
+    # the feature net's backward trio: both reductions, train / eval, the trainer's two-call accumulating form and the launch geometry
+    # (tests/helpers/pfn_cases.py), against float64 at a 2e-5 floor
+    **{k: "test_gpu_pfn_cases.py::test_pfn_case_vs_float64" for k in ("df_pfn_bwd_stats", "df_pfn_bwd_finalize", "df_pfn_bwd_weights")},
     # GRU trio (and the decoder's bias-sum / weight-plane helpers): one golden input (B = 3, rows 333 / 0 / 1) at 1 - 16 iterations, and
     # the cases built for the row tiles and split-K walks (tests/helpers/decoder_cases.py), lean / lean_fp32 / full forms
     **{k: "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64" for k in (
         "df_gru_decoder_fwd_mp", "df_gru_decoder_bwd_mp", "df_gru_wgrad_mp", "df_gru_xtab", "df_gru_lean_fwd", "df_gru_lean_bwd",
         "df_gru_lean_wgrad", "df_gru_lean_head_wgrad", "df_gru_lean_finalize", "df_gru_head_wgrad", "df_split_bf16x2_rows",
-        "df_colsum_finalize", "df_conv2d_wgrad_reduce")},
+        "df_conv2d_wgrad_reduce")},
+    # the column sum that ends the decoder's bias sums and the feature net's dW (the latter also with accumulate = 1)
+    "df_colsum_finalize": "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64, "
+                          "test_gpu_pfn_cases.py::test_pfn_case_vs_float64",
     # the two-stage column sum runs from B ceil(N / 64) >= 2048 only: the `blocks` case
     "df_colsum_stage": "test_gpu_decoder_cases.py::test_decoder_case_vs_float64[blocks-*]",
     # the segmented gather backward: against float64 above, and to the bit against the sequential fp32 sum (both lane forms, accumulate,
