@@ -7,7 +7,8 @@ The checkpoint carries its training configuration (``hyper_parameters``, as Ligh
 checkpoint and the data need naming.  Metrics: deflow_amd/metrics.py -- ``leaderboard_version=1`` (default) the Argoverse-2 three-way
 EPE table, ``leaderboard_version=2`` the bucketed normalised EPE; plus a range-free EPE / accuracy summary -- over the sweeps
 of ``val_data`` (preprocessed scene files, deflow_amd/data.py) or over seeded synthetic pairs with ``val_data=synthetic``.
-``av2_mode=test`` (leaderboard submission zips) is the reference's control plane and is not built."""
+``metrics_impl=device`` accumulates the same tables and summary on the GPU (deflow_amd/metrics_device.py: no host sync per batch; default
+``host``).  ``av2_mode=test`` (leaderboard submission zips) is the reference's control plane and is not built."""
 from __future__ import annotations
 
 import json
@@ -16,11 +17,12 @@ import sys
 
 import torch
 
-from .train import DATA_KEYS, DEFAULTS, _TARGET_ALIASES, build_model, grid_from, parse_overrides
+from .train import DATA_KEYS, DEFAULTS, _TARGET_ALIASES, build_model, grid_from, parse_overrides, split_metrics_impl
 
 
 def main(argv=None):
-    args = list(sys.argv[1:] if argv is None else argv)
+    # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
+    metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
     if given.get("av2_mode", "av2_mode=val") != "av2_mode=val":
         raise SystemExit("only av2_mode=val is implemented (test-split submission files are out of scope)")
@@ -59,7 +61,11 @@ def main(argv=None):
     version = int(given.get("leaderboard_version", "leaderboard_version=1").split("=", 1)[1])
     if version not in (1, 2):
         raise SystemExit("leaderboard_version must be 1 (three-way EPE) or 2 (bucketed normalised EPE)")
-    official = OfficialMetrics()
+    if metrics_impl == "device":      # the same tables and summary accumulated on the GPU, no host sync per batch (metrics_device.py)
+        from .metrics_device import DeviceMetrics, evaluate_batch_device
+        official = DeviceMetrics(dev)
+    else:
+        official = OfficialMetrics()
     model = build_model(cfg).to(dev)
     res = model.load_from_checkpoint(path)
     if res.missing_keys or res.unexpected_keys:   # strict=False as the reference loads [REF deflow.py:47] -- but never silently
@@ -82,12 +88,15 @@ def main(argv=None):
     tot, wsum = {}, {}
     with torch.no_grad():
         for batch in batches:
+            if metrics_impl == "device":
+                evaluate_batch_device(model, batch, official)
+                continue
             m = evaluate_batch(model(batch), batch, official)
             w = len(batch["pose0"])
             for k, v in m.items():
                 tot[k] = tot.get(k, 0.0) + v * w
                 wsum[k] = wsum.get(k, 0) + w
-    out = {k: tot[k] / wsum[k] for k in tot}
+    out = official.summary() if metrics_impl == "device" else {k: tot[k] / wsum[k] for k in tot}
     # the leaderboard table the reference prints at the end of validation [REF README.md:88-91]: leaderboard_version=1 the three-way
     # EPE (+ IoU, accuracies, angle error inside the 35 m box), leaderboard_version=2 the bucketed normalised EPE
     board = official.result(version)

@@ -10,7 +10,11 @@ hydra-style ``key=value`` overrides (lists in brackets, dotted ``model.target.*`
 on (``<scene>.h5`` + ``index_total.pkl``, section 8(f) N2) through deflow_amd/data.py (in-tree HDF5 reader, NaN-pad
 collate, per-rank sharding, ``num_workers`` reader threads prefetching to the GPU; ``stage_dir=<scratch>`` first copies
 the files node-local as 1_train.sh does); ``train_data=synthetic`` draws seeded Argoverse-2-shaped pairs
-(deflow_amd/synth.py).  wandb / slurm keys are accepted and ignored."""
+(deflow_amd/synth.py).  wandb / slurm keys are accepted and ignored.
+
+``metrics_impl=device`` (default ``host``) accumulates the per-epoch validation line on the GPU (deflow_amd/metrics_device.py) instead of
+per sample on the host.  The line is then ``DeviceMetrics.summary()``, weighted by batch size; that equals the host path's plain mean
+over batches when all batches are equal-sized and carry every key.  The key is not a hyper-parameter and is never saved."""
 from __future__ import annotations
 
 import ast
@@ -43,6 +47,22 @@ _IGNORED_PREFIXES = ("wandb", "slurm", "hydra", "model.val_monitor", "exp_note",
 _TARGET_ALIASES = {"model.target.voxel_size": "voxel_size", "model.target.point_cloud_range": "point_cloud_range",
                    "model.name": "model", "optimizer.lr": "lr"}
 DATA_KEYS = ("dataset_path", "train_data", "val_data")
+# metrics_impl=host|device: WHERE the validation metrics are accumulated (metrics.py on per-sample tensors, or metrics_device.py on the
+# padded batch without a host sync).  Not a hyper-parameter: it is taken off the command line before parse_overrides and never saved.
+METRICS_IMPLS = ("host", "device")
+
+
+def split_metrics_impl(args: List[str]):
+    """-> (metrics_impl, the other arguments); the last metrics_impl= wins, default host"""
+    impl, rest = "host", []
+    for a in args:
+        if a.lstrip("+").split("=", 1)[0] == "metrics_impl" and "=" in a:
+            impl = a.split("=", 1)[1]
+        else:
+            rest.append(a)
+    if impl not in METRICS_IMPLS:
+        raise SystemExit(f"metrics_impl must be one of {', '.join(METRICS_IMPLS)}, got {impl!r}")
+    return impl, rest
 
 
 def parse_overrides(argv: List[str]) -> Dict[str, Any]:
@@ -138,7 +158,8 @@ def save_checkpoint(path: str, model, trainer, cfg, epoch: int, step: int):
 
 
 def main(argv=None):
-    cfg = parse_overrides(sys.argv[1:] if argv is None else argv)
+    metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
+    cfg = parse_overrides(args)
     rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     assert torch.cuda.is_available(), "training runs on the HIP engine only"
     local = local % torch.cuda.device_count()      # more ranks than GPUs only in tests (dist_backend=gloo, ranks share a device)
@@ -244,7 +265,16 @@ def main(argv=None):
         trainer.sync_buffers()         # every rank validates (and rank 0 saves) rank 0's BatchNorm statistics, as DDP does
         model.eval()
         with torch.no_grad():
-            if val_loader is not None:
+            if metrics_impl == "device":
+                # the batch-size-weighted summary of metrics_device.DeviceMetrics, nothing read back until the epoch's batches are queued.
+                # It equals the plain mean over batches below when all batches are equal-sized and carry every key
+                from deflow_amd.metrics_device import DeviceMetrics, evaluate_batch_device
+                dm = DeviceMetrics(dev)
+                for vb in (val_loader if val_loader is not None
+                           else [synth_batch(min(B, 4), N, seed=int(cfg["seed"]) + 10 ** 6 + epoch, grid_hw=(H, H), device=dev)]):
+                    evaluate_batch_device(model, vb, dm)
+                metrics = dm.summary()
+            elif val_loader is not None:
                 per_batch = [evaluate_batch(model(vb), vb) for vb in val_loader]
                 metrics = {k: float(sum(m[k] for m in per_batch) / max(len(per_batch), 1)) for k in (per_batch[0] if per_batch else {})}
             else:

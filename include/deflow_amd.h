@@ -699,6 +699,40 @@ int df_ground_height(const int32_t* zmin, int B, int Gx, int Gy, int ox, int oy,
 int df_ground_mask(const float* points, const int32_t* count, int B, int N, float xmin, float ymin, float kxy, float z_min, float kz,
                    int Gx, int Gy, int H, const int32_t* height, int tol, uint8_t* mask, void* stream);
 
+/* ------------------------------------------------------------------ validation metrics, accumulated on the device ----
+ * The tables of deflow_amd/metrics.py OfficialMetrics (leaderboard versions 1 and 2) and the range-free summary of evaluate_batch, fed a
+ * whole padded batch per call (what DeFlow.forward_padded leaves on the device) and read back only when the caller reads the state.
+ * Inputs: flow [B,N,3] f32 (compact rows i < counts[b]); idx_c [B,N] i64 (compact row -> row of the padded batch); pose_flow, pc0 (the
+ * untransformed cloud), gt_flow [B,N,3] f32 and the optional u8 is_valid, eval_mask, cats [B,N], all read at j = idx_c[b,i]; counts [B] i32
+ * (clamped to [0, N]).  A j outside [0, N) drops the row and adds 1 to the optional status word.
+ *   row arithmetic   est = fp32(pose_flow + flow) per component; from there double, every operation rounded on its own:
+ *                    norm(v) = sqrt((x x + y y) + z z); err = norm(est - gt); speed = norm(gt - pose_flow); est_speed = norm(est - pose_flow);
+ *                    rel = err / (norm(gt) + 1e-10); strict / relaxed accuracy = err < t or rel < t, t = 0.05 / 0.10; dynamic = speed >= 0.05;
+ *                    ok = is_valid and eval_mask (each 1 when absent); cat = min(cats, 30) (0 when absent); finite = the twelve values
+ *   version 1        sel = finite, ok, |pc0.x| <= 35, |pc0.y| <= 35; foreground = cat != 0.  Per frame: the mean err of foreground-dynamic,
+ *                    foreground-static and background-static rows, tp / (tp + fp + fn) of the dynamic flags (est_speed >= 0.05 against
+ *                    dynamic), the means of err, both accuracies and the space-time angle arccos(clamp((est.gt + 0.01) /
+ *                    (sqrt(est.est + 0.01) sqrt(gt.gt + 0.01)))) over sel; each value that exists is added to v1_sum, its v1_cnt raised by 1
+ *   version 2        finite, ok, sqrt(x x + y y) <= 35 and an evaluated category: cell = meta-class x 51 + (number of edges <= speed), the 50
+ *                    edges a host-computed double[50] (k * 2.0 / 50, k = 1 .. 50); err_sum, speed_sum and count per cell
+ *   summary          over ok rows with finite est and gt, per sample: mean err, both accuracies, n, the mean err of the three classes
+ *                    (foreground = cats != 0, every row when cats is absent) and the mean of those that exist; per call, each key's mean
+ *                    over the samples that have it, then tot[key] += mean * B, wsum[key] += B
+ *   skip rule        with has_eval_mask [B] u8: a sample without one is left out of everything iff some sample of the call has one
+ * df_metrics_rows: rows -> per-block partials in ws (df_metrics_rows_per_block() rows per block; fixed reduction order, no float atomics).
+ * df_metrics_accumulate: partials -> per-frame sums (ascending block order) -> the running state (ascending sample order):
+ *   state_f double[526] = v1_sum[8] (EPE_FD EPE_FS EPE_BS IoU EPE AccS AccR Angle), err_sum[5][51], speed_sum[5][51], tot[8]
+ *   state_i int64[272]  = v1_cnt[8], n, count[5][51], wsum[8]            (summary keys: EPE AccS AccR n EPE_FD EPE_FS EPE_BS EPE_3way)
+ * ws: df_metrics_ws_bytes(B, N) bytes, 8-byte aligned (DF_E_ALIGN).  1 <= B <= 65535, N >= 1, B * N < 2^31: violations return DF_E_SHAPE;
+ * NULL required buffers return DF_E_ARG.  No launch then.  The entries never allocate or synchronise; two runs are bit-identical. */
+int df_metrics_rows_per_block(void);
+int64_t df_metrics_ws_bytes(int B, int N);
+int df_metrics_rows(const float* flow, const float* pose_flow, const float* pc0, const float* gt_flow, const int64_t* idx_c,
+                    const int32_t* counts, const uint8_t* is_valid /*nullable*/, const uint8_t* eval_mask /*nullable*/,
+                    const uint8_t* cats /*nullable*/, int B, int N, const double* edges, void* ws, int32_t* status /*nullable*/, void* stream);
+int df_metrics_accumulate(const int32_t* counts, const uint8_t* has_eval_mask /*nullable*/, int B, int N, void* ws, double* state_f,
+                          int64_t* state_i, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
