@@ -8,3 +8,4 @@ from .cluster import dbscan, dynamic_cluster_labels  # noqa: F401
 from .voidmap import VoidMap, label_scene  # noqa: F401
 from .ground import GroundSegmenter  # noqa: F401
 from .metrics_device import DeviceMetrics  # noqa: F401
+from .sweeps import SweepFlow  # noqa: F401

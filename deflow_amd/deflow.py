@@ -44,6 +44,17 @@ def cal_pose0to1(pose0: torch.Tensor, pose1: torch.Tensor, form: Optional[str] =
     return inv @ pose0.type(inv.dtype)
 
 
+def batch_transform(batch: Dict[str, torch.Tensor], device) -> torch.Tensor:
+    """T [B,4,4] f32 on ``device``: the batch's ``ego_motion`` when it has one, else inv(pose1) pose0 per sample.  The one place the
+    transform is formed: forward_padded and sweeps.SweepFlow (whose pose flow must have the same bits) both call it."""
+    with torch.no_grad():
+        if "ego_motion" in batch:
+            T = batch["ego_motion"]
+        else:
+            T = torch.stack([cal_pose0to1(batch["pose0"][b], batch["pose1"][b]) for b in range(len(batch["pose0"]))])
+        return T.to(device=device, dtype=torch.float32).contiguous()
+
+
 _CANVASES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()   # model -> {shape key: (canvas, occupancy words)}: persistent canvases
 # ... and who used an entry last: {"stream", "event" (recorded behind the forward's last reader; None under capture), "captured", "tick"}.
 # A persistent canvas is ONE buffer per (model, shape): two forwards of a model that may overlap on the GPU -- another stream, a second host
@@ -229,12 +240,7 @@ class DeFlow(nn.Module):
         pc1s = batch["pc1"].contiguous().float()
         B, N, _ = pc0.shape
         self.timer[0][0].start("pose")
-        with torch.no_grad():
-            if "ego_motion" in batch:
-                T = batch["ego_motion"]
-            else:
-                T = torch.stack([cal_pose0to1(batch["pose0"][b], batch["pose1"][b]) for b in range(len(batch["pose0"]))])
-            T = T.to(device=pc0.device, dtype=torch.float32).contiguous()
+        T = batch_transform(batch, pc0.device)
         self.timer[0][0].stop()
         self.timer[0][1].start("transform")
         pc0s = torch.empty_like(pc0)

@@ -20,6 +20,31 @@ import torch
 from .train import DATA_KEYS, DEFAULTS, _TARGET_ALIASES, build_model, grid_from, parse_overrides, split_metrics_impl
 
 
+def resolve_config(path: str, given: dict, skip=()) -> dict:
+    """The configuration of a command that works from a checkpoint (eval, save): defaults < what the checkpoint was trained with < what
+    the command line names.  ``given``: {key: "key=value"} as typed; the keys in ``skip`` are the command's own and are left out.  The
+    reference's Lightning checkpoints hold a NESTED (omegaconf) config -- model.target.num_iters etc. -- so it is flattened to the
+    dotted keys used here; keys this trainer does not know are ignored."""
+    from .ckpt import flatten, load_checkpoint, plain
+    ckpt = load_checkpoint(path)
+    cfg = dict(DEFAULTS)
+    hp = plain(ckpt.get("hyper_parameters", {}))
+    saved = flatten(hp.get("cfg", hp) if isinstance(hp, dict) else {})
+    # nested reference configs name the architecture ``model.name`` (and repeat voxel_size / point_cloud_range under
+    # ``model.target``): map them onto this trainer's keys BEFORE filtering, or a fastflow3d checkpoint is built as DeFlow and
+    # loaded with strict=False (ADVICE r2)
+    saved = {_TARGET_ALIASES.get(k, k): v for k, v in saved.items()}
+    cfg.update({k: v for k, v in saved.items() if k in DEFAULTS and k not in DATA_KEYS and not isinstance(v, dict)})
+    typed = parse_overrides([a for k, a in given.items() if k not in skip])
+    cfg.update({k: typed[k] for k in typed["_given"] if k in typed})
+    for k in ("train_data", "val_data"):       # dataset_path=<root> [REF 2_eval.sh:33-35] -> <root>/val
+        if typed[k] != DEFAULTS[k]:
+            cfg[k] = typed[k]
+    if cfg["model"] == "fastflow3d":
+        cfg["model.target.decoder_option"] = "linear"
+    return cfg
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
@@ -29,26 +54,7 @@ def main(argv=None):
     if "checkpoint" not in given:
         raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]")
     path = given["checkpoint"].split("=", 1)[1]
-    from .ckpt import flatten, load_checkpoint, plain
-    ckpt = load_checkpoint(path)
-    # configuration: defaults < what the checkpoint was trained with < what this command line names.  The reference's
-    # Lightning checkpoints hold a NESTED (omegaconf) config -- model.target.num_iters etc. -- so it is flattened to the
-    # dotted keys used here; keys this trainer does not know are ignored.
-    cfg = dict(DEFAULTS)
-    hp = plain(ckpt.get("hyper_parameters", {}))
-    saved = flatten(hp.get("cfg", hp) if isinstance(hp, dict) else {})
-    # nested reference configs name the architecture ``model.name`` (and repeat voxel_size / point_cloud_range under
-    # ``model.target``): map them onto this trainer's keys BEFORE filtering, or a fastflow3d checkpoint is built as DeFlow and
-    # loaded with strict=False
-    saved = {_TARGET_ALIASES.get(k, k): v for k, v in saved.items()}
-    cfg.update({k: v for k, v in saved.items() if k in DEFAULTS and k not in DATA_KEYS and not isinstance(v, dict)})
-    typed = parse_overrides([a for k, a in given.items() if k not in ("leaderboard_version", "inference_dtype")])
-    cfg.update({k: typed[k] for k in typed["_given"] if k in typed})
-    for k in ("train_data", "val_data"):       # dataset_path=<root> [REF 2_eval.sh:33-35] -> <root>/val
-        if typed[k] != DEFAULTS[k]:
-            cfg[k] = typed[k]
-    if cfg["model"] == "fastflow3d":
-        cfg["model.target.decoder_option"] = "linear"
+    cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
     if not any(k in given for k in DATA_KEYS):
         print("[deflow_amd.eval] NOTE: no dataset_path= / val_data= given -- evaluating on seeded SYNTHETIC pairs, not on a "
               "dataset (the reference reads its config's dataset_path default here)", file=sys.stderr)

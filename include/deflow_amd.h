@@ -733,6 +733,39 @@ int df_metrics_rows(const float* flow, const float* pose_flow, const float* pc0,
 int df_metrics_accumulate(const int32_t* counts, const uint8_t* has_eval_mask /*nullable*/, int B, int N, void* ws, double* state_f,
                           int64_t* state_i, void* stream);
 
+/* ------------------------------------------------------------------ whole-sweep flow: what the save command writes per raw row ----
+ * UNPINNED: the reference's save.py writes the estimated flow of every sweep into the dataset under the checkpoint's name; its source is
+ * absent, so this definition is the project's own.  For sweep k of a scene (rows p_r of `lidar`, N_raw of them), its
+ * successor and T = ego_motion or inv(pose1) pose0 exactly as DeFlow.forward_padded forms it:
+ *   pose flow       of a raw row: what df_ego_transform computes for it -- per component i, a = fp32(x T[i][0]); a = fp32(a + fp32(y T[i][1]));
+ *                   a = fp32(a + fp32(z T[i][2])); a = fp32(a + T[i][3]); pose_flow = fp32(a - p[i]): one rounding per operation
+ *   decoded row     not ground, three finite coordinates, inside the model's range: the rows behind idx_c0[b, i], i < counts0[b].
+ *                   flow_est = fp32(pose_flow + flow) per component; dynamic = (fp32(fp32(fp32(fx fx) + fp32(fy fy)) + fp32(fz fz)) >=
+ *                   0.0025f) on the model's flow alone -- the 0.05 m per frame of the version-1 metrics, compared as squares
+ *   other finite    rows (ground, out of range): flow_est = pose_flow, dynamic = 0
+ *   non-finite      rows and padded rows r >= count_raw[b]: flow_est = (0, 0, 0), dynamic = 0
+ *   half            flow_est rounded to fp16, round to nearest even
+ * df_sweep_compact: raw [B,N,3] f32, count_raw [B] i32 (clamped to [0, N]), drop [B,N] u8 (non-zero = ground) -> pc [B,N,3]: the kept rows
+ *   (r < count_raw[b], drop == 0) first, in their order and bit for bit, every further row three fp32 NaNs of pattern 0x7FC00000 (what
+ *   collate_fn_pad pads with); row_of [B,N] i32: the raw row of each kept row, -1 in the padding; pos_of [B,N] i32: the compact position of
+ *   each raw row, -1 for dropped and padded rows; kept [B] i32.  df_sweep_rows_per_block() raw rows per block; ws: df_sweep_compact_ws_bytes
+ *   (B, N) bytes.  Every output element is written exactly once.
+ * df_flow_compose: raw, count_raw, T [B,4,4] f32, pos_of as above; flow [B,Nc,3] f32, idx_c [B,Nc] i64 (compact position of decoded row i,
+ *   no duplicates among the first counts[b]; an entry outside [0, N) is ignored), counts [B] i32 (clamped to [0, Nc]) -> flow_est [B,N,3]
+ *   f32 (half = 0) or f16 (half = 1), dynamic [B,N] u8.  ws: df_flow_compose_ws_bytes(B, N) bytes.  Every output element is written exactly
+ *   once.
+ * ws 4-byte aligned (DF_E_ALIGN).  1 <= B <= 65535, N >= 1 (and Nc >= 1), B * N < 2^31: violations return DF_E_SHAPE (the _ws_bytes
+ * functions return it too); NULL buffers and half outside {0, 1} return DF_E_ARG.  No launch then.  The entries never allocate or
+ * synchronise and read nothing back; two runs are bit-identical. */
+int df_sweep_rows_per_block(void);
+int64_t df_sweep_compact_ws_bytes(int B, int N);
+int df_sweep_compact(const float* raw, const int32_t* count_raw, const uint8_t* drop, int B, int N, void* ws, float* pc, int32_t* row_of,
+                     int32_t* pos_of, int32_t* kept, void* stream);
+int64_t df_flow_compose_ws_bytes(int B, int N);
+int df_flow_compose(const float* raw, const int32_t* count_raw, const float* T, const int32_t* pos_of, const float* flow,
+                    const int64_t* idx_c, const int32_t* counts, int B, int N, int Nc, int half, void* ws, void* flow_est,
+                    uint8_t* dynamic, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
