@@ -22,7 +22,7 @@ from .autograd import DeFlowFn
 from .decoder import ConvGRUDecoder, LinearDecoder, PointSet
 from .encoder import DynamicEmbedder, canvas_alloc
 from .timer import Timing
-from .unet import FastFlow3DUNet
+from .unet import FastFlow3DUNet, check_tile_rule
 
 
 POSE_INVERSE = "rigid"   # "rigid" | "general" (torch.linalg.inv): see cal_pose0to1
@@ -164,6 +164,10 @@ class DeFlow(nn.Module):
         emb = self.embedder
         B = pc0s.shape[0]
         dev = pc0s.device
+        if train and isinstance(self.backbone, FastFlow3DUNet):
+            # the backbone's training grid rule (unet.check_tile_rule; FastFlow3DUNet.run checks it again for its direct callers),
+            # asked before the feature net runs: a refused forward has launched nothing and moved no running statistic
+            check_tile_rule(B, emb.H, emb.W)
         merged = not save and pc0s.shape == pc1s.shape and os.environ.get("DF_MERGE_CLOUDS") != "0"
         # round 5: a PERSISTENT canvas where the engine owns its lifetime -- no-grad forwards and the trainer's one-forward-one-
         # backward step (`_persist_canvas`, set by optim.Trainer) -- so that the band kernels write occupied cells only instead of

@@ -82,7 +82,9 @@ def _cwn_forward(m: ConvWithNorms, x: DfImg, z: DfImg, n_imgs: int, groups: int,
     ipg = n_imgs // groups
     rows_pg = ipg * z.h * z.w
     tile_m = ops.conv_tile_m(rows_pg, C)
-    assert rows_pg % tile_m == 0, "BatchNorm statistic groups must be a multiple of the row tile"
+    if rows_pg % tile_m:        # (FastFlow3DUNet.run checks its whole pyramid before the first launch: only a stand-alone layer gets here)
+        raise ValueError(f"batch statistics over {ipg} images of {z.h} x {z.w}: {rows_pg} rows per statistic group is not a multiple of "
+                         f"df_conv2d_tile_m = {tile_m}")
     tiles_pg = rows_pg // tile_m
     y = torch.empty(n_imgs, z.h, z.w, C, dtype=torch.bfloat16 if store16 else torch.float32, device=dev)
     partial = torch.empty(tiles_pg * groups, C, 2, dtype=torch.float32, device=dev)
@@ -131,6 +133,19 @@ def _h2p_ok(n: int, h: int, w: int, cin: int, cout: int, dev) -> bool:
             and call("df_conv2d_wgrad_h2p_ok", d(cin, 2), d(cout, 2), 3, 1) == 1)
 
 
+def check_tile_rule(B: int, H: int, W: int, widths=(64, 128, 256)) -> None:
+    """Training-mode (batch-statistic) grids: the conv epilogue sums the statistics per row tile and a tile belongs to ONE statistic
+    group (one cloud's B images), so at every level k = 1, 2, 3 the group's B * (H / 2^k) * (W / 2^k) rows must be whole tiles of
+    df_conv2d_tile_m.  Raises ValueError otherwise -- before anything is launched (no running statistic has moved)."""
+    for k, C in enumerate(widths, start=1):
+        rows_pg = B * (H >> k) * (W >> k)
+        tile_m = ops.conv_tile_m(rows_pg, C)
+        if rows_pg % tile_m:
+            raise ValueError(f"training with batch statistics on B = {B}, H = {H}, W = {W}: B*(H/2^k)*(W/2^k) must be a multiple of "
+                             f"df_conv2d_tile_m for k = 1, 2, 3, but k = {k} has {rows_pg} rows per statistic group and a tile of "
+                             f"{tile_m} (eval mode takes any H, W that are multiples of 8)")
+
+
 def _is_h2(t) -> bool:
     return getattr(t, "_df_h2", None) is not None
 
@@ -159,6 +174,8 @@ class FastFlow3DUNet(nn.Module):
         the returned tensor is NOT written."""
         B, H, W, _ = bstar.shape
         assert H % 8 == 0 and W % 8 == 0
+        if train:
+            check_tile_rule(B, H, W, [s[0].conv.out_channels for s in (self.encoder_step_1, self.encoder_step_2, self.encoder_step_3)])
         dev = bstar.device
         f32 = dict(dtype=torch.float32, device=dev)
         x = img_pair(bstar, 32)

@@ -16,6 +16,11 @@ Runs (each after two Adam steps at lr 2e-4, so that weights and BatchNorm runnin
   B  configs[1] forward: B = 1, 512 x 512, eval, DeFlow.forward_padded as the bench times it; + its flow against the CPU oracle
   C  bf16 training mode: Trainer(dtype="bf16"), B = 16, 256 x 256, 20 000 points (the bs16_256 shape); references on the bf16
      values the kernels read: fp32-stored outputs to fp32 summation accuracy, bf16-stored outputs within one bf16 ulp
+  D  run A's body on a rectangular grid: B = 16, [H, W] = [320, 512] (range +-51.2 m in x, +-32 m in y), 50 000 points -- the smallest
+     rectangular shape on which every form run A reaches is selected (tests/helpers/rect_cases.py), with h = 160 / 80 / 40 and every
+     h * w no power of two: the elementwise kernels decode their indices by real division, which A, B and C never do
+  E  run C's body on [H, W] = [192, 256] (range +-25.6 m in x, +-19.2 m in y), B = 16, 20 000 points: bf16-tile forms at h = 96 / 48
+Each run prints its wall time; D (0.625 of A's pixels) and E (0.75 of C's) stay below A and C.
 """
 import math
 import os
@@ -27,6 +32,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import ref64 as R  # noqa: E402
+import rect_cases as RC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -617,3 +623,38 @@ def test_census_B_configs1_forward_and_oracle(dev):
     print(f"[census B] configs[1] eval forward flow vs CPU oracle: max err / max|flow| = {e:.3e} (bound 1e-4)")
     _verdict(census, wall)
     assert e <= 1e-4
+
+
+def test_census_D_rectangular_fp32_step(dev):
+    """run A's body on [320, 512]: B = 16, 50 000 points, fp32 training step through the Trainer (eager)"""
+    import deflow_amd
+    from deflow_amd.optim import Trainer
+    from deflow_amd.synth import synth_batch
+    c = RC.case("320x512")
+    assert (c.grid, c.point_cloud_range, c.B, c.N) == ([320, 512], [-51.2, -32, -3, 51.2, 32, 3], 16, 50000)
+    torch.manual_seed(0)
+    model = deflow_amd.DeFlow(**c.cfg, num_iters=4).to(dev).train()
+    tr = Trainer(model, lr=2e-4)
+    batch = synth_batch(c.B, c.N, seed=Trainer.shard_seed(c.seed, 0, c.B), grid_hw=(512, 512), device=dev)
+    _two_adam_steps_then(tr, batch)
+    census, wall = _census_step("D", tr, model, batch, dev)
+    _verdict(census, wall)
+    forms = {r["form"] for r in census.rows}
+    assert any(str(f).endswith(",xp>") for f in forms) and "wgrad3_h2p_kernel<4>" in forms, sorted(map(str, forms))   # the pre-split forms ran
+
+
+def test_census_E_rectangular_bf16_training_mode(dev):
+    """run C's body on [192, 256]: Trainer(dtype="bf16"), B = 16, 20 000 points"""
+    import deflow_amd
+    from deflow_amd.optim import Trainer
+    from deflow_amd.synth import synth_batch
+    c = RC.case("192x256")
+    assert (c.grid, c.point_cloud_range, c.B, c.N) == ([192, 256], [-25.6, -19.2, -3, 25.6, 19.2, 3], 16, 20000)
+    torch.manual_seed(4242)
+    model = deflow_amd.DeFlow(**c.cfg).to(dev).train()
+    tr = Trainer(model, lr=2e-4, dtype="bf16")
+    batch = synth_batch(c.B, c.N, seed=c.seed, grid_hw=(256, 256), device=dev)
+    _two_adam_steps_then(tr, batch)
+    census, wall = _census_step("E", tr, model, batch, dev)
+    _verdict(census, wall)
+    assert any("ulps" in r for r in census.rows) and "wgrad3_tr_kernel<4>/bf16" in {r["form"] for r in census.rows}      # the bf16-tile stages ran
