@@ -113,8 +113,10 @@ def deflow_backward(model, st: dict, dflow: torch.Tensor, params: List[torch.Ten
     dv = torch.empty(B, H, W, 64, dtype=torch.float32, device=dev)
     # d(bstar) is only read at occupied pillars (pillar feature net backward): the UNet's two data gradients into it
     # -- skip conv and first encoder conv -- are evaluated there only (df_pillar_input_grad) instead of densely for
-    # all H*W cells.  DF_DENSE_CANVAS_GRAD=1 keeps the dense kernels (A/B, tests).
-    sparse = os.environ.get("DF_DENSE_CANVAS_GRAD") != "1" and isinstance(model.backbone, FastFlow3DUNet)
+    # all H*W cells.  DF_DENSE_CANVAS_GRAD=1 keeps the dense kernels (A/B, tests); so does a grid outside the bound of
+    # df_sparse_in_wgrad's packed cell coordinates (y << 16 | x).
+    sparse = (os.environ.get("DF_DENSE_CANVAS_GRAD") != "1" and isinstance(model.backbone, FastFlow3DUNet)
+              and H < 32768 and W < 65536)
     if sparse:
         # decoder: its gather backward writes d(before) = d(bstar) and d(after) = dv densely (a cheap stream)
         dh0 = model.head.run_backward(dflow, st["ps"], st["sv"], img(dbstar), img(dv), False, False, grads,

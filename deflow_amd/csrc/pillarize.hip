@@ -660,6 +660,15 @@ __global__ __launch_bounds__(576) void sparse_wgrad3x3_kernel(SparseWgradParams 
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // a window's sum (acc) is added to the workgroup's total (tot) when the window ends.  ONE fp32 chain over all n pixels of a workgroup
+  // loses ~2^-25 n / sqrt(2) of a term's size: 4.1e-6 of max |dW| for 9000 pixels in one workgroup (tests/helpers/sparse_cases.py, `wrap`
+  // at nblk = 1), twice the 2e-6 every other weight gradient keeps.  In two levels a chain is <= SW_WIN pixels or n / SW_WIN windows long.
+  // (with tot the kernel sits at its register limit of 168: the compiler spills 41 registers around a window's multiply loop, none inside it)
+  f32x4 tot[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
   const SampleRange sr = sample_range(p.counts, b);
   const int end = sr.off + sr.cnt;
@@ -731,6 +740,14 @@ __global__ __launch_bounds__(576) void sparse_wgrad3x3_kernel(SparseWgradParams 
         mma_step(a1, b1);
       }
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tot[i][j][r] += acc[i][j][r];   // (component by component: a vector add is v_pk_add_f32, which this file keeps out)
+        acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -742,7 +759,7 @@ __global__ __launch_bounds__(576) void sparse_wgrad3x3_kernel(SparseWgradParams 
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o[((16 * ct + 4 * lq + r) * 9 + tap) * 64 + 16 * nt + li] = acc[ct][nt][r];
+      for (int r = 0; r < 4; ++r) o[((16 * ct + 4 * lq + r) * 9 + tap) * 64 + 16 * nt + li] = tot[ct][nt][r];
   if (tap == 4 && p.bias_ws) {   // bsum[t] on lane (li, lq) = sum over this lane's pixels of dy[.., 16 t + li]
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -1600,6 +1617,7 @@ extern "C" int df_sparse_wgrad3x3_x2(const uint32_t* key_sorted, const int32_t* 
                  (dy.img_stride % 4) == 0 && df_aligned16(ws) && (!bias_ws || df_aligned16(bias_ws)),
              DF_E_ALIGN);
   DF_REQUIRE((int64_t)dy.h * dy.w * dy.ld < (int64_t)0x30000000 && (int64_t)x.h * x.w * x.ld < (int64_t)0x30000000, DF_E_SHAPE);   // 32-bit byte offsets
+  DF_REQUIRE(dy.w < 65536 && dy.h < 32768, DF_E_SHAPE);   // the pixel lists hold y << 16 | x in an int (df_sparse_wgrad3x3 has no such bound)
   SparseWgradParams p;
   p.key_sorted = key_sorted; p.counts = counts; p.H = dy.h; p.W = dy.w; p.dy = dy; p.x = x; p.ws = ws; p.bias_ws = bias_ws;
   hipLaunchKernelGGL(sparse_wgrad3x3_x2_kernel, dim3(nblk, B), dim3(576), 0, reinterpret_cast<hipStream_t>(stream), p);
@@ -1666,7 +1684,8 @@ extern "C" int df_sparse_in_wgrad(const uint32_t* key_sorted, const int32_t* cou
   DF_REQUIRE(key_sorted && counts && dy1 && canvas.ptr && ws && B > 0 && nblk > 0 && (cloud == 0 || cloud == 1), DF_E_ARG);
   DF_REQUIRE((H % 2) == 0 && (W % 2) == 0 && canvas.n == B && canvas.h == H && canvas.w == W && canvas.c == 32, DF_E_SHAPE);
   DF_REQUIRE((int64_t)H * W * canvas.ld < (int64_t)0x30000000, DF_E_SHAPE);   // 32-bit byte offsets inside one sample
-  DF_REQUIRE(df_aligned16(dy1) && (((uintptr_t)canvas.ptr) & 7) == 0 && (canvas.ld % 2) == 0 && (canvas.img_stride % 2) == 0 && W < 65536,
+  DF_REQUIRE(W < 65536 && H < 32768, DF_E_SHAPE);                             // the cell lists hold y << 16 | x in an int
+  DF_REQUIRE(df_aligned16(dy1) && (((uintptr_t)canvas.ptr) & 7) == 0 && (canvas.ld % 2) == 0 && (canvas.img_stride % 2) == 0,
              DF_E_ALIGN);                                                    // 16-byte dy1 rows, 8-byte canvas pairs
   SparseInWgradParams p;
   p.key_sorted = key_sorted; p.counts = counts; p.B = B; p.H = H; p.W = W; p.cloud = cloud; p.dy1 = dy1; p.canvas = canvas;

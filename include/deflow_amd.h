@@ -153,7 +153,8 @@ int df_pillar_input_grad(const uint32_t* key_sorted, const int32_t* counts, int 
 int df_sparse_wgrad3x3(const uint32_t* key_sorted, const int32_t* counts, int B, df_img x, df_img dy, float* ws,
                        float* bias_ws, int nblk, void* stream);
 /* ... with both operands as two bf16 planes (16 significant bits; three v_mfma_f32_16x16x32_bf16 per tile and 32 pixels -- the product of
- * the GRU kernels) instead of the fp32 matrix pipe; x / dy rows 16-byte aligned.  Same arguments and partial layout. */
+ * the GRU kernels) instead of the fp32 matrix pipe; x / dy rows 16-byte aligned.  Same arguments and partial layout.  Its pixel lists
+ * hold y << 16 | x: H < 32768 and W < 65536, else DF_E_SHAPE and nothing is written (df_sparse_wgrad3x3 has no such bound). */
 int df_sparse_wgrad3x3_x2(const uint32_t* key_sorted, const int32_t* counts, int B, df_img x, df_img dy, float* ws,
                           float* bias_ws, int nblk, void* stream);
 
@@ -173,7 +174,8 @@ int df_sparse_conv3x3_bf16(const uint32_t* key_sorted, const int32_t* counts, in
 
 /* Weight gradient of the first encoder conv (3x3, stride 2, pad 1, 32 -> 64; dy1 [2B,H/2,W/2,64], image = cloud*B + b)
  * summed over the occupied cells of one cloud's canvas [B,H,W,32] only.  ws [nblk*B][64][9][32] partials; finish with
- * df_conv2d_wgrad_reduce(ws, nblk*B, 64, 9, 32, ..., accumulate = cloud). */
+ * df_conv2d_wgrad_reduce(ws, nblk*B, 64, 9, 32, ..., accumulate = cloud).  The cell lists hold y << 16 | x: H < 32768 and W < 65536, else
+ * DF_E_SHAPE and nothing is written (the caller then takes the dense weight gradient: deflow_amd/autograd.py). */
 int df_sparse_in_wgrad(const uint32_t* key_sorted, const int32_t* counts, int B, int H, int W, int cloud,
                        const float* dy1, df_img canvas, float* ws, int nblk, void* stream);
 

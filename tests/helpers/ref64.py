@@ -27,9 +27,9 @@ def bf16_rne(t: torch.Tensor) -> torch.Tensor:
     return t.detach().float().to(torch.bfloat16)
 
 
-def operand(t: torch.Tensor, rnd: Optional[Callable] = None) -> torch.Tensor:
+def operand(t: torch.Tensor, rnd: Optional[Callable] = None, dtype: torch.dtype = torch.float64) -> torch.Tensor:
     t = t.detach()
-    return (t if rnd is None else rnd(t)).double()
+    return (t if rnd is None else rnd(t)).to(dtype)
 
 
 def _imgs_per_chunk(n: int, pixels: int, width: int) -> int:
@@ -69,10 +69,10 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     return y
 
 
-def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, hw, stride: int = 1, rnd=None) -> torch.Tensor:
+def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, hw, stride: int = 1, rnd=None, dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """data gradient of conv2d: dx [n,h,w,ci] for the output gradient dy [n,ho,wo,co]; hw = (h, w) of the input (stride 2 with an
     odd size: the last row / column receives no tap of the window that would start past the end)"""
-    dy, w = operand(dy, rnd), operand(w, rnd)
+    dy, w = operand(dy, rnd, dtype), operand(w, rnd, dtype)
     n, ho, wo, co = dy.shape
     _, ci, k, _ = w.shape
     h, wd = hw
@@ -87,9 +87,9 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, hw, stride: int = 1, rnd=Non
     return dxp[:, p:p + h, p:p + wd, :]
 
 
-def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, k: int, stride: int = 1, rnd=None):
+def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, k: int, stride: int = 1, rnd=None, dtype: torch.dtype = torch.float64):
     """-> (dw [co,ci,k,k], db [co]) = the weight and bias gradients of conv2d for input x and output gradient dy"""
-    x, dy = operand(x, rnd), operand(dy, rnd)
+    x, dy = operand(x, rnd, dtype), operand(dy, rnd, dtype)
     n, h, wd, ci = x.shape
     _, ho, wo, co = dy.shape
     assert _out_hw(h, wd, k, stride) == (ho, wo)
@@ -207,16 +207,18 @@ def upsample2x_bwd(dy: torch.Tensor, align_corners: bool) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------- sparse edge kernels ----
+# (dtype: the arithmetic, float64 unless a test asks for the reference's own fp32 error on the CPU -- tests/helpers/sparse_cases.py)
 def cells(keys: torch.Tensor, h: int, w: int):
     """sorted cell keys (b * h * w + row * w + col) -> (b, row, col) index tensors"""
     k = keys.long()
     return k // (h * w), (k % (h * w)) // w, k % w
 
 
-def sparse_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], keys: torch.Tensor, rnd=None) -> torch.Tensor:
+def sparse_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], keys: torch.Tensor, rnd=None,
+                   dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """df_sparse_conv3x3 / _h2 / _bf16: the 3x3 stride-1 convolution evaluated at the listed cells only -> [ncells, co] (row j = cell
     keys[j]); the dense convolution restricted to those cells"""
-    x, w = operand(x, rnd), operand(w, rnd)
+    x, w = operand(x, rnd, dtype), operand(w, rnd, dtype)
     n, h, wd, _ = x.shape
     b, r, c = cells(keys, h, wd)
     xp = _pad(x, 1)
@@ -224,13 +226,13 @@ def sparse_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor
     for ky in range(3):
         for kx in range(3):
             y += xp[b, r + ky, c + kx] @ w[:, :, ky, kx].T
-    return y if bias is None else y + bias.detach().double()
+    return y if bias is None else y + bias.detach().to(dtype)
 
 
-def sparse_wgrad3x3(x: torch.Tensor, dy: torch.Tensor, keys: torch.Tensor):
+def sparse_wgrad3x3(x: torch.Tensor, dy: torch.Tensor, keys: torch.Tensor, dtype: torch.dtype = torch.float64):
     """df_sparse_wgrad3x3 / _x2: weight and bias gradients of the 3x3 stride-1 convolution whose output gradient is non-zero at the
     listed cells only -> (dw [co,ci,3,3], db [co])"""
-    x, dy = operand(x), operand(dy)
+    x, dy = operand(x, None, dtype), operand(dy, None, dtype)
     n, h, wd, ci = x.shape
     b, r, c = cells(keys, h, wd)
     d = dy[b, r, c]                                  # [ncells, co]
@@ -242,25 +244,26 @@ def sparse_wgrad3x3(x: torch.Tensor, dy: torch.Tensor, keys: torch.Tensor):
     return dw, d.sum(0)
 
 
-def occupancy(keys: torch.Tensor, n: int, h: int, w: int) -> torch.Tensor:
+def occupancy(keys: torch.Tensor, n: int, h: int, w: int, dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """[n,h,w,1] float64 mask of the listed cells"""
-    m = torch.zeros(n * h * w, dtype=torch.float64, device=keys.device)
+    m = torch.zeros(n * h * w, dtype=dtype, device=keys.device)
     m[keys.long()] = 1.0
     return m.view(n, h, w, 1)
 
 
-def sparse_in_wgrad(x: torch.Tensor, dy: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+def sparse_in_wgrad(x: torch.Tensor, dy: torch.Tensor, keys: torch.Tensor, dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """df_sparse_in_wgrad: weight gradient of the first encoder conv (3x3 stride 2) of one cloud, summed over the occupied input
     cells only (x = that cloud's [B,H,W,32] canvas view, dy its [B,H/2,W/2,64] output gradient) -> dw [co,ci,3,3]"""
     n, h, w, _ = x.shape
-    return conv2d_wgrad(operand(x) * occupancy(keys, n, h, w), dy, 3, 2)[0]
+    return conv2d_wgrad(operand(x, None, dtype) * occupancy(keys, n, h, w, dtype), dy, 3, 2, dtype=dtype)[0]
 
 
-def pillar_input_grad(dy1: torch.Tensor, w1: torch.Tensor, dskip: torch.Tensor, w3: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+def pillar_input_grad(dy1: torch.Tensor, w1: torch.Tensor, dskip: torch.Tensor, w3: torch.Tensor, keys: torch.Tensor,
+                      dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """df_pillar_input_grad: d(canvas) of one cloud at the occupied cells = data gradient of the first encoder conv (3x3 stride 2, w1)
     + data gradient of the skip conv on the canvas (1x1, w3 [lat, 64, 1, 1], this cloud's 32 input channels) -> [ncells, 32]"""
     n, h, w, _ = dskip.shape
-    d = conv2d_dgrad(dy1, w1, (h, w), 2) + conv2d_dgrad(dskip, w3, (h, w), 1)
+    d = conv2d_dgrad(dy1, w1, (h, w), 2, dtype=dtype) + conv2d_dgrad(dskip, w3, (h, w), 1, dtype=dtype)
     b, r, c = cells(keys, h, w)
     return d[b, r, c]
 

@@ -4,7 +4,8 @@ their launches while the GRU decoder's forward kernel ran on another stream driv
 (packed-fp32) build of csrc/pillarize.hip only; the library builds that file with -fno-slp-vectorize (deflow_amd/build.py) and the cause
 below the ISA was never identified.  These tests fence that state: the shipped library must be bit-reproducible
 
-  * for the pillar feature net's backward on fixed inputs, and
+  * for the pillar feature net's backward on fixed inputs,
+  * for the sparse kernels at the UNet's ends on fixed inputs (sparse_wgrad3x3_x2_kernel emits a packed fp32 subtraction on purpose), and
   * for the whole training step (fp32 and bf16, weight gradients on the side stream),
 
 while a second host thread of this process keeps the GRU decoder's forward kernel -- the one neighbour that triggered it -- running on
@@ -111,6 +112,60 @@ def test_pfn_backward_is_bit_reproducible_beside_the_gru_forward(dev, lean):
                 worst = max(worst, float((cur - first).abs().max() / first.abs().max()))
             reps += 1
         ran = nb.count
+    assert reps >= 300 and ran >= 64, (reps, ran)
+    assert nbad == 0, f"{nbad} of {reps} repetitions differ from the first (worst rel {worst:.2e}) beside {ran} neighbour launches"
+
+
+@pytest.mark.parametrize("lean", [True, False], ids=["gru_fwd4", "gru_fwd3"])
+def test_sparse_edge_kernels_are_bit_reproducible_beside_the_gru_forward(dev, lean):
+    """df_pillar_input_grad, df_sparse_conv3x3_h2, df_sparse_wgrad3x3_x2 (whose residual split is ONE packed fp32 subtraction per pair, in a
+    file otherwise built without the SLP vectoriser), df_sparse_in_wgrad and the fp32-MFMA form df_sparse_wgrad3x3 (the engine's choice
+    outside the packed-coordinate bound and with DF_GRU_X2=0) on the FIXED inputs of the `wrap` case of
+    tests/helpers/sparse_cases.py, beside the neighbour: every repetition bit-equal to the first"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    import sparse_cases as SC
+    from deflow_amd._lib import call, img, ptr, stream
+    c = SC.case("wrap")
+    B, H, W, nblk = c.B, c.H, c.W, c.nblk
+    t = {k: v.to(dev) for k, v in c.t.items()}
+    keys, counts = c.keys.to(dev), c.counts.to(dev)
+    w = t["w"].permute(0, 2, 3, 1).contiguous()
+    w1 = t["w1"].permute(0, 2, 3, 1).contiguous()
+    w3 = t["w3"].reshape(64, 64).contiguous()
+    xa, wa = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
+    call("df_absmax", img(t["x"]), ptr(xa), stream())
+    call("df_absmax", img(w.reshape(1, 1, -1, 64)), ptr(wa), stream())
+    w2 = torch.empty(2 * w.numel(), dtype=torch.float16, device=dev)
+    call("df_split_h2", ptr(w), ptr(wa), ptr(w2), w.numel(), stream())
+    dc = torch.zeros(B, H, W, 64, device=dev)
+    y = torch.zeros(B, H, W, 64, device=dev)
+    ws = torch.zeros(nblk * B, 64 * 9 * 64, device=dev)
+    bws = torch.zeros(nblk * B, 64, device=dev)
+    ws1 = torch.zeros(nblk * B, 64 * 9 * 32, device=dev)
+    ws0, bws0 = torch.zeros_like(ws), torch.zeros_like(bws)
+    torch.cuda.synchronize()
+    first, nbad, worst = None, 0, 0.0
+    with GruNeighbour(dev, lean) as nb:
+        t0 = time.time()
+        reps = 0
+        while reps < 1500 and time.time() - t0 < 12:
+            for g in (0, 1):
+                call("df_pillar_input_grad", ptr(keys), ptr(counts), B, H, W, g, ptr(t["dy1"]), ptr(w1), img(t["dskip"]), ptr(w3),
+                     img(dc, 32, 32 * g), 0, nblk, stream())
+            call("df_sparse_conv3x3_h2", ptr(keys), ptr(counts), B, img(t["x"]), ptr(w2), ptr(xa), ptr(wa), ptr(t["bias"]), img(y), nblk, stream())
+            call("df_sparse_wgrad3x3_x2", ptr(keys), ptr(counts), B, img(t["x"]), img(t["dy"]), ptr(ws), ptr(bws), nblk, stream())
+            call("df_sparse_wgrad3x3", ptr(keys), ptr(counts), B, img(t["x"]), img(t["dy"]), ptr(ws0), ptr(bws0), nblk, stream())
+            call("df_sparse_in_wgrad", ptr(keys), ptr(counts), B, H, W, 1, ptr(t["dy1"]), img(t["canvas"], 32, 32), ptr(ws1), nblk, stream())
+            cur = torch.cat([v.reshape(-1) for v in (dc, y, ws, bws, ws1, ws0, bws0)])
+            torch.cuda.synchronize()
+            if first is None:
+                first = cur
+            elif not torch.equal(cur, first):
+                nbad += 1
+                worst = max(worst, float((cur - first).abs().max() / first.abs().max()))
+            reps += 1
+        ran = nb.count
+    print(f"[soak] sparse edge kernels: {reps} repetitions, {nbad} differ, beside {ran} neighbour launches")
     assert reps >= 300 and ran >= 64, (reps, ran)
     assert nbad == 0, f"{nbad} of {reps} repetitions differ from the first (worst rel {worst:.2e}) beside {ran} neighbour launches"
 
