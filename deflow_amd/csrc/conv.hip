@@ -129,14 +129,25 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvParams p) {
   int rslot[BK / 8];                              // swizzled slots of this lane's fragments
 #pragma unroll
   for (int g = 0; g < BK / 8; ++g) rslot[g] = ((2 * g + kh) ^ ((li >> 1) & 7)) * 4;
+  // bf16-operand mode (p.bf16): both operands are rounded to bf16 (RNE) on their way into LDS and multiplied on the fp32 MFMA -- the
+  // product of two bf16 values is exact in fp32, so this is the convolution of the rounded operands with fp32 accumulation, the result
+  // class of conv_dma_kernel<.., BF>.  (Until the generic stride-2 data gradient was checked against the rounded operands this kernel
+  // ignored the mode: a bf16-mode step on a grid with an odd stride-2 size mixed fp32 and bf16 products.)
+  const bool bf = p.bf16 != 0;
+  auto rne = [](f32x4 v) {
+    f32x4 r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = (float)(__bf16)v[k];
+    return r;
+  };
   auto store_stage = [&](int buf) {
     float* a = As + buf * BM * LDT;
     float* b = Bs + buf * BN * LDT;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < RA; ++i) st4(a + (r0 + 32 * i) * LDT + wslot, ((amask >> i) & 1) ? areg[i] : zero);
+    for (int i = 0; i < RA; ++i) st4(a + (r0 + 32 * i) * LDT + wslot, ((amask >> i) & 1) ? (bf ? rne(areg[i]) : areg[i]) : zero);
 #pragma unroll
-    for (int i = 0; i < RB; ++i) st4(b + (r0 + 32 * i) * LDT + wslot, breg[i]);
+    for (int i = 0; i < RB; ++i) st4(b + (r0 + 32 * i) * LDT + wslot, bf ? rne(breg[i]) : breg[i]);
   };
 
   f32x16 acc[TM][TN];
@@ -504,7 +515,7 @@ int launch_conv(const ConvParams& p, hipStream_t s) {
   const size_t lds_bytes = (size_t)2 * (BM + BN) * LDT * sizeof(float);
   DF_SET_LDS_ONCE((conv_kernel<BM, BN, WM, WN>), (int)lds_bytes);
   DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN>), (int)lds_bytes);
-  if (p.x_bytes && p.bf16) {   // (the register-staged fallback for > 4 GB tensors stays fp32)
+  if (p.x_bytes && p.bf16) {   // (the register-staged fallback rounds its operands itself: conv_kernel's store_stage)
     DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN, true>), (int)lds_bytes);
     hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN, true>), dim3(p.tiles_m * p.tiles_n), dim3(256), lds_bytes, s, p);
   } else if (p.x_bytes)

@@ -2415,6 +2415,7 @@ static int wgrad_x3_impl(df_img x, df_img dy, const float* x_amax, const float* 
   DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
   p.total_chunks = (int)chunks;
   p.chunks_per_split = (int)((chunks + splits - 1) / splits);
+  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
   dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
   static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
   p.xcd_map = xcd_map;
@@ -2467,6 +2468,7 @@ extern "C" int df_conv2d_wgrad1_h2(df_img x, df_img dy, const float* x_amax, con
   DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
   p.total_chunks = (int)chunks;
   p.chunks_per_split = (int)((chunks + splits - 1) / splits);
+  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
   const int cot = wgrad1_cot(dy.c), cit = wgrad1_cit(x.c);
   dim3 grid((x.c + cit - 1) / cit, dy.c / cot, splits);
   static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
@@ -2526,6 +2528,7 @@ extern "C" int df_conv2d_wgrad_s2_h2(df_img x, df_img dy, const float* x_amax, c
   DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
   p.total_chunks = (int)chunks;
   p.chunks_per_split = (int)((chunks + splits - 1) / splits);
+  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
   dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
   static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
   p.xcd_map = xcd_map;
@@ -2576,6 +2579,7 @@ extern "C" int df_conv2d_wgrad_h2p(df_img x, df_img dy, const float* x_bound, co
   DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
   p.total_chunks = (int)chunks;
   p.chunks_per_split = (int)((chunks + splits - 1) / splits);
+  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
   dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
   static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
   p.xcd_map = xcd_map;
@@ -2612,6 +2616,7 @@ extern "C" int df_conv2d_wgrad_bf16(df_img x, df_img dy, int ksize, int stride, 
   DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
   p.total_chunks = (int)chunks;
   p.chunks_per_split = (int)((chunks + splits - 1) / splits);
+  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
   dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
   static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
   p.xcd_map = xcd_map;

@@ -197,7 +197,9 @@ int df_conv2d(df_img x, const float* w, const float* bias, df_img y, int ksize, 
               int accumulate, void* stream);
 /* Mixed-precision form (training with BASELINE configs[4]'s "bf16 MFMA"): mfma_bf16 != 0 rounds both MFMA operands to bf16
  * as they leave LDS (v_cvt_pk_bf16_f32, round to nearest even) and multiplies on v_mfma_f32_32x32x16_bf16 with fp32
- * accumulation; every tensor stays fp32 in memory, epilogues unchanged.  mfma_bf16 == 0 is df_conv2d. */
+ * accumulation; every tensor stays fp32 in memory, epilogues unchanged.  mfma_bf16 == 0 is df_conv2d.  (The register-staged kernel --
+ * the generic stride-2 data gradient, tensors beyond 32-bit offsets -- rounds the operands on their way INTO LDS and multiplies them
+ * on the fp32 MFMA: the same exact products, fp32 accumulation.) */
 int df_conv2d_mp(df_img x, const float* w, const float* bias, df_img y, int ksize, int stride, int pad,
                  int mode, int epi, const float* scale, const float* shift, float* stats_partial,
                  int accumulate, int mfma_bf16, void* stream);

@@ -51,9 +51,10 @@ def _pad(x: torch.Tensor, p: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------- convolutions ----
-def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1, rnd=None) -> torch.Tensor:
+def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1, rnd=None,
+           dtype: torch.dtype = torch.float64) -> torch.Tensor:
     """y = conv(x; w) + bias, padding k // 2 (the UNet's 1x1 and 3x3 layers, stride 1 or 2).  x [n,h,w,ci] -> [n,ho,wo,co]"""
-    x, w = operand(x, rnd), operand(w, rnd)
+    x, w = operand(x, rnd, dtype), operand(w, rnd, dtype)
     n, h, wd, ci = x.shape
     co, _, k, _ = w.shape
     ho, wo = _out_hw(h, wd, k, stride)
@@ -65,7 +66,7 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
             for kx in range(k):
                 y[i:i + step] += _tap(xp[i:i + step], ky, kx, ho, wo, stride) @ w[:, :, ky, kx].T
     if bias is not None:
-        y += bias.detach().double()
+        y += bias.detach().to(dtype)
     return y
 
 

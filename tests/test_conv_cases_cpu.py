@@ -1,0 +1,356 @@
+"""CPU: the conditions that make tests/test_gpu_conv_cases.py meaningful, decided without a GPU (the library's host-side queries launch
+nothing).
+
+  * tile selection: df_conv2d_variant / df_conv2d_tile_m give every problem of tests/helpers/conv_cases.py the tile its case was built for,
+    with the stated tile count and last-tile size; the class-mode condition of conv2d_impl, restated, holds for `s2_class` only;
+  * form queries: df_conv2d_x3_ok / df_conv2d_w16_ok say 1 for the halo_* cases and 0 for tail*; the weight-gradient _ok functions answer as
+    the forms table says; the *_splits functions return the recorded counts;
+  * chunks and splits: the restated wg_chunk / chunks_per_split / c_begin / c_end show which split starts mid-row, which crosses an image,
+    which has fewer chunks than the ring is deep and which is empty;
+  * the restatements (rows -> tiles; chunks -> splits -> reduce) equal ref64 with no fault, and every fault injected into them (never into
+    a kernel) lands at least ten times over the bound the GPU test applies, in the case built for it;
+  * the float32 evaluation of every reference meets every bound of the GPU test: a correct fp32 computation can pass.
+"""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import conv_cases as CC  # noqa: E402
+import ref64 as R  # noqa: E402
+
+ALL = [p for ps in CC.PROBS.values() for p in ps]
+WALL = [p for ps in CC.WPROBS.values() for p in ps]
+
+
+def _by(case, **kw):
+    out = [p for p in CC.PROBS[case] if all(getattr(p, k) == v for k, v in kw.items())]
+    assert out, (case, kw)
+    return out
+
+
+def _close(a, b, tag):
+    e = float((a - b).abs().max() / b.abs().max().clamp_min(1e-300))
+    assert e <= 1e-12, (tag, e)
+
+
+def _desc(shape, lay, elt=0):
+    """a descriptor of that geometry on an aligned address nobody dereferences"""
+    from deflow_amd._lib import DfImg
+    probe = torch.empty(64, dtype=torch.float32)
+    base = (probe.data_ptr() + 127) // 128 * 128
+    n, h, w, c = shape
+    return DfImg(base + 4 * (lay.lead + lay.off), n, h, w, c, lay.ld, lay.grp_size, lay.img_stride, lay.grp_off, elt, 0)
+
+
+def _descs(p):
+    return (_desc(p.in_shape, CC.layout(p.in_shape, p.grp, p.views, "x")), _desc(p.out_shape, CC.layout(p.out_shape, p.grp, p.views, "y")))
+
+
+def _wdescs(p):
+    xs, ds = (p.n, p.h, p.w, p.cin), (p.n, p.ho, p.wo, p.cout)
+    return _desc(xs, CC.layout(xs, p.grp, p.views, "x")), _desc(ds, CC.layout(ds, p.grp, p.views, "y"))
+
+
+# ---- tile selection -------------------------------------------------------------------------------------------------------------
+# per case, per problem in table order: (variant, class mode, row tiles, rows of the last tile)
+TILES = {
+    "tail64": [(64064, False, 3, 7)] * 8,
+    "tail128": [(128064, False, 34, 1)] * 4 + [(128128, False, 34, 1)] * 2 + [(128064, False, 34, 1)] * 2,     # (64->128 data gradient writes 64 channels)
+    "n32": [(128032, False, 2, 26)] * 6,
+    "s2_odd": [(64064, False, 2, 6)] * 2 + [(128032, False, 2, 106)] * 2,           # forward 70 rows; dx [2,9,13,32]: 234 rows of 32 channels
+    "s2_even_ragged": [(64064, False, 1, 35)] + [(128032, False, 2, 12)] * 2,       # dx [1,10,14,32]: 140 rows
+    "s2_class": [(64064, True, 8, 64)] * 2 + [(64064, True, 4, 64)] * 2,
+    "thin": [(64064, False, 1, 1)] * 2 + [(64064, False, 2, 16)] * 4,
+    "halo_thin": [(128064, False, 2, 128)] * 2 + [(128064, False, 6, 128)] + [(128128, False, 2, 128)] * 2 + [(128128, False, 6, 128)],
+    "halo_odd": [(128064, False, 33, 128)] * 3 + [(128128, False, 33, 128)] * 3,
+    "views": [(64064, False, 3, 52)] * 4 + [(64064, False, 3, 12)] * 2 + [(128032, False, 4, 84)] * 2,
+}
+
+
+@pytest.mark.parametrize("case", CC.NAMES)
+def test_tile_selection(case):
+    assert len(TILES[case]) == len(CC.PROBS[case])
+    for p, (var, cls, ntiles, last) in zip(CC.PROBS[case], TILES[case]):
+        tl = CC.tiling(p)
+        m0, m1 = tl["tiles"][-1][1:]
+        assert (tl["var"], tl["cls"], len(tl["tiles"]), min(m1, tl["m_end"]) - m0) == (var, cls, ntiles, last), (p.pid, tl["var"], tl["cls"], len(tl["tiles"]))
+        assert tl["bm"] == var // 1000 and p.out_shape[3] % tl["bn"] == 0
+        if p.epi == "stats":
+            from deflow_amd._lib import call
+            rpg = (p.grp or p.n) * p.ho * p.wo
+            assert call("df_conv2d_tile_m", rpg, p.cout) == 128 and rpg % 128 == 0
+    assert CC.CASES[case]["why"]
+
+
+def test_class_mode_condition():
+    for p in ALL:
+        if p.mode != "dgrad" or p.stride != 2:
+            assert not CC.class_mode_asked(p)
+    for p in CC.PROBS["s2_class"]:
+        assert CC.class_mode_asked(p) and CC.tiling(p)["cls"]
+        assert len(CC.tiling(p)["tiles"]) // 4 == (2 if p.n == 2 else 1)            # tiles per parity class
+    for p in _by("s2_odd", mode="dgrad") + _by("views", mode="dgrad", stride=2):
+        assert not CC.class_mode_asked(p)                                           # odd dx
+    for p in _by("s2_even_ragged", mode="dgrad"):
+        tl = CC.tiling(p)
+        assert CC.class_mode_asked(p) and not tl["cls"] and (p.M // 4) == 35 and 35 % tl["bm"] != 0
+
+
+def test_cases_are_what_they_claim():
+    assert CC.PROBS["tail64"][0].M == 135 == 2 * 64 + 7 and CC.PROBS["tail64"][0].h * CC.PROBS["tail64"][0].w == 45
+    assert CC.PROBS["tail128"][0].M == 4225 > 4096 and 4225 == 33 * 128 + 1
+    assert CC.PROBS["n32"][0].M == 154 == 128 + 26
+    assert CC.PROBS["halo_odd"][0].M == 4224 == 33 * 128
+    p = CC.PROBS["s2_odd"][0]
+    assert (p.ho, p.wo) == (5, 7) and (p.ho - 1) * 2 == p.h - 1 and (p.wo - 1) * 2 == p.w - 1      # the last window starts on the last row / column
+    p = CC.PROBS["s2_even_ragged"][0]
+    assert (p.ho, p.wo) == (5, 7) and p.h % 2 == 0 and p.w % 2 == 0
+    assert {(p.n, p.h, p.w) for p in CC.PROBS["thin"]} == {(1, 1, 1), (2, 1, 40), (2, 40, 1)}
+    for p in CC.PROBS["halo_thin"]:
+        assert p.epi == "stats" and ((p.grp == 1 and p.n == 2) or p.n == 1)
+    assert CC.stats_layout(_by("halo_thin", cout=64, w=256)[0], "x3") == (256, 2) and CC.stats_layout(_by("halo_thin", cout=64, w=256)[0], "mp") == (128, 1)
+    assert CC.stats_layout(_by("halo_thin", cout=128, w=256)[0], "h2") == (128, 1)
+    for p in ALL:
+        for v in CC.tensors(p).values():
+            assert v is None or (v.dtype == torch.float32 and bool(torch.isfinite(v).all()))
+        assert set(CC.forms(p.case)) <= set(CC.F_TAIL + CC.F_HALO)
+    assert all("yh2" in CC.forms(c) and "ybf16" in CC.forms(c) for c in ("tail64", "tail128"))
+    assert all("yh2" not in CC.forms(c) for c in CC.NAMES if not c.startswith("tail"))
+
+
+def test_layouts():
+    for p in ALL + WALL:
+        shapes = (p.in_shape, p.out_shape) if isinstance(p, CC.Prob) else ((p.n, p.h, p.w, p.cin), (p.n, p.ho, p.wo, p.cout))
+        for shape, side in zip(shapes, "xy"):
+            lay = CC.layout(shape, p.grp, p.views, side)
+            idx = CC.index(lay, shape)
+            assert idx.unique().numel() == idx.numel() and int(idx.min()) == lay.lead + lay.off
+            assert lay.lead >= CC.GUARD_ROWS * lay.ld and lay.total - int(idx.max()) - 1 >= CC.GUARD_ROWS * lay.ld - lay.ld
+            assert all(v % 4 == 0 for v in (lay.ld, lay.off, lay.img_stride, lay.grp_off, lay.lead))
+            if p.views:
+                assert p.n == 4 and lay.grp_size == 2 and lay.grp_off != 2 * lay.img_stride and lay.off > 0 and lay.off + shape[3] < lay.ld
+            if p.case.startswith("tail"):
+                assert lay.ld % 32 == 0 and lay.img_stride % 32 == 0 and (4 * lay.lead) % 128 == 0      # what a pre-split output asks for
+
+
+# ---- form queries ---------------------------------------------------------------------------------------------------------------
+def test_forward_form_queries():
+    from deflow_amd._lib import call
+    for p in ALL:
+        x, y = _descs(p)
+        mode = CC.FWD if p.mode == "fwd" else CC.DGRAD
+        ok = (call("df_conv2d_x3_ok", x, y, p.k, p.stride, mode, CC.EPI[p.epi]), call("df_conv2d_w16_ok", x, y, p.k, p.stride, mode, CC.EPI[p.epi]))
+        if p.case.startswith("halo"):
+            assert ok == (1, 1), (p.pid, ok)
+        if p.case.startswith("tail"):
+            assert ok == (0, 0), (p.pid, ok)
+        assert ("x3" in CC.forms(p.case)) <= (ok == (1, 1)), p.pid
+    assert CC.refused(_by("tail64", acc=True)[0], "yh2") == CC.E_ARG and CC.refused(_by("tail64", acc=False)[0], "yh2") is None
+
+
+# the library's own split counts (wgrad, wgrad1_h2, wgrad_s2_h2) per weight-gradient problem, in table order
+OWN_SPLITS = {"w_ragged": [15], "w_two_seg": [60], "w_x3": [12, 12], "w_s2_odd": [30], "w_k96": [4], "w_1x1": [14, 14, 14], "w_rows": [8], "w_views": [20, 60]}
+
+
+def test_weight_gradient_form_queries_and_splits():
+    from deflow_amd._lib import call
+    for case in CC.WNAMES:
+        for p, own in zip(CC.WPROBS[case], OWN_SPLITS[case]):
+            x, dy = _wdescs(p)
+            assert call("df_conv2d_wgrad_splits", x, dy, p.k, p.stride) == own == len(CC.wchunks(p)[2]), p.pid
+            x3 = call("df_conv2d_wgrad_x3_ok", x, dy, p.k, p.stride)
+            assert x3 == int(p.k == 3 and p.stride == 1 and p.wo % 32 == 0), p.pid
+            assert ("x3" in CC.wforms(case, p)) == ("h2" in CC.wforms(case, p)) == ("bf16" in CC.wforms(case, p)) == bool(x3), p.pid
+            if p.k == 1:
+                assert call("df_conv2d_wgrad1_h2_ok", x, dy) == 1 and call("df_conv2d_wgrad1_h2_splits", x, dy) == own
+                assert ("w1h2" in CC.wforms(case, p)) == (p.row_counts is None)           # (row lists: df_conv2d_wgrad_mp only)
+            if p.stride == 2:
+                assert call("df_conv2d_wgrad_s2_h2_ok", x, dy) == 1 and call("df_conv2d_wgrad_s2_h2_splits", x, dy) == own
+                assert "s2h2" in CC.wforms(case, p) and "s2bf16" in CC.wforms(case, p)
+            for form in CC.wforms(case, p):
+                assert own in CC.wsplits(p, form, x, dy)
+
+
+# ---- chunks and splits ----------------------------------------------------------------------------------------------------------
+def _split_facts(p, splits):
+    P, cpr, chunks = CC.wchunks(p)
+    rng = CC.split_ranges(len(chunks), splits)
+    return dict(mid_row=[s for s, (lo, hi) in enumerate(rng) if lo < hi and chunks[lo][2] != 0],
+                mid_image=[s for s, (lo, hi) in enumerate(rng) if lo < hi and (chunks[lo][1] != 0 or chunks[lo][2] != 0)],
+                crosses=[s for s, (lo, hi) in enumerate(rng) if lo < hi and chunks[lo][0] != chunks[hi - 1][0]],
+                sizes=[max(hi - lo, 0) for lo, hi in rng], empty=[s for s, (lo, hi) in enumerate(rng) if lo >= hi])
+
+
+def test_chunk_walk():
+    p = CC.WPROBS["w_ragged"][0]
+    assert CC.wchunks(p)[:2] == (32, 1) and len(CC.wchunks(p)[2]) == 15 and p.wo == 9
+    f = _split_facts(p, 2)
+    assert f["sizes"] == [8, 7] and f["crosses"] == [0, 1] and f["mid_image"] == [1]       # split 1 starts at image 1, row 3
+    assert _split_facts(p, 9)["empty"] == [8] and _split_facts(p, 9)["sizes"][7] == 1 and _split_facts(p, 15)["sizes"] == [1] * 15
+    p = CC.WPROBS["w_two_seg"][0]
+    assert CC.wchunks(p)[:2] == (32, 2) and len(CC.wchunks(p)[2]) == 60 and p.wo % 32 == 8
+    assert _split_facts(p, 9)["mid_row"] == [1, 3, 5, 7] and _split_facts(p, 7)["mid_row"] == [1, 3, 5]
+    assert _split_facts(p, 7)["crosses"] == [3] and _split_facts(p, 16)["empty"] == [15] and _split_facts(p, 60)["empty"] == []
+    for p in CC.WPROBS["w_x3"]:
+        assert CC.wchunks(p)[:2] == (32, 2) and len(CC.wchunks(p)[2]) == 12
+        assert max(_split_facts(p, 12)["sizes"]) == 1 < 2 and _split_facts(p, 8)["empty"] == [6, 7]      # fewer stages than the shallowest ring (2)
+    p = CC.WPROBS["w_s2_odd"][0]
+    assert CC.wchunks(p)[:2] == (16, 3) and p.wo == 34 == 16 + 16 + 2 and len(CC.wchunks(p)[2]) == 30
+    assert (p.wo - 1) * 2 + 1 == p.w and 32 * 2 + 33 - 1 > p.w and p.cin == 32                # the last chunk's 33-pixel patch passes the right border
+    assert _split_facts(p, 7)["empty"] == [6] and _split_facts(p, 4)["mid_row"] == [1, 2]
+    p = CC.WPROBS["w_k96"][0]
+    assert (p.cin + 63) // 64 == 2 and p.cin % 64 == 32 and p.cout // 64 == 3 and _split_facts(p, 3)["empty"] == [2]
+    for p in CC.WPROBS["w_1x1"]:
+        assert CC.wchunks(p)[:2] == (32, 1) and p.wo == 11 and _split_facts(p, 8)["empty"] == [7]
+    assert [(p.cin, p.cout) for p in CC.WPROBS["w_1x1"]] == [(64, 64), (128, 128), (96, 128)]
+    p = CC.WPROBS["w_rows"][0]
+    ok = CC.row_ok(p).view(6, 40)
+    assert ok.sum(1).tolist() == [0, 1, 31, 32, 33, 40] and bool(ok[2, :31].all()) and not bool(ok[2, 31:].any())
+    valid = CC.row_ok(p).view(-1)
+    assert bool(valid[2 * 40 + 30]) and not bool(valid[2 * 40 + 31]) and bool(valid[3 * 40 + 31]) and bool(valid[4 * 40 + 32])
+    assert _split_facts(p, 5)["empty"] == [4]
+    # segment 2 (pixels 80 .. 119) ends its valid run at pixel 110; chunk 3 = pixels 96 .. 127 holds the boundary; segment 3 ends on pixel
+    # 151, the last valid pixel before chunk boundary 160 is 8 pixels short: both sides of a chunk boundary see valid and invalid pixels
+    assert not bool(valid[96:128].all()) and bool(valid[96:111].all()) and bool(valid[120:152].all()) and not bool(valid[152:160].any())
+
+
+# ---- the restatements ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CC.NAMES)
+def test_row_walk_equals_ref64(case):
+    for p in CC.PROBS[case]:
+        _close(CC.restate(p), CC.reference(p)["plain"][1], p.pid)
+
+
+def test_chain_reference_is_the_reference():
+    p = CC.PROBS["tail64"][1]
+    e = R.errors(CC.chain32(p), CC.reference(p)["plain"][1])
+    assert e["finite"] and e["max"] <= 2e-6, e
+
+
+@pytest.mark.parametrize("case", CC.WNAMES)
+def test_chunk_walk_equals_ref64(case):
+    for p in CC.WPROBS[case]:
+        dw64, db64 = CC.wreference(p)["plain"][1]
+        for s in p.splits:
+            ws, bws = CC.partials64(p, s or len(CC.wchunks(p)[2]))
+            assert bool(torch.isfinite(ws).all()) and bool(torch.isfinite(bws).all())
+            _close(CC.reduce64(ws), dw64, p.pid)
+            _close(bws.sum(0), db64, p.pid)
+
+
+# ---- the faults -----------------------------------------------------------------------------------------------------------------
+def _over(p, got):
+    r32, r64 = CC.reference(p)["plain"]
+    return CC.excess(R.errors(got, r64), CC.bounds(CC.CONV32, r32, r64, -1))
+
+
+def _wover(p, got):
+    (dw32, _), (dw64, _) = CC.wreference(p)["plain"]
+    return CC.excess(R.errors(got, dw64, 0), CC.bounds(CC.CONV32, dw32, dw64, 0))
+
+
+@pytest.mark.parametrize("case", ["tail64", "tail128", "n32", "s2_odd", "views"])
+def test_fault_ragged_tile_dropped_or_doubled(case):
+    for p in CC.PROBS[case]:
+        assert _over(p, CC.restate(p)) <= 1e-3
+        assert _over(p, CC.restate(p, "drop_ragged")) >= 10, p.pid
+        if p.acc:
+            assert _over(p, CC.restate(p, "dup_ragged")) >= 10, p.pid
+
+
+@pytest.mark.parametrize("case", ["tail64", "s2_odd", "thin", "views"])
+def test_fault_rows_decoded_with_h_and_w_swapped(case):
+    for p in CC.PROBS[case]:
+        if p.out_shape[1] != p.out_shape[2]:
+            assert _over(p, CC.restate(p, "swap_hw")) >= 10, p.pid
+
+
+@pytest.mark.parametrize("case", ["tail64", "tail128", "thin", "halo_odd", "s2_odd"])
+def test_fault_tap_wraps_into_the_neighbouring_row(case):
+    for p in CC.PROBS[case]:
+        # (one-row images have no neighbouring row; the taps of a stride-2 data gradient onto an odd image never leave dy: the parity
+        # test takes out exactly those that would)
+        if p.in_shape[1] > 1 and p.k == 3 and not (p.mode == "dgrad" and p.stride == 2):
+            assert _over(p, CC.restate(p, "tap_wrap")) >= 10, p.pid
+
+
+@pytest.mark.parametrize("case", ["tail64", "thin", "s2_class", "views"])
+def test_fault_tile_reads_across_an_image_boundary(case):
+    for p in CC.PROBS[case]:
+        if p.n > 1 and p.k == 3 and not (p.mode == "dgrad" and p.stride == 2 and p.h % 2 == 1):
+            assert _over(p, CC.restate(p, "cross_image")) >= 10, p.pid
+
+
+def test_fault_last_chunk_of_a_row_skipped():
+    for p in CC.WPROBS["w_two_seg"] + CC.WPROBS["w_s2_odd"]:
+        assert _wover(p, CC.reduce64(CC.partials64(p, 7)[0])) <= 1e-3
+        assert _wover(p, CC.reduce64(CC.partials64(p, 7, "skip_last_chunk")[0])) >= 10, p.pid
+
+
+def test_fault_invalid_pixels_of_a_ragged_chunk_counted():
+    for p in CC.WPROBS["w_ragged"] + CC.WPROBS["w_1x1"][:1]:
+        assert _wover(p, CC.reduce64(CC.partials64(p, 2, "count_invalid")[0])) >= 10, p.pid
+
+
+def test_fault_one_split_lost():
+    for case in ("w_two_seg", "w_x3", "w_k96"):
+        for p in CC.WPROBS[case]:
+            assert _wover(p, CC.reduce64(CC.partials64(p, 4)[0], "lose_split")) >= 10, p.pid
+
+
+def test_fault_row_counts_ignored():
+    p = CC.WPROBS["w_rows"][0]
+    assert _wover(p, CC.reduce64(CC.partials64(p, 3, "ignore_row_counts")[0])) >= 10
+
+
+# ---- the fp32 references stay inside the bounds -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CC.NAMES)
+def test_fp32_reference_meets_the_bounds(case):
+    for p in CC.PROBS[case]:
+        for key in ("plain", "bf16"):
+            r32, r64 = CC.reference(p)[key]
+            e = R.errors(r32, r64)
+            print(f"[conv cases] {p.pid} {key}: ref64 in fp32 vs float64 max {e['max']:.2e} rms {e['rms']:.2e} ch {e['ch']:.2e}")
+            assert r32.dtype == torch.float32 and CC.bounds(CC.CONV32, r32, r64, -1).ok(e) and e["max"] <= CC.CONV32.max, (p.pid, e)
+        r32, r64 = CC.reference(p)["plain"]
+        if "ybf16" in CC.forms(case):
+            assert R.bf16_excess(r32.bfloat16().float(), r64, CC.BF16_FLOOR) <= 1.0
+        if p.epi == "stats":
+            for form in ("mp", "x3"):
+                a, b = CC.stats64(p, r32.double(), form), CC.stats64(p, r64, form)
+                assert float((a - b).abs().max(0)[0].max() / b.abs().max()) <= CC.STATS_TOL
+
+
+@pytest.mark.parametrize("case", CC.WNAMES)
+def test_fp32_weight_gradient_reference_meets_the_bounds(case):
+    for p in CC.WPROBS[case]:
+        for key in ("plain", "bf16"):
+            (dw32, db32), (dw64, db64) = CC.wreference(p)[key]
+            e, eb = R.errors(dw32, dw64, 0), R.errors(db32, db64)
+            print(f"[conv cases] {p.pid} {key}: ref64 in fp32 vs float64 dw max {e['max']:.2e} rms {e['rms']:.2e} ch {e['ch']:.2e} | db max {eb['max']:.2e}")
+            assert CC.bounds(CC.CONV32, dw32, dw64, 0).ok(e) and e["max"] <= CC.CONV32.max and CC.bounds(CC.BIAS32, db32, db64, -1).ok(eb), (p.pid, e, eb)
+
+
+def test_reduce_shapes():
+    """64 x 9 x 36 = 81 blocks of 256 exactly; 65 output channels leave the last block of the weight part 68 threads and the bias part a
+    third block with one column"""
+    assert CC.REDUCE_COUTS == (64, 65) and CC.REDUCE_SHAPE["taps"] * CC.REDUCE_SHAPE["cin"] == 324 and CC.REDUCE_SHAPE["pad"] == 20
+    assert (64 * 324) % 256 == 0 and (65 * 324) % 256 == 68 and 65 % 32 == 1
+
+
+@pytest.mark.parametrize("cout", CC.REDUCE_COUTS)
+@pytest.mark.parametrize("splits", CC.REDUCE_SPLITS)
+def test_reduce_case(splits, cout):
+    ws, bws, old = CC.reduce_case(splits, cout)
+    assert ws.shape == (splits, cout, 324) and bws.shape == (splits, cout) and old.shape == (cout, 324)
+    r32, r64 = CC.reduce_refs(ws, old)
+    e = R.errors(r32, r64, 0)
+    assert e["finite"] and e["max"] <= 1e-6
+    b = bws.double().sum(0)
+    assert bool(((bws.double().sum(0).float().double() - b).abs() <= CC.ulp32(b)).all())       # the rounded float64 sum is within one ulp
+    # the loops' remainders: the 4-way body with 0 .. 3 left over; the bias part's 32-stride body (k + 24 < splits) and its stride-8 tail
+    assert {s % 4 for s in CC.REDUCE_SPLITS} == {0, 1, 2, 3} and any(s > 24 for s in CC.REDUCE_SPLITS) and any(s <= 24 for s in CC.REDUCE_SPLITS)
+    assert any(s > 32 and s % 8 for s in CC.REDUCE_SPLITS)

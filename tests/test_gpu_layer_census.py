@@ -64,8 +64,11 @@ ALLOW = {
     # the cases built for the row tiles and split-K walks (tests/helpers/decoder_cases.py), lean / lean_fp32 / full forms
     **{k: "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64" for k in (
         "df_gru_decoder_fwd_mp", "df_gru_decoder_bwd_mp", "df_gru_wgrad_mp", "df_gru_xtab", "df_gru_lean_fwd", "df_gru_lean_bwd",
-        "df_gru_lean_wgrad", "df_gru_lean_head_wgrad", "df_gru_lean_finalize", "df_gru_head_wgrad", "df_split_bf16x2_rows",
-        "df_conv2d_wgrad_reduce")},
+        "df_gru_lean_wgrad", "df_gru_lean_head_wgrad", "df_gru_lean_finalize", "df_gru_head_wgrad", "df_split_bf16x2_rows")},
+    # the split-K reduction: behind the decoder's weight gradients, and on a workspace of known content (every loop remainder, ld_co wider
+    # than a row, accumulate)
+    "df_conv2d_wgrad_reduce": "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64, "
+                              "test_gpu_conv_cases.py::test_conv_wgrad_reduce_alone",
     # the column sum that ends the decoder's bias sums and the feature net's dW (the latter also with accumulate = 1)
     "df_colsum_finalize": "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64, "
                           "test_gpu_pfn_cases.py::test_pfn_case_vs_float64",

@@ -33,7 +33,10 @@ def _gen(seed):
 
 
 # cin, cout, k, stride, n, h, w: 1x1 and 3x3, stride 1 and 2, odd and even extents
-CONV = [(5, 7, 3, 1, 2, 9, 11), (6, 4, 3, 2, 3, 9, 7), (6, 4, 3, 2, 1, 10, 8), (8, 3, 1, 1, 2, 5, 7), (3, 5, 1, 2, 2, 7, 5)]
+# (the last two: the stride-2 geometries of tests/helpers/conv_cases.py -- the last window starts on the last row and column of a 9 x 13
+# image; 9 x 67 -> 5 x 34)
+CONV = [(5, 7, 3, 1, 2, 9, 11), (6, 4, 3, 2, 3, 9, 7), (6, 4, 3, 2, 1, 10, 8), (8, 3, 1, 1, 2, 5, 7), (3, 5, 1, 2, 2, 7, 5),
+        (4, 6, 3, 2, 2, 9, 13), (3, 4, 3, 2, 2, 9, 67)]
 
 
 @pytest.mark.parametrize("ci,co,k,s,n,h,w", CONV)
@@ -51,6 +54,20 @@ def test_conv_forward_and_gradients_vs_autograd(ci, co, k, s, n, h, w):
     dw, db = R.conv2d_wgrad(x, nhwc(dy), k, s)
     close(dw, wt.grad)
     close(db, b.grad)
+
+
+def test_conv_dtype_argument():
+    """dtype = float32: the same functions evaluated in float32 (the yardstick of the case tables' bounds), operands and bias included"""
+    g = _gen(9)
+    x, wt, b = torch.randn(2, 9, 13, 8, generator=g), torch.randn(6, 8, 3, 3, generator=g), torch.randn(6, generator=g)
+    dy = torch.randn(2, 5, 7, 6, generator=g)
+    for f32, f64 in ((R.conv2d(x, wt, b, 2, dtype=torch.float32), R.conv2d(x, wt, b, 2)),
+                     (R.conv2d_dgrad(dy, wt, (9, 13), 2, dtype=torch.float32), R.conv2d_dgrad(dy, wt, (9, 13), 2)),
+                     (R.conv2d_wgrad(x, dy, 3, 2, dtype=torch.float32)[0], R.conv2d_wgrad(x, dy, 3, 2)[0])):
+        assert f32.dtype == torch.float32 and f64.dtype == D
+        e = float((f32.double() - f64).abs().max() / f64.abs().max())
+        assert 0.0 < e <= 1e-5, e
+    close(R.conv2d(x, wt, b, 2, rnd=R.bf16_rne, dtype=torch.float32).double(), R.conv2d(x, wt, b, 2, rnd=R.bf16_rne), 1e-5)
 
 
 def test_conv_chunking_by_image(monkeypatch):
