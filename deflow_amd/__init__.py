@@ -9,3 +9,4 @@ from .voidmap import VoidMap, label_scene  # noqa: F401
 from .ground import GroundSegmenter  # noqa: F401
 from .metrics_device import DeviceMetrics  # noqa: F401
 from .sweeps import SweepFlow  # noqa: F401
+from .submit import SubmitFlow  # noqa: F401

@@ -8,12 +8,21 @@ checkpoint and the data need naming.  Metrics: deflow_amd/metrics.py -- ``leader
 EPE table, ``leaderboard_version=2`` the bucketed normalised EPE; plus a range-free EPE / accuracy summary -- over the sweeps
 of ``val_data`` (preprocessed scene files, deflow_amd/data.py) or over seeded synthetic pairs with ``val_data=synthetic``.
 ``metrics_impl=device`` accumulates the same tables and summary on the GPU (deflow_amd/metrics_device.py: no host sync per batch; default
-``host``).  ``av2_mode=test`` (leaderboard submission zips) is the reference's control plane and is not built."""
+``host``).
+
+``python -m deflow_amd.eval checkpoint=<ckpt> av2_mode=test dataset_path=<root> [leaderboard_version=1|2]`` ([REF README.md:90-91]: "it
+will output a command with absolute path of a zip file for you to submit to leaderboard") writes the Argoverse-2 submission of the frames
+under ``<root>/test`` (``test_data=<dir>`` names the directory itself): per frame of the directory's index that carries an ``eval_mask`` and
+has a successor, ``<scene_id>/<timestamp>.feather`` with the fp16 flow of the masked rows, in one zip (``output=<zip>``, default
+``<checkpoint stem>.av2_submit_v<version>.zip`` beside the checkpoint).  The rows are selected, rounded and laid out as the file's body on
+the GPU (deflow_amd/submit.py, DESIGN.md section 6g, UNPINNED); deflow_amd/feather.py wraps the metadata around it.  ``ground_source=
+auto|file|sidecar|online``, ``batch_size=``, ``num_workers=`` and ``inference_dtype=`` as in ``deflow_amd.save``."""
 from __future__ import annotations
 
 import json
 import os
 import sys
+from typing import Any, Dict, List
 
 import torch
 
@@ -45,14 +54,125 @@ def resolve_config(path: str, given: dict, skip=()) -> dict:
     return cfg
 
 
+# ---- av2_mode=test: the leaderboard submission ---------------------------------------------------------------------------------------------
+TEST_OWN_KEYS = ("leaderboard_version", "test_data", "output", "ground_source", "inference_dtype")     # not hyper-parameters: kept from resolve_config
+TEST_USAGE = ("usage: python -m deflow_amd.eval checkpoint=<ckpt> av2_mode=test dataset_path=<root> [leaderboard_version=1|2] [test_data=<dir>] "
+              "[output=<zip>] [ground_source=auto|file|sidecar|online] [batch_size=] [num_workers=] [inference_dtype=fp32|bf16]")
+
+
+def parse_test_args(argv: List[str]) -> Dict[str, Any]:
+    """The key=value arguments of ``av2_mode=test`` -> checkpoint, version, test_dir (None when neither ``test_data=`` nor
+    ``dataset_path=`` names one: the reference reads its configuration's default there, this command then stops), output, ground_source,
+    inference_dtype, and under ``_given`` ({key: "key=value"}) everything ``resolve_config`` lays over the checkpoint's configuration.
+    Needs no GPU and reads no file."""
+    from .save import GROUND_SOURCES
+    given: Dict[str, str] = {}
+    for a in argv:
+        if "=" not in a:
+            raise SystemExit(f"expected key=value, got {a!r}")
+        given[a.split("=", 1)[0].lstrip("+")] = a
+    val = lambda k, default=None: given[k].split("=", 1)[1] if k in given else default
+    if val("av2_mode") != "test":
+        raise SystemExit(TEST_USAGE)
+    if not val("checkpoint"):
+        raise SystemExit(TEST_USAGE)
+    opt: Dict[str, Any] = {"checkpoint": val("checkpoint"), "ground_source": val("ground_source", "auto"), "inference_dtype": val("inference_dtype")}
+    if val("leaderboard_version", "1") not in ("1", "2"):
+        raise SystemExit("leaderboard_version must be 1 (flow and is_dynamic) or 2 (is_valid and flow)")
+    opt["version"] = int(val("leaderboard_version", "1"))
+    if opt["ground_source"] not in GROUND_SOURCES:
+        raise SystemExit(f"bad value for ground_source: {opt['ground_source']!r} ({', '.join(GROUND_SOURCES)})")
+    if opt["inference_dtype"] not in (None, "fp32", "bf16"):
+        raise SystemExit(f"bad value for inference_dtype: {opt['inference_dtype']!r} (fp32, bf16)")
+    for k, low in (("batch_size", 1), ("num_workers", 0)):
+        if k in given:
+            try:
+                ok = int(val(k)) >= low
+            except ValueError:
+                ok = False
+            if not ok:
+                raise SystemExit(f"bad value for {k}: {val(k)!r}")
+    for k in ("test_data", "dataset_path", "output"):
+        if k in given and not val(k):
+            raise SystemExit(f"bad value for {k}: {val(k)!r}")
+    opt["test_dir"] = val("test_data") or (os.path.join(val("dataset_path"), "test") if "dataset_path" in given else None)
+    stem = os.path.splitext(os.path.basename(opt["checkpoint"]))[0]
+    opt["output"] = val("output") or os.path.join(os.path.dirname(opt["checkpoint"]), f"{stem}.av2_submit_v{opt['version']}.zip")
+    opt["_given"] = given
+    return opt
+
+
+def main_test(argv: List[str]) -> Dict[str, Any]:
+    opt = parse_test_args(argv)
+    if not opt["test_dir"]:
+        raise SystemExit("av2_mode=test needs the data: dataset_path=<root> (reads <root>/test) or test_data=<dir>\n" + TEST_USAGE)
+    assert torch.cuda.is_available(), "the submission is computed on the HIP engine only"
+    from torch.utils.data import DataLoader
+    from .feather import body_len, feather_file
+    from .save import _Pinned
+    from .submit import SubmissionZip, SubmitFlow, collate_submit_pad, submission_frames
+    path, version, online = opt["checkpoint"], opt["version"], opt["ground_source"] == "online"
+    cfg = resolve_config(path, opt["_given"], skip=TEST_OWN_KEYS)
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(dev)
+    model = build_model(cfg).to(dev)
+    res = model.load_from_checkpoint(path)
+    if res.missing_keys or res.unexpected_keys:
+        print(f"[deflow_amd.eval] WARNING: checkpoint / model mismatch (model={cfg['model']}): {len(res.missing_keys)} missing keys "
+              f"{res.missing_keys[:4]}..., {len(res.unexpected_keys)} unexpected keys {res.unexpected_keys[:4]}...", file=sys.stderr)
+    model.eval()
+    if opt["inference_dtype"]:
+        model.inference_dtype = opt["inference_dtype"]
+    frames, skipped = submission_frames(opt["test_dir"], opt["ground_source"])
+    flows: Dict[int, SubmitFlow] = {}
+
+    def submit_flow_for(B: int) -> SubmitFlow:           # a ground segmenter belongs to one batch size
+        if B not in flows:
+            ground = None
+            if online:
+                from .ground import GroundSegmenter
+                ground = GroundSegmenter(B, device=dev)
+            flows[B] = SubmitFlow(model, ground=ground)
+        return flows[B]
+
+    pinned = _Pinned()
+    rows = 0
+    out = os.path.abspath(opt["output"])
+    with SubmissionZip(out) as zf:
+        loader = DataLoader(frames, batch_size=int(cfg["batch_size"]), shuffle=False, collate_fn=collate_submit_pad,
+                            num_workers=max(0, int(cfg["num_workers"])), pin_memory=True, drop_last=False) if len(frames) else ()
+        for host in loader:
+            d = {k: v.to(dev, non_blocking=True) for k, v in host.items() if isinstance(v, torch.Tensor)}
+            body, kept = submit_flow_for(len(host["timestamp"])).infer(
+                d["raw0"], d["n0"], None if online else d["drop0"], d["raw1"], d["n1"], None if online else d["drop1"], d["pose0"], d["pose1"],
+                d["eval0"], ego_motion=d.get("ego_motion"), version=version)
+            hb, hk = pinned.like("body", body), pinned.like("kept", kept)
+            hb.copy_(body, non_blocking=True)
+            hk.copy_(kept, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            hbn = hb.numpy()
+            for i, (sid, ts, M) in enumerate(zip(host["scene_id"], host["timestamp"], hk.tolist())):      # hk is on the host
+                zf.add(sid, ts, feather_file(version, M, hbn[i, : body_len(M, version)]))
+                rows += M
+        members = zf.members
+    result = {"zip": out, "frames": members, "rows": rows, "skipped": skipped, "leaderboard_version": version, "checkpoint": path,
+              "model": cfg["model"], "test_data": opt["test_dir"]}
+    print(f"[deflow_amd.eval] submission of {members} frames written: upload {out} to the Argoverse-2 scene flow leaderboard "
+          f"(version {version})", file=sys.stderr, flush=True)
+    print(json.dumps(result), flush=True)
+    return result
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
+    if given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        return main_test(args)          # the leaderboard submission: no metrics (the test split has no labels)
     if given.get("av2_mode", "av2_mode=val") != "av2_mode=val":
-        raise SystemExit("only av2_mode=val is implemented (test-split submission files are out of scope)")
+        raise SystemExit(f"unknown {given['av2_mode']} (val: the metrics, test: the leaderboard submission)")
     if "checkpoint" not in given:
-        raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]")
+        raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE)
     path = given["checkpoint"].split("=", 1)[1]
     cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
     if not any(k in given for k in DATA_KEYS):

@@ -11,8 +11,8 @@ one copy per batch and output array comes back.  Per scene ``<scene_id>.<res_nam
 
 The configuration is the checkpoint's, overridden by the command line, exactly as ``deflow_amd.eval`` resolves it.  ``res_name`` defaults
 to the checkpoint's file stem; ``ground_source=auto|file|sidecar`` as ``HDF5Dataset`` reads masks, ``online`` computes them on the GPU per
-batch (``ground.GroundSegmenter``) and needs no mask on disk.  ``av2_mode=test`` (leaderboard submission zips) stays out of scope: the
-submission format is feather, which cannot be written here."""
+batch (``ground.GroundSegmenter``) and needs no mask on disk.  ``av2_mode`` is refused: the leaderboard submission (a zip of feather files) is
+``python -m deflow_amd.eval checkpoint=<ckpt> av2_mode=test dataset_path=<root>``."""
 from __future__ import annotations
 
 import json
@@ -55,7 +55,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         k = k.lstrip("+")
         if k == "av2_mode":
             raise SystemExit("deflow_amd.save writes <scene_id>.<res_name>.flow.npz beside the scene files and takes no av2_mode: the "
-                             "av2_mode=test leaderboard submission is a zip of feather files, which cannot be written here (out of scope)")
+                             "av2_mode=test leaderboard submission, a zip of feather files, is written by  python -m deflow_amd.eval checkpoint=<ckpt> "
+                             "av2_mode=test dataset_path=<root>")
         if k in ("checkpoint", "dataset_path", "res_name"):
             if not v:
                 raise SystemExit(f"bad value for {k}: {v!r}")

@@ -770,6 +770,27 @@ int df_flow_compose(const float* raw, const int32_t* count_raw, const float* T, 
                     const int64_t* idx_c, const int32_t* counts, int B, int N, int Nc, int half, void* ws, void* flow_est,
                     uint8_t* dynamic, void* stream);
 
+/* ------------------------------------------------------------------ leaderboard submission: the body of one feather file per sweep ----
+ * UNPINNED: column names, order and types of the Argoverse-2 scene-flow submission are recalled, and no file written
+ * here was ever accepted by the evaluation server.  The benchmark's rows of a sweep are the rows with eval_mask != 0, in raw order:
+ * df_sweep_compact with drop = (eval_mask == 0) gives row_of [B,N] and kept [B]; M = kept[b] clamped to [0, N] below.
+ * df_submit_pack: flow_est [B,N,3] f32 and dynamic [B,N] u8 (df_flow_compose with half = 0), row_of, kept, version in {1, 2} ->
+ *   body [B,S] u8, S = df_submit_body_stride(N): the body of an uncompressed Arrow record batch of M rows and four columns, every buffer
+ *   padded with zeros to 8 bytes.  P = pad8(2 M), Q = pad8(ceil(M / 8)), L(M) = 3 P + Q.
+ *     version 1: flow_tx_m at 0, flow_ty_m at P, flow_tz_m at 2 P (M fp16 values each), the is_dynamic bits at 3 P
+ *     version 2: the is_valid bits at 0 (set for every p < M), the three fp16 columns at Q, Q + P, Q + 2 P
+ *   fp16 values: the fp32 component of row row_of[b, p] rounded to nearest even (numpy's astype(float16), overflow to inf included); bit p of
+ *   a flag column is bit p & 7 of byte p >> 3 (Arrow's boolean layout); is_dynamic of p is dynamic[row_of[b, p]] != 0.  A row_of entry
+ *   outside [0, N) among the first M (df_sweep_compact writes none) packs as a zero row.  Bytes [0, L(M)) of a sample are each written
+ *   exactly once; bytes from L(M) on are not touched.
+ * df_submit_body_stride(N): L(N) rounded up to 64 (DF_E_SHAPE for N < 1).  No workspace.
+ * body 8-byte aligned (DF_E_ALIGN).  1 <= B <= 65535, N >= 1, B * S < 2^31: violations return DF_E_SHAPE; NULL buffers and a version outside
+ * {1, 2} return DF_E_ARG.  No launch then.  The grid comes from N, never from a device value; the entry never allocates or synchronises
+ * and reads nothing back; no atomics, two runs are bit-identical. */
+int64_t df_submit_body_stride(int N);
+int df_submit_pack(const float* flow_est, const uint8_t* dynamic, const int32_t* row_of, const int32_t* kept, int B, int N, int version,
+                   uint8_t* body, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
