@@ -656,7 +656,11 @@ __global__ __launch_bounds__(256) void gru_lean_finalize_kernel(FinParams p) {
   }
 }
 
-// Waves per workgroup of the lean kernels (round 6; same arithmetic per point in every form, bit-identical results):
+// Waves per workgroup of the lean kernels (round 6).  Same arithmetic per point in every form: flow, the saved planes, the gate-gradient
+// planes, dh0 and dpre1 are bit-identical.  The backward's per-workgroup partial sums (S, dW_2, d b_2) are not: a workgroup adds its 4 or 8
+// waves' partials before the column sum adds the workgroups', so the 4-wave form groups the same fp32 terms differently and everything
+// derived from those sums (biases, x columns, offset encoder, W_2) differs in the last bits
+// (tests/test_gpu_decoder_bf16_cases.py::test_wave_forms_bit_identical).
 //   backward: DF_GRU_WAVES = 8 (default: 128 points, one workgroup per CU, five of the six S accumulators in LDS: no scratch traffic
 //             in the iteration loop -- 5.26 vs 5.60 ms) | 4 (64 points, two workgroups per CU: rounds 3-5; 20 scratch instructions per iteration)
 //   forward:  DF_GRU_FWD_WAVES = 12 (default in bf16x2 mode: 192 points, THREE waves per SIMD at 168 registers -- 2.50 vs 2.72 ms,

@@ -62,9 +62,15 @@ ALLOW = {
     **{k: "test_gpu_pfn_cases.py::test_pfn_case_vs_float64" for k in ("df_pfn_bwd_stats", "df_pfn_bwd_finalize", "df_pfn_bwd_weights")},
     # GRU trio (and the decoder's bias-sum / weight-plane helpers): one golden input (B = 3, rows 333 / 0 / 1) at 1 - 16 iterations, and
     # the cases built for the row tiles and split-K walks (tests/helpers/decoder_cases.py), lean / lean_fp32 / full forms
+    # bf16 mode (runs C and E): the lean trio and the full form's forward against the float64 emulation of their own rounding points
+    # (tests/helpers/decoder_bf16_ref.py); the full form's bf16 backward stays on the 2e-2 rule of test_decoder_case_bf16_operand_mode
     **{k: "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64" for k in (
-        "df_gru_decoder_fwd_mp", "df_gru_decoder_bwd_mp", "df_gru_wgrad_mp", "df_gru_xtab", "df_gru_lean_fwd", "df_gru_lean_bwd",
-        "df_gru_lean_wgrad", "df_gru_lean_head_wgrad", "df_gru_lean_finalize", "df_gru_head_wgrad", "df_split_bf16x2_rows")},
+        "df_gru_decoder_bwd_mp", "df_gru_wgrad_mp", "df_gru_head_wgrad", "df_split_bf16x2_rows")},
+    **{k: "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64; bf16 mode: "
+          "test_gpu_decoder_bf16_cases.py::test_bf16_mode_step_vs_float64, ::test_mode1_equals_mode2, ::test_wave_forms_bit_identical"
+       for k in ("df_gru_xtab", "df_gru_lean_fwd", "df_gru_lean_bwd", "df_gru_lean_wgrad", "df_gru_lean_head_wgrad", "df_gru_lean_finalize")},
+    "df_gru_decoder_fwd_mp": "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64; bf16 mode: "
+                             "test_gpu_decoder_bf16_cases.py::test_bf16_mode_forward_vs_float64",
     # the split-K reduction: behind the decoder's weight gradients, and on a workspace of known content (every loop remainder, ld_co wider
     # than a row, accumulate)
     "df_conv2d_wgrad_reduce": "test_gpu_kernels.py::test_gru_decoder_golden, test_gpu_decoder_cases.py::test_decoder_case_vs_float64, "
@@ -82,7 +88,8 @@ ALLOW = {
     **{k: "test_gpu_model.py::test_alternate_kernel_paths (through the _mp entry)" for k in (
         "df_gru_decoder_fwd", "df_gru_decoder_bwd", "df_gru_wgrad")},
     # the bf16 inference forward of the head (DeFlow.inference_dtype = "bf16")
-    "df_gru_decoder_fwd_bf16": "test_gpu_model.py::test_bf16_inference_path_vs_oracle",
+    "df_gru_decoder_fwd_bf16": "test_gpu_decoder_bf16_cases.py::test_inference_kernel_vs_float64, "
+                               "test_gpu_model.py::test_bf16_inference_path_vs_oracle",
     # ego-motion transform, deflowLoss through DeflowLossFn, host-step Adam at n = 4096
     **{k: "test_gpu_kernels.py::test_ego_transform_loss_adam" for k in ("df_ego_transform", "df_adam_step")},
     # the loss trios, the ground-truth gather and the device-step Adam, each against a float64 restatement
