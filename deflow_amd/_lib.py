@@ -126,6 +126,8 @@ _SIGS = {
     "df_conv2d_wgrad_reduce_bias": [P, I, I, I, I, P, L, I, P, P, P],
     "df_upsample2x": [DfImg, DfImg, I, P],
     "df_upsample2x_bwd": [DfImg, DfImg, I, P],
+    "df_upsample2x_bwd_h2": [DfImg, DfImg, I, P, P],
+    "df_u5u1_decompose": [P, P, P, P, P, I, I, I, I, P, P, P, P, P],
     "df_gru_decoder_fwd": [DfImg, DfImg, P, P, P, I, I, I, DfGruWeights, P, P, P],
     "df_gru_decoder_fwd_mp": [DfImg, DfImg, P, P, P, I, I, I, DfGruWeights, P, P, I, P],
     "df_gru_decoder_bwd_mp": [P, P, P, I, I, I, DfGruWeights, DfGruWeightsT, P, P, P, P, P, P, I, P],

@@ -134,19 +134,128 @@ struct df_wprep_layer {
   int64_t wt_off, w2_off, wt2_off;   // element offsets in the output buffer (wt: floats; w2 / wt2: in floats too, 2 x numel halfs = numel floats)
   int32_t cout, taps, cin, split;    // split: also write the fp16 planes
   int32_t blk0;                      // first workgroup of this layer
-  int32_t pad;
+  int32_t pad;                       // > 0: a COMPOSED layer (below) -- w_off / b_off address `out`, and tab[pad] is its source record
 };
-__global__ __launch_bounds__(256) void weight_prep_kernel(const float* __restrict__ params, const df_wprep_layer* __restrict__ tab, int nlayers,
-                                                          const float* __restrict__ w_amax, float* __restrict__ out,
-                                                          unsigned* __restrict__ norms /* [nlayers][3]: l1w, l1wt, bmax */) {
+
+// ---- composed layers (df_weight_prep, before the forms above are made) ---------------------------------------------------------
+// An UpsampleSkip block's last 3x3 convolution (W5 [C][taps][I], b5) is read by the next block's 1x1 convolution (W1 [O][C], b1) alone,
+// with nothing in between [REF deflow.py:32 FastFlow3DUNet / UpsampleSkip]: the pair is ONE 3x3 layer, exactly (the 1x1 has no padding
+// and b5 is present at every pixel, so the identity holds at the border too):
+//   We[o][tap][i] = sum_c W1[o][c] W5[c][tap][i]        be[o] = sum_c W1[o][c] b5[c] + b1[o]
+// A composed layer is an ordinary record whose weights live in `out` (pad > 0); its source record tab[pad] (past the nlayers ordinary
+// ones) holds  w_off = W5, b_off = b5, wt_off = W1, w2_off = b1 (elements in `params`), wt2_off = the index in `norms` of the slot that
+// receives max |We| (the scale of the composed planes: it can exceed the arena's max |w|), cout = C, taps, cin = I, split = O.
+// Sums run over c in ascending order in double; the maximum is an integer atomic max: the result is bit-reproducible.
+// out[row0 + r][j] = sum_k A[(row0 + r) * rs + k * ks] Bm[k * J + j]   for r < 8, one j per thread
+__device__ __forceinline__ void df_small_gemm8(const float* __restrict__ A, int64_t rs, int64_t ks, const float* __restrict__ Bm, int K, int J,
+                                               int row0, int j, double (&acc)[8]) {
+#pragma unroll
+  for (int r = 0; r < 8; ++r) acc[r] = 0.0;
+  if (j >= J) return;
+  for (int k = 0; k < K; ++k) {
+    const double b = (double)Bm[(int64_t)k * J + j];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = __builtin_fma((double)A[(row0 + r) * rs + k * ks], b, acc[r]);
+  }
+}
+__global__ __launch_bounds__(256) void weight_compose_kernel(const float* __restrict__ params, const df_wprep_layer* __restrict__ tab, int nlayers,
+                                                             float* __restrict__ out, unsigned* __restrict__ norms) {
+  for (int L = 0; L < nlayers; ++L) {
+    const df_wprep_layer t = tab[L];
+    if (t.pad <= 0) continue;
+    const df_wprep_layer src = tab[t.pad];
+    const int O = t.cout, J = t.taps * t.cin, C = src.cout;
+    const float* __restrict__ w5 = params + src.w_off;
+    const float* __restrict__ w1 = params + src.wt_off;
+    const int nj = (J + 255) >> 8, ntile = nj * (O >> 3);
+    for (int g = blockIdx.x; g <= ntile; g += gridDim.x) {
+      if (g == ntile) {            // the bias
+        for (int o = threadIdx.x; o < O; o += 256) {
+          double a = 0.0;
+          for (int c = 0; c < C; ++c) a = __builtin_fma((double)w1[(int64_t)o * C + c], (double)params[src.b_off + c], a);
+          out[t.b_off + o] = (float)(a + (double)params[src.w2_off + o]);
+        }
+        continue;
+      }
+      const int rt = g / nj, j = (g - rt * nj) * 256 + (int)threadIdx.x;
+      double acc[8];
+      df_small_gemm8(w1, C, 1, w5, C, J, rt * 8, j, acc);
+      float m = 0.f;
+      if (j < J) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const float v = (float)acc[r];
+          out[t.w_off + (int64_t)(rt * 8 + r) * J + j] = v;
+          m = fmaxf(m, fabsf(v));
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+      if ((threadIdx.x & 63) == 0) df_atomic_amax(norms + src.wt2_off, m);
+    }
+  }
+}
+
+// The parameter gradients behind a composed layer, from its weight gradient dWe [O][taps][I] and bias sum dbe [O] (df_u5u1_decompose):
+//   dW5[c][tap][i] = sum_o W1[o][c] dWe[o][tap][i]                               blocks [0, na): 8 rows c x 256 columns
+//   dW1[o][c]      = sum_{tap,i} dWe[o][tap][i] W5[c][tap][i] + dbe[o] b5[c]     blocks [na, na + nb): 16 x 16 outputs, LDS tiles of 64 k
+//   db5[c] = sum_o W1[o][c] dbe[o],  db1 = dbe                                   the last block
+// every sum in ascending index order in double: bit-reproducible
+__global__ __launch_bounds__(256) void u5u1_decompose_kernel(const float* __restrict__ w1, const float* __restrict__ w5, const float* __restrict__ b5,
+                                                             const float* __restrict__ dwe, const float* __restrict__ dbe, int O, int C, int J,
+                                                             float* __restrict__ dw5, float* __restrict__ db5, float* __restrict__ dw1,
+                                                             float* __restrict__ db1) {
+  __shared__ float As[16][65], Bs[16][65];
+  const int nj = (J + 255) >> 8, na = nj * (C >> 3), nb = (O >> 4) * (C >> 4);
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (g < na) {
+    const int rt = g / nj, j = (g - rt * nj) * 256 + tid;
+    double acc[8];
+    df_small_gemm8(w1, 1, C, dwe, O, J, rt * 8, j, acc);
+    if (j < J) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) dw5[(int64_t)(rt * 8 + r) * J + j] = (float)acc[r];
+    }
+  } else if (g < na + nb) {
+    const int b = g - na, o0 = (b / (C >> 4)) * 16, c0 = (b % (C >> 4)) * 16;
+    const int ty = tid >> 4, tx = tid & 15;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < J; k0 += 64) {
+      const f32x4 a = ld4(dwe + (int64_t)(o0 + ty) * J + k0 + tx * 4), q = ld4(w5 + (int64_t)(c0 + ty) * J + k0 + tx * 4);
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        As[ty][tx * 4 + u] = a[u];
+        Bs[ty][tx * 4 + u] = q[u];
+      }
+      __syncthreads();
+#pragma unroll 8
+      for (int k = 0; k < 64; ++k) acc = __builtin_fma((double)As[ty][k], (double)Bs[tx][k], acc);
+    }
+    acc = __builtin_fma((double)dbe[o0 + ty], (double)b5[c0 + tx], acc);
+    dw1[(int64_t)(o0 + ty) * C + c0 + tx] = (float)acc;
+  } else {
+    for (int c = tid; c < C; c += 256) {
+      double a = 0.0;
+      for (int o = 0; o < O; ++o) a = __builtin_fma((double)w1[(int64_t)o * C + c], (double)dbe[o], a);
+      db5[c] = (float)a;
+    }
+    for (int o = tid; o < O; o += 256) db1[o] = dbe[o];
+  }
+}
+__global__ __launch_bounds__(256) void weight_prep_kernel(const float* params, const df_wprep_layer* __restrict__ tab, int nlayers,
+                                                          const float* __restrict__ w_amax, float* out,
+                                                          unsigned* norms /* [nlayers][3]: l1w, l1wt, bmax (+ the composed layers' max |We|) */) {
   __shared__ float red[4];
   int L = 0;
   for (int i = 1; i < nlayers; ++i)
     if ((int)blockIdx.x >= tab[i].blk0) L = i;      // (a few dozen layers: a linear scan of scalar loads)
   const df_wprep_layer t = tab[L];
   const int r = (int)blockIdx.x - t.blk0;
-  const float s = df_h2_scale(*w_amax);
-  const float* w = params + t.w_off;
+  // (a composed layer: weights and bias in `out`, written by weight_compose_kernel before this launch; planes scaled by ITS maximum)
+  const float* pbase = t.pad > 0 ? out : params;
+  const float s = df_h2_scale(t.pad > 0 ? __builtin_bit_cast(float, norms[tab[t.pad].wt2_off]) : *w_amax);
+  const float* w = pbase + t.w_off;
   const int64_t numel = (int64_t)t.cout * t.taps * t.cin;
   float a = 0.f;
   if (r < t.cout) {                 // a row of w: [taps][cin] contiguous
@@ -188,7 +297,7 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const float* __restric
     df_atomic_amax(norms + 3 * L + (r < t.cout ? 0 : 1), (red[0] + red[1]) + (red[2] + red[3]));
     if (r == 0 && t.b_off >= 0) {
       float b = 0.f;
-      for (int i = 0; i < t.cout; ++i) b = fmaxf(b, fabsf(params[t.b_off + i]));
+      for (int i = 0; i < t.cout; ++i) b = fmaxf(b, fabsf(pbase[t.b_off + i]));
       df_atomic_amax(norms + 3 * L + 2, b);
     }
   }
@@ -756,7 +865,13 @@ __global__ __launch_bounds__(256) void upsample2x_bf16_kernel(df_img x, df_img y
 }
 
 // gather form of the transpose: every input pixel sums the <= 6x6 output pixels that read it
-__global__ __launch_bounds__(256) void upsample2x_bwd_kernel(df_img dy, df_img dx, int align_corners, int64_t total4) {
+// H2: dx is an h2 image (the dy of a 3x3 layer composed of a block's last 3x3 and the next block's 1x1: its consumers are the pre-split
+// data- and weight-gradient kernels), scaled by *dx_bound (>= max |dx|: 4.5 max |dy|); the sums are those of the fp32 form, so the
+// planes equal df_h2_pack of its output bit for bit
+template <bool H2>
+__global__ __launch_bounds__(256) void upsample2x_bwd_kernel(df_img dy, df_img dx, int align_corners, int64_t total4,
+                                                             const float* __restrict__ dx_bound) {
+  const float hs = H2 ? df_h2_scale(*dx_bound) : 1.f;
   const int C4 = dx.c >> 2;
   const int c4s = df_pow2_shift(C4), xws = df_pow2_shift(dx.w), xhs = df_pow2_shift(dx.h);
   const float* __restrict__ dyp = reinterpret_cast<const float*>(dy.ptr);
@@ -795,14 +910,17 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(df_img dy, df_img d
         acc += (wy[a] * wx[k]) * ld4(b + ((int64_t)Y * dy.w + X) * dy.ld);
       }
     }
-    st4(dxp + df_img_base(dx, n) + ((int64_t)yy * dx.w + xx) * dx.ld + c, acc);
+    if constexpr (H2) st_h2x4(dx.ptr, df_img_base(dx, n) + ((int64_t)yy * dx.w + xx) * dx.ld + c, acc, hs);
+    else st4(dxp + df_img_base(dx, n) + ((int64_t)yy * dx.w + xx) * dx.ld + c, acc);
   }
 }
 
 // align_corners = false, eight channels per thread (round 6, second session): only the 4 x 4 outputs 2 y - 1 .. 2 y + 2 can read input
 // row / column y; their weights come from the same source-index function as the forward (borders included), loads are unconditional at
 // clamped addresses (a tap outside the image, or one that does not read this input, has weight 0), summation order = the gather form's
-__global__ __launch_bounds__(256) void upsample2x_bwd8_kernel(df_img dy, df_img dx, int64_t total8) {
+template <bool H2>
+__global__ __launch_bounds__(256) void upsample2x_bwd8_kernel(df_img dy, df_img dx, int64_t total8, const float* __restrict__ dx_bound) {
+  const float hs = H2 ? df_h2_scale(*dx_bound) : 1.f;
   const int C8 = dx.c >> 3;
   const int c8s = df_pow2_shift(C8), xws = df_pow2_shift(dx.w), xhs = df_pow2_shift(dx.h);
   const float* __restrict__ dyp = reinterpret_cast<const float*>(dy.ptr);
@@ -842,9 +960,14 @@ __global__ __launch_bounds__(256) void upsample2x_bwd8_kernel(df_img dy, df_img 
         acc1 += w * v1[k];
       }
     }
-    float* q = dxp + df_img_base(dx, n) + ((int64_t)yy * dx.w + xx) * dx.ld + c;
-    st4(q, acc0);
-    st4(q + 4, acc1);
+    const int64_t qi = df_img_base(dx, n) + ((int64_t)yy * dx.w + xx) * dx.ld + c;
+    if constexpr (H2) {
+      st_h2x4(dx.ptr, qi, acc0, hs);
+      st_h2x4(dx.ptr, qi + 4, acc1, hs);
+    } else {
+      st4(dxp + qi, acc0);
+      st4(dxp + qi + 4, acc1);
+    }
   }
 }
 
@@ -863,6 +986,11 @@ bool h2_ok(const df_img& d) {
 bool up8_on() {
   static const bool on = !(getenv("DF_UP8") && atoi(getenv("DF_UP8")) == 0);
   return on;
+}
+// DF_FUSE_U5U1=0: no composed layers (the table then holds none either: ops.WeightPrep); read per call, as ops.fuse_u5u1_on does
+bool fuse_u5u1_on() {
+  const char* e = getenv("DF_FUSE_U5U1");
+  return !(e && atoi(e) == 0);
 }
 bool rowpart_ok(int C) { return C >= 4 && C <= 1024 && (C % 4) == 0 && (256 % (C / 4)) == 0; }
 unsigned grid_for(int64_t total, int per_block = 256, unsigned cap = 256 * 16) {
@@ -1107,8 +1235,29 @@ extern "C" int df_rows_l1max(const float* w, int rows, int row_len, const float*
 extern "C" int df_weight_prep(const float* params, const void* table, int nlayers, int total_blocks, const float* w_amax, float* out,
                               float* norms, void* stream) {
   DF_REQUIRE(params && table && nlayers > 0 && total_blocks > 0 && w_amax && out && norms, DF_E_ARG);
+  // composed layers first (records with pad > 0; the launch finds them in the table: a table without any costs an empty pass)
+  if (fuse_u5u1_on()) {
+    hipLaunchKernelGGL(weight_compose_kernel, dim3(256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params,
+                       reinterpret_cast<const df_wprep_layer*>(table), nlayers, out, reinterpret_cast<unsigned*>(norms));
+    DF_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL(weight_prep_kernel, dim3(total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params,
                      reinterpret_cast<const df_wprep_layer*>(table), nlayers, w_amax, out, reinterpret_cast<unsigned*>(norms));
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+// dW5 [C][taps][I], db5 [C], dW1 [O][C], db1 [O] from the weight gradient dwe [O][taps][I] and bias sum dbe [O] of the layer composed of
+// w5 [C][taps][I], b5 [C] and w1 [O][C] (kernel comment above); O, C % 16 == 0, I % 64 == 0
+extern "C" int df_u5u1_decompose(const float* w1, const float* w5, const float* b5, const float* dwe, const float* dbe, int O, int C, int taps,
+                                 int I, float* dw5, float* db5, float* dw1, float* db1, void* stream) {
+  DF_REQUIRE(w1 && w5 && b5 && dwe && dbe && dw5 && db5 && dw1 && db1, DF_E_ARG);
+  DF_REQUIRE(O > 0 && C > 0 && taps > 0 && I > 0 && (O % 16) == 0 && (C % 16) == 0 && (I % 64) == 0, DF_E_SHAPE);
+  DF_REQUIRE(df_aligned16(dwe) && df_aligned16(w5), DF_E_ALIGN);
+  const int J = taps * I;
+  const int grid = ((J + 255) / 256) * (C / 8) + (O / 16) * (C / 16) + 1;
+  hipLaunchKernelGGL(u5u1_decompose_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w1, w5, b5, dwe, dbe, O, C, J, dw5,
+                     db5, dw1, db1);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }
@@ -1137,13 +1286,31 @@ extern "C" int df_upsample2x_bwd(df_img dy, df_img dx, int align_corners, void* 
   DF_REQUIRE(dx.n == dy.n && dx.c == dy.c && dy.h == 2 * dx.h && dy.w == 2 * dx.w, DF_E_SHAPE);
   const int64_t total4 = (int64_t)dx.n * dx.h * dx.w * (dx.c / 4);
   if (!align_corners && up8_on() && (dx.c % 8) == 0) {
-    hipLaunchKernelGGL(upsample2x_bwd8_kernel, dim3(grid_for(total4 / 2)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, dx,
-                       total4 / 2);
+    hipLaunchKernelGGL(upsample2x_bwd8_kernel<false>, dim3(grid_for(total4 / 2)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, dx,
+                       total4 / 2, nullptr);
     DF_CHECK_LAUNCH();
     return DF_OK;
   }
-  hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), dy, dx, align_corners, total4);
+  hipLaunchKernelGGL(upsample2x_bwd_kernel<false>, dim3(grid_for(total4)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), dy, dx, align_corners, total4, nullptr);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+// ... into an h2 image dx (dx.elt = 2), scaled by *dx_bound (>= max |dx|; the engine passes 4.5 max |dy|): the planes df_h2_pack would
+// make of df_upsample2x_bwd's output with the same bound, without the fp32 tensor in between
+extern "C" int df_upsample2x_bwd_h2(df_img dy, df_img dx, int align_corners, const float* dx_bound, void* stream) {
+  DF_REQUIRE(h2_ok(dx) && img_ok(dy) && dx_bound, DF_E_ARG);
+  DF_REQUIRE(dx.n == dy.n && dx.c == dy.c && dy.h == 2 * dx.h && dy.w == 2 * dx.w, DF_E_SHAPE);
+  const int64_t total4 = (int64_t)dx.n * dx.h * dx.w * (dx.c / 4);
+  if (!align_corners && up8_on()) {     // (h2 images hold whole 32-channel chunks: c % 8 == 0)
+    hipLaunchKernelGGL(upsample2x_bwd8_kernel<true>, dim3(grid_for(total4 / 2)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, dx,
+                       total4 / 2, dx_bound);
+    DF_CHECK_LAUNCH();
+    return DF_OK;
+  }
+  hipLaunchKernelGGL(upsample2x_bwd_kernel<true>, dim3(grid_for(total4)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), dy, dx, align_corners, total4, dx_bound);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }

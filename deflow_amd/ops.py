@@ -318,6 +318,11 @@ def h2_pack(x: torch.Tensor, bound: torch.Tensor) -> torch.Tensor:
     return t
 
 
+def fuse_u5u1_on() -> bool:
+    """DF_FUSE_U5U1=0: no composed layers -- every UpsampleSkip block runs its last 3x3 and the next block its 1x1 (unet._upsample_skip)"""
+    return os.environ.get("DF_FUSE_U5U1", "1") != "0"
+
+
 class WeightPrep:
     """Every convolution layer's per-step weight forms from ONE launch (df_weight_prep; round 4): transposed weights, [hi | lo] fp16
     planes of the weights and of their transpose (every layer: the 3x3 stride-1 kernels and, since the round's second session, the
@@ -325,15 +330,26 @@ class WeightPrep:
     ops.WPREP; ops.weight_transpose / _split_h2 / rows_l1max answer from it when the tensor they are asked about is one of its
     layers, and fall back to their own launches otherwise (plain autograd users, the decoder head's GEMM weights)."""
 
-    def __init__(self, convs, w_amax: torch.Tensor):
+    def __init__(self, convs, w_amax: torch.Tensor, compose=()):
+        """compose: (conv5, conv1) pairs -- a 3x3 layer and the 1x1 layer that is its only reader, with nothing in between (an UpsampleSkip
+        block's last convolution and the next block's first): the prep then also holds the ONE 3x3 layer  conv1 o conv5  as an ordinary
+        layer (weights We [O,kh,kw,I] and bias be in its own storage: self.composed), made by the compose launch inside df_weight_prep.
+        DF_FUSE_U5U1=0: none."""
         import numpy as np
         self.convs = [m for m in convs if m.weight.dim() == 4]
-        dev = self.convs[0].weight.device
+        self.compose = [(m5, m1) for m5, m1 in compose] if fuse_u5u1_on() else []
+        srcs = [m for pair in self.compose for m in pair]
+        assert all(m.bias is not None for m in srcs)
+        dev = (self.convs + srcs)[0].weight.device
         ws = [ohwi(m.weight) for m in self.convs]
         assert all(w.data_ptr() == m.weight.data_ptr() for w, m in zip(ws, self.convs)), "conv weights must be channels_last (OHWI memory)"
+        assert all(ohwi(m.weight).data_ptr() == m.weight.data_ptr() for m in srcs), "conv weights must be channels_last (OHWI memory)"
         ptrs = [w.data_ptr() for w in ws] + [m.bias.data_ptr() for m in self.convs if m.bias is not None]
+        ptrs += [m.weight.data_ptr() for m in srcs] + [m.bias.data_ptr() for m in srcs]
         self.base = min(ptrs)
-        rec = np.zeros(len(ws), dtype=[("w_off", "<i8"), ("b_off", "<i8"), ("wt_off", "<i8"), ("w2_off", "<i8"), ("wt2_off", "<i8"),
+        nc = len(self.compose)
+        nl = len(ws) + nc           # ordinary records (the composed layers among them); their source records follow
+        rec = np.zeros(nl + nc, dtype=[("w_off", "<i8"), ("b_off", "<i8"), ("wt_off", "<i8"), ("w2_off", "<i8"), ("wt2_off", "<i8"),
                                        ("cout", "<i4"), ("taps", "<i4"), ("cin", "<i4"), ("split", "<i4"), ("blk0", "<i4"), ("pad", "<i4")])
         off, blk = 0, 0
         self.layer = {}
@@ -346,14 +362,42 @@ class WeightPrep:
             self.layer[w.data_ptr()] = (i, off, n, (co, kh, kw, ci), split)
             off += 3 * n if split else n
             blk += co + ci
-        self.total_blocks, self.nl = blk, len(ws)
+        comp = []
+        for k, (m5, m1) in enumerate(self.compose):
+            i = len(ws) + k
+            c5, kh, kw, ci = ohwi(m5.weight).shape
+            co = m1.weight.shape[0]
+            assert tuple(m1.weight.shape) == (co, c5, 1, 1) and co % 8 == 0 and m5.stride == (1, 1) and m1.stride == (1, 1)
+            n = co * kh * kw * ci
+            we_off, be_off = off, off + n
+            off += n + (co + 63) // 64 * 64
+            rec[i] = (we_off, be_off, off, off + n, off + 2 * n, co, kh * kw, ci, 1, blk, nl + k)
+            rec[nl + k] = ((m5.weight.data_ptr() - self.base) // 4, (m5.bias.data_ptr() - self.base) // 4, (m1.weight.data_ptr() - self.base) // 4,
+                           (m1.bias.data_ptr() - self.base) // 4, 3 * nl + k, c5, kh * kw, ci, co, 2 ** 31 - 1, 0)
+            comp.append((i, we_off, be_off, off, n, (co, kh, kw, ci)))
+            off += 3 * n
+            blk += co + ci
+        self.total_blocks, self.nl = blk, nl
         self.table = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
         self.out = torch.empty(off, dtype=torch.float32, device=dev)
-        self.norms = torch.zeros(self.nl, 3, dtype=torch.float32, device=dev)
+        self._norms = torch.zeros(3 * nl + nc, dtype=torch.float32, device=dev)     # [nl][3], then the composed layers' max |We|
+        self.norms = self._norms[:3 * nl].view(nl, 3)
         self.w_amax = w_amax
         self.by_wt = {}                 # data_ptr of a transposed view -> (layer, plane offset) for _split_h2 of the transpose
         self.bias_of = {m.bias.data_ptr(): self.layer[w.data_ptr()][0] for w, m in zip(ws, self.convs) if m.bias is not None}
+        self.comp_of, self.comp_amax = {}, {}
+        for k, ((m5, m1), (i, we_off, be_off, foff, n, shape)) in enumerate(zip(self.compose, comp)):
+            we, be = self.out[we_off:we_off + n].view(shape), self.out[be_off:be_off + shape[0]]
+            self.layer[we.data_ptr()] = (i, foff, n, shape, 1)
+            self.bias_of[be.data_ptr()] = i
+            self.comp_of[(id(m5), id(m1))] = (we, be)
+            self.comp_amax[i] = self._norms[3 * nl + k:3 * nl + k + 1]
+        self._src_ptrs = [(m, m.weight.data_ptr(), m.bias.data_ptr(), tuple(m.weight.shape)) for m in srcs]
         self._anchor = torch.empty(0, dtype=torch.float32, device=dev)
+
+    def composed(self, m5, m1):
+        """(We [O,kh,kw,I], be [O]) of the layer composed of conv5 and conv1 (views of this prep's storage, valid after run()), or None"""
+        return self.comp_of.get((id(m5), id(m1)))
 
     def stale(self) -> bool:
         """True when a conv parameter no longer lives where the table says (model.to(), load_state_dict(assign=True), p.data = ...):
@@ -365,6 +409,9 @@ class WeightPrep:
                 return True
             if m.bias is not None and m.bias.data_ptr() not in self.bias_of:
                 return True
+        for m, wp, bp, shape in self._src_ptrs:
+            if m.weight.data_ptr() != wp or m.bias is None or m.bias.data_ptr() != bp or tuple(m.weight.shape) != shape:
+                return True
         return False
 
     def run(self, w_amax: torch.Tensor):
@@ -372,7 +419,7 @@ class WeightPrep:
         import ctypes
         assert not self.stale(), "WeightPrep: a conv parameter moved since the table was built -- rebuild it (Trainer does: _wprep)"
         self.w_amax = w_amax
-        self.norms.zero_()
+        self._norms.zero_()
         call("df_weight_prep", ctypes.c_void_p(self.base), ptr(self.table), self.nl, self.total_blocks, ptr(w_amax), ptr(self.out), ptr(self.norms),
              stream())
 
@@ -389,12 +436,12 @@ class WeightPrep:
         """[hi | lo] planes (a float16 view of 2 x numel) of a layer's weights, or of its transpose as self.wt() returned it"""
         e = self.layer.get(w.data_ptr())
         if e is not None and e[4]:
-            _, off, n, _, _ = e
-            return self.out[off + n:off + 2 * n].view(torch.float16), self.w_amax
+            i, off, n, _, _ = e
+            return self.out[off + n:off + 2 * n].view(torch.float16), self.comp_amax.get(i, self.w_amax)    # (a composed layer: its own scale)
         e = self.by_wt.get(w.data_ptr())
         if e is not None and e[3]:
-            _, o2, n, _ = e
-            return self.out[o2:o2 + n].view(torch.float16), self.w_amax
+            i, o2, n, _ = e
+            return self.out[o2:o2 + n].view(torch.float16), self.comp_amax.get(i, self.w_amax)
         return None
 
     def l1(self, w: torch.Tensor, bias: Optional[torch.Tensor]):
@@ -918,10 +965,13 @@ def _wgrad3_name(stride: int) -> str:
 
 def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld_co: Optional[int] = None,
                  accumulate: bool = False, row_counts: Optional[torch.Tensor] = None, rows_per_seg: int = 0, dw_off: int = 0,
-                 want_bias: bool = False) -> Optional[torch.Tensor]:
+                 want_bias: bool = False, decompose: Optional[tuple] = None) -> Optional[torch.Tensor]:
     """dw (float memory [Cout][taps][Cin] with row pitch ld_co, starting dw_off elements in) (+)= dy^T x.
-    want_bias: also return the bias gradient sum_p dy[p, :] (fused: the kernel already stages every dy tile)."""
+    want_bias: also return the bias gradient sum_p dy[p, :] (fused: the kernel already stages every dy tile).
+    decompose = (w1, w5, b5, dw5, db5, dw1, db1): the layer is one composed of w5 [C,kh,kw,I], b5 and the 1x1 layer w1 [O,1,1,C]
+    (WeightPrep.composed); dw and the bias sum are then taken apart into the four parameter gradients (df_u5u1_decompose)."""
     dev = dw.device
+    assert decompose is None or (want_bias and ld_co is None and not accumulate and not dw_off)
     pre = x.elt == 2 and dy.elt == 2       # both operands pre-split (h2 images): wgrad3_h2p_kernel
     assert pre or (x.elt != 2 and dy.elt != 2), "a pre-split tensor meets an fp32 one in a weight gradient: unpack it (ops.h2_unpack) or keep both split"
     if pre:
@@ -976,14 +1026,25 @@ def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld
         db = _f32(dy.c, device=dev)
         call("df_conv2d_wgrad_reduce_bias", ptr(ws), splits, dy.c, taps, x.c, dw.data_ptr() + 4 * dw_off,
              taps * x.c if ld_co is None else ld_co, int(accumulate), ptr(bias_ws), ptr(db), stream())
+        _decompose(decompose, dw, db, taps)
         return db
     call("df_conv2d_wgrad_reduce", ptr(ws), splits, dy.c, taps, x.c, dw.data_ptr() + 4 * dw_off,
          taps * x.c if ld_co is None else ld_co, int(accumulate), stream())
     if want_bias:
         db = _f32(dy.c, device=dev)
         call("df_colsum_finalize", ptr(bias_ws), splits, dy.c, 1, ptr(db), 0, stream())
+        _decompose(decompose, dw, db, taps)
         return db
     return None
+
+
+def _decompose(d: Optional[tuple], dwe: torch.Tensor, dbe: torch.Tensor, taps: int) -> None:
+    if d is None:
+        return
+    w1, w5, b5, dw5, db5, dw1, db1 = d
+    O, C, I = w1.shape[0], w5.shape[0], w5.shape[-1]
+    with timed("u5u1_decompose", flops=4.0 * O * C * taps * I, tag=f"decompose {C}->{O} of 3x3 {I}->{C}"):
+        call("df_u5u1_decompose", ptr(w1), ptr(w5), ptr(b5), ptr(dwe), ptr(dbe), O, C, taps, I, ptr(dw5), ptr(db5), ptr(dw1), ptr(db1), stream())
 
 
 def upsample2x(x: DfImg, y: DfImg, align_corners: bool):
@@ -994,6 +1055,9 @@ def upsample2x(x: DfImg, y: DfImg, align_corners: bool):
 
 
 def upsample2x_bwd(dy: DfImg, dx: DfImg, align_corners: bool):
+    if dx.elt == 2:     # dx is the output gradient of a composed 3x3 layer: written pre-split, scaled by its bound (>= 4.5 max |dy|)
+        call("df_upsample2x_bwd_h2", dy, dx, int(align_corners), ptr(dx._amax), stream())
+        return
     call("df_upsample2x_bwd", dy, dx, int(align_corners), stream())
 
 

@@ -552,16 +552,26 @@ class Trainer:
             # every conv layer's transposed weights / fp16 planes / row norms of THIS step's parameters in one launch (round 4:
             # ~80 small launches per step before); DF_WPREP=0: the per-call launches
             backbone = getattr(model, "backbone", None)
+            # the composed layers (each UpsampleSkip block's last 3x3 with the next block's 1x1: unet.FastFlow3DUNet.fuse_pairs) are made
+            # by the same launch; DF_FUSE_U5U1=0: none.  DF_WPREP=0 keeps them too, in a prep of their own that holds nothing else, so
+            # that switch still changes only where the parameters' own forms come from
+            pairs = backbone.fuse_pairs() if (ops.fuse_u5u1_on() and hasattr(backbone, "fuse_pairs")) else []
             if backbone is not None and os.environ.get("DF_WPREP", "1") != "0":
                 wp = getattr(self, "_wprep", None)
-                if wp and wp.stale():      # a parameter was re-assigned since the table of raw addresses was built
+                if wp and (wp.stale() or len(wp.compose) != len(pairs)):      # a parameter was re-assigned since the table of raw addresses was built
                     wp = None
                 if wp is None:
                     convs = [m for m in backbone.modules() if isinstance(m, torch.nn.Conv2d)]
-                    wp = self._wprep = ops.WeightPrep(convs, wa) if convs else False
+                    wp = self._wprep = ops.WeightPrep(convs, wa, compose=pairs) if convs else False
                 if wp:
                     wp.run(wa)
                     ops.WPREP = wp
+            elif pairs:
+                wp = getattr(self, "_wprep_fused", None)
+                if wp is None or wp.stale():
+                    wp = self._wprep_fused = ops.WeightPrep([], wa, compose=pairs)
+                wp.run(wa)
+                ops.WPREP = wp
         try:
             return self._forward_backward_impl(batch)
         finally:

@@ -239,6 +239,34 @@ class FastFlow3DUNet(nn.Module):
                 tape.append(("conv", m4, u, 3))
         return v
 
+    def fuse_pairs(self):
+        """(last 3x3 of a block, first 1x1 of the next) for the two block boundaries where the 3x3 layer's output has that one reader and
+        nothing in between (UpsampleSkip has no normalisation and no nonlinearity): the pairs ops.WeightPrep composes into one 3x3 layer"""
+        return [(self.decoder_step1.u4_u5[1], self.decoder_step2.u1_u2[0]), (self.decoder_step2.u4_u5[1], self.decoder_step3.u1_u2[0])]
+
+    def _composed_next(self, m: UpsampleSkip, u4: torch.Tensor):
+        """(We, be) of block m's last 3x3 composed with the next block's 1x1 if this step's WeightPrep holds the layer and the pre-split
+        kernels (forward, data gradient, weight gradient) have forms for its channel pair at u4's shape; else None (DF_FUSE_U5U1=0, no
+        WeightPrep, the last block)"""
+        nxt = self.decoder_step2 if m is self.decoder_step1 else self.decoder_step3 if m is self.decoder_step2 else None
+        if nxt is None or ops.WPREP is None or not ops.h2p_on():
+            return None
+        m5, m1 = m.u4_u5[1], nxt.u1_u2[0]
+        comp = ops.WPREP.composed(m5, m1)
+        if comp is None:
+            return None
+        n, h, w, cin = u4.shape
+        cout = comp[0].shape[0]
+        base = (u4.data_ptr() + 127) // 128 * 128
+
+        def d(c, elt):
+            return DfImg(base, n, h, w, c, c, n, h * w * c, 0, elt, 0)
+        ok = (cout % 32 == 0
+              and call("df_conv2d_h2p_ok", d(cin, 2), d(cout, 0), 3, 1, ops.CONV_FWD, ops.EPI_BIAS) == 1
+              and call("df_conv2d_h2p_ok", d(cout, 2), d(cin, 2), 3, 1, ops.CONV_DGRAD, ops.EPI_BIAS) == 1
+              and call("df_conv2d_wgrad_h2p_ok", d(cin, 2), d(cout, 2), 3, 1) == 1)
+        return (m5, m1) + comp if ok else None
+
     def _conv(self, m: nn.Conv2d, x: torch.Tensor, y: DfImg, ks: int, tape: Optional[list], amax=None):
         ops.conv2d(img(x), ops.ohwi(m.weight), m.bias.detach(), y, ks, 1, amax_out=amax)
         if tape is not None:
@@ -259,11 +287,15 @@ class FastFlow3DUNet(nn.Module):
         # norm of a weight row + max |bias|; the upsampled half: max |t|, measured) -- and read by LDS-DMA
         h2d = bool(train and tape is not None and not s16 and _h2p_ok(B, 2 * h, 2 * w, 2 * lat, outc, dev)
                    and _h2p_ok(B, 2 * h, 2 * w, outc, outc, dev))
-        t = torch.empty(B, h, w, lat, **f32)
         # fp16x2 mode: ONE max |x| slot for the concatenation -- both 1x1 convolutions accumulate into it (the upsampled half is
         # made of convex combinations of t, so max |t| bounds it)
-        cat_amax = ops.amax_slot(dev) if (ops.h2_active() and not s16) else None
-        self._conv(m.u1_u2[0], a, img(t), 1, tape, amax=cat_amax)
+        if getattr(a, "_df_fused_t", None) is not None:
+            # the block in front ran its last 3x3 composed with this block's u1 (below): `a` IS t, its maximum measured into the slot
+            t, cat_amax = a, a._df_fused_t
+        else:
+            t = torch.empty(B, h, w, lat, **f32)
+            cat_amax = ops.amax_slot(dev) if (ops.h2_active() and not s16) else None
+            self._conv(m.u1_u2[0], a, img(t), 1, tape, amax=cat_amax)
         if h2d:
             w3 = ops.ohwi(m.u3.weight)
             cat_bound = ops.conv_out_bound(img(b), w3, m.u3.bias.detach(), dev, other=cat_amax)
@@ -290,6 +322,17 @@ class FastFlow3DUNet(nn.Module):
         else:
             u4 = torch.empty(B, 2 * h, 2 * w, outc, **mid)
         self._conv(m.u4_u5[0], cat, img(u4), 3, tape)
+        comp = self._composed_next(m, u4) if h2d else None
+        if comp is not None:
+            # the next block's u1 (1x1, its only reader) folded into this block's last 3x3: ONE 3x3 layer outc -> lat' straight into the next
+            # block's t; the full-width block output is never written.  max |t| goes to the slot the next block takes as its cat_amax
+            m5, m1, we, be = comp
+            tn = torch.empty(B, 2 * h, 2 * w, we.shape[0], **f32)
+            slot = ops.amax_slot(dev)
+            ops.conv2d(img(u4), we, be, img(tn), 3, 1, amax_out=slot)
+            tape.append(("fconv", m5, u4, 3, m1, we))
+            tn._df_fused_t = slot
+            return tn
         u5 = torch.empty(B, 2 * h, 2 * w, outc, **f32)
         self._conv(m.u4_u5[1], u4, img(u5), 3, tape)
         return u5
@@ -460,15 +503,44 @@ class FastFlow3DUNet(nn.Module):
                 return hold(ops.h2_empty(x.shape, dev, ops.conv_out_bound(img(dy), wt, None, dev))), wt
             return hold(torch.empty_like(x)), None
 
-        def upsample_skip_bwd(dout: torch.Tensor, a_like: Optional[torch.Tensor], db: Optional[DfImg], acc_b: bool):
+        def fused_conv_bwd(dt: torch.Tensor) -> torch.Tensor:
+            """backward of a composed layer (block k's last 3x3 with block k+1's u1; dt = the gradient of block k+1's t, pre-split):
+            -> d(u4) of block k; the four parameters' gradients come out of the composed layer's weight gradient (ops._decompose)"""
+            _, m5, x5, _, m1, we = pop("fconv")
+            wte = ops.weight_transpose(we)
+            du4 = hold(ops.h2_empty(x5.shape, dev, ops.conv_out_bound(img(dt), wte, None, dev)))
+            ops.conv2d(img(dt), wte, None, img(du4), 3, 1, mode=ops.CONV_DGRAD)
+
+            def wgrad():
+                w5, w1 = ops.ohwi(m5.weight), ops.ohwi(m1.weight)
+                dwe = hold(torch.empty_like(we))
+                dw5, dw1 = torch.empty_like(w5), torch.empty_like(w1)
+                db5, db1 = torch.empty_like(m5.bias.detach()), torch.empty_like(m1.bias.detach())
+                ops.conv2d_wgrad(img(x5), img(dt), 3, 1, dwe, want_bias=True,
+                                 decompose=(w1, w5, m5.bias.detach(), dw5, db5, dw1, db1))
+                grads[m5.weight], grads[m5.bias] = dw5.permute(0, 3, 1, 2), db5
+                grads[m1.weight], grads[m1.bias] = dw1.permute(0, 3, 1, 2), db1
+
+            if ops.SIDE is None:
+                wgrad()
+            else:
+                with ops.SIDE.fork():
+                    wgrad()
+            return du4
+
+        def upsample_skip_bwd(dout: torch.Tensor, db: Optional[DfImg], acc_b: bool, dout_is_du4: bool = False):
             # reverse of: u1(a)->t ; up(t)->cat[:lat] ; u3(b)->cat[lat:] ; u4(cat) ; u5(u4)
             # (bf16-storage mode: u4 and cat were bfloat16 -> du4 is bfloat16 as well, so both 3x3 weight gradients see bf16
             #  x and dy; dcat stays fp32 for the 1x1 / upsample kernels behind it.  Pre-split mode: the same with h2 images.)
-            # a_like: the tensor whose layout d(a) takes (the u4 of the block in front: bf16 / h2 / fp32), None = fp32
-            # -> d(a) [the block's input gradient: the output gradient of the block in front]
-            _, m5, x5, _ = tape[-1]
-            du4, wt5 = grad_like(x5, dout, m5)
-            plain_conv_bwd(dout, img(du4), False, wt5)
+            # dout_is_du4: the block's last 3x3 ran composed with the next block's u1, whose backward (fused_conv_bwd) already produced d(u4)
+            # -> (d(a) [the block's input gradient: the output gradient of the block in front], False), or across a composed boundary
+            #    (d(u4) of the block in front, True)
+            if dout_is_du4:
+                du4 = dout
+            else:
+                _, m5, x5, _ = tape[-1]
+                du4, wt5 = grad_like(x5, dout, m5)
+                plain_conv_bwd(dout, img(du4), False, wt5)
             _, m4, x4, _ = tape[-1]
             dcat = hold(torch.empty(x4.shape, **f32))
             plain_conv_bwd(du4, img(dcat), False)
@@ -479,14 +551,23 @@ class FastFlow3DUNet(nn.Module):
             if db is None:
                 retained["dskip"] = (dcat, lat)
             _, h, w, lat_ = pop("up")
-            dt = hold(torch.empty(B, h, w, lat, **f32))
             dci = img(dcat, lat, 0)
+            if tape[-1][0] == "fconv":
+                # t came out of a composed 3x3 layer: dt is that layer's dy, read by the pre-split data- and weight-gradient kernels ->
+                # written pre-split by the bilinear backward itself, scaled by the bound below (4.5 max |dcat|)
+                dt = hold(ops.h2_empty((B, h, w, lat), dev, ops.h2_bound(ops.amax_of(dci, dev), slack=4.5)))
+                ops.upsample2x_bwd(dci, img(dt), self.align_corners)
+                return fused_conv_bwd(dt), True
+            dt = hold(torch.empty(B, h, w, lat, **f32))
             ops.upsample2x_bwd(dci, img(dt), self.align_corners)
             if getattr(dci, "_amax", None) is not None:
                 # every input pixel of the bilinear x2 receives a total weight <= 2 per axis (4 in all; 4.5 covers align_corners
                 # = True): max |dt| <= 4.5 max |dcat| -- a bound without a pass over dt, for the 1x1 data / weight gradients behind
                 dt._df_amax = (ops.h2_bound(dci._amax, slack=4.5), ver(dt))
             _, m1, xa, ks = pop("conv")
+            # a_like: the tensor whose layout d(a) takes = the u4 of the block in front, the input of the "conv" entry that now ends the
+            # tape (bf16 / h2 / fp32); the first block has the encoder in front: fp32
+            a_like = tape[-1][2] if tape[-1][0] == "conv" else None
             wt1 = None
             if a_like is not None and _is_h2(a_like):
                 wt1 = ops.weight_transpose(ops.ohwi(m1.weight))
@@ -494,7 +575,7 @@ class FastFlow3DUNet(nn.Module):
             else:
                 dA = hold(torch.empty(xa.shape, dtype=torch.float32 if a_like is None else a_like.dtype, device=dev))
             self._conv_bwd(m1, img(xa), img(dt), 1, 1, img(dA), False, grads, wt=wt1)
-            return dA
+            return dA, False
 
         # the gradient a block receives at its output (du, dT, dS) is bfloat16 when that block kept its u4 in bfloat16 (bf16-
         # storage mode): its two consumers are then the bf16-tile data- and weight-gradient kernels of the block's second conv
@@ -536,11 +617,12 @@ class FastFlow3DUNet(nn.Module):
         else:
             acc_b = True
         # conv entries of a block in tape order: u1, u3, u4, u5 -> from the end: u5 (x = u4), u4, u3, u1
-        dT = upsample_skip_bwd(du, conv_x(5), None if sparse_input_grad else img(dbstar), acc_b)   # step3 (4 entries), step2.u5 (x = u4)
+        # (across a composed boundary dT / dS is the d(u4) of the block in front, and that block starts behind its last 3x3)
+        dT, comp32 = upsample_skip_bwd(du, None if sparse_input_grad else img(dbstar), acc_b)   # step3
         dF = hold(torch.empty(B, H // 2, W // 2, 128, **f32))   # d(fstar)
-        dS = upsample_skip_bwd(dT, conv_x(5), img(dF), False)    # (tape shrank by one block) step1.u5
+        dS, comp21 = upsample_skip_bwd(dT, img(dF), False, comp32)    # step2
         dL = hold(torch.empty(B, H // 4, W // 4, 256, **f32))   # d(lstar)
-        dR = upsample_skip_bwd(dS, None, img(dL), False)         # d(rstar) [B,H/8,W/8,512], fp32: the encoder's BatchNorm backward reads it
+        dR, _ = upsample_skip_bwd(dS, img(dL), False, comp21)         # d(rstar) [B,H/8,W/8,512], fp32: the encoder's BatchNorm backward reads it
         if phase is not None:   # the four decoder steps are complete: their gradients can leave (optim.GradSink)
             phase([p for m in (self.decoder_step1, self.decoder_step2, self.decoder_step3, self.decoder_step4)
                    for p in m.parameters()])

@@ -360,6 +360,10 @@ int df_upsample2x_bf16(df_img x, df_img y, int align_corners, void* stream); /* 
 /* bilinear x2 (PyTorch F.interpolate semantics, align_corners selectable), forward and backward */
 int df_upsample2x(df_img x, df_img y, int align_corners, void* stream);
 int df_upsample2x_bwd(df_img dy, df_img dx, int align_corners, void* stream);
+/* ... into a pre-split dx (dx.elt = 2; "PRE-SPLIT tensors" below), scaled by *dx_bound >= max |dx| (4.5 max |dy| always holds): the
+ * planes df_h2_pack makes of df_upsample2x_bwd's output with that bound, bit for bit -- for a dx that is the output gradient of a
+ * composed 3x3 layer (df_weight_prep), whose consumers are the pre-split data- and weight-gradient kernels */
+int df_upsample2x_bwd_h2(df_img dy, df_img dx, int align_corners, const float* dx_bound, void* stream);
 
 /* ---- PRE-SPLIT ("h2") tensors, round 4: the operands of the fp16x2 kernels written split by their PRODUCERS -------------------
  * df_img.elt = 2: the tensor has the geometry of its fp32 form (4 bytes per element: ld / img_stride / grp_off unchanged), but per
@@ -410,6 +414,18 @@ int df_h2_bound(float* out, const float* a, const float* l1, const float* b, con
  * norms [nlayers][3] = (max row L1 of w, of w^T, max |bias|), zero-initialised by the caller; w_amax = max |p| over the arena */
 int df_weight_prep(const float* params, const void* table, int nlayers, int total_blocks, const float* w_amax, float* out, float* norms,
                    void* stream);
+/* COMPOSED layers (unless DF_FUSE_U5U1=0): a record with pad > 0 is the 3x3 layer  We[o][tap][i] = sum_c W1[o][c] W5[c][tap][i],
+ * be[o] = sum_c W1[o][c] b5[c] + b1[o]  of an UpsampleSkip block's last 3x3 convolution (W5, b5) and the next block's 1x1 (W1, b1), which
+ * is its only reader [REF deflow.py:32].  Its w_off / b_off address `out` (We [O][taps][I] and be, written by a compose launch inside
+ * df_weight_prep before the forms are made); tab[pad], a record past the nlayers ordinary ones, names the sources: w_off = W5, b_off =
+ * b5, wt_off = W1, w2_off = b1 (elements in `params`), wt2_off = the index in `norms` (past [nlayers][3], zero-initialised with them)
+ * of the slot that receives max |We| -- the scale of the composed layer's planes --, cout = C, taps, cin = I, split = O (O % 8 == 0).
+ * df_u5u1_decompose: the four parameter gradients from the composed layer's weight gradient dwe [O][taps][I] and bias sum dbe [O]:
+ *   dw5[c][tap][i] = sum_o W1[o][c] dwe[o][tap][i]      dw1[o][c] = sum_{tap,i} dwe[o][tap][i] W5[c][tap][i] + dbe[o] b5[c]
+ *   db5[c] = sum_o W1[o][c] dbe[o]                      db1 = dbe
+ * (O, C % 16 == 0, I % 64 == 0; sums in ascending index order in double, no float atomics: bit-reproducible) */
+int df_u5u1_decompose(const float* w1, const float* w5, const float* b5, const float* dwe, const float* dbe, int O, int C, int taps,
+                      int I, float* dw5, float* db5, float* dw1, float* db1, void* stream);
 
 /* ------------------------------------------------------- point decoder (A6-A10) --------
  * Replaces ConvGRUDecoder / LinearDecoder forward_single ([REF decoder.py:72-199]): integer
