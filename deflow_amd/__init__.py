@@ -10,3 +10,4 @@ from .ground import GroundSegmenter  # noqa: F401
 from .metrics_device import DeviceMetrics  # noqa: F401
 from .sweeps import SweepFlow  # noqa: F401
 from .submit import SubmitFlow  # noqa: F401
+from .augment import Augmenter  # noqa: F401

@@ -14,7 +14,11 @@ the files node-local as 1_train.sh does); ``train_data=synthetic`` draws seeded 
 
 ``metrics_impl=device`` (default ``host``) accumulates the per-epoch validation line on the GPU (deflow_amd/metrics_device.py) instead of
 per sample on the host.  The line is then ``DeviceMetrics.summary()``, weighted by batch size; that equals the host path's plain mean
-over batches when all batches are equal-sized and carry every key.  The key is not a hyper-parameter and is never saved."""
+over batches when all batches are equal-sized and carry every key.  The key is not a hyper-parameter and is never saved.
+
+``augment=true`` augments every training batch on the GPU (deflow_amd/augment.py: flip, yaw, height, jitter, point dropout; one launch, a pure
+function of (seed, epoch, sample id, row), so a resumed run repeats exactly); ``aug_flip_x_p``, ``aug_flip_y_p``, ``aug_yaw_deg``,
+``aug_height``, ``aug_jitter_sigma`` and ``aug_drop_p`` are its arguments.  Validation batches are never augmented."""
 from __future__ import annotations
 
 import ast
@@ -34,6 +38,10 @@ DEFAULTS: Dict[str, Any] = {
     # online cluster labels for loss_fn=seflowLoss (cluster.dynamic_cluster_labels): cluster_labels=online computes pc0_dynamic /
     # pc1_dynamic inside the step from the per-point dynamic flag; the other four keys are that call's arguments (its defaults)
     "cluster_labels": "", "cluster_eps": 0.7, "cluster_min_points": 4, "cluster_min_size": 20, "cluster_min_dynamic_frac": 0.3,
+    # augment=true: every TRAINING batch goes through augment.Augmenter (csrc/augment.hip) before the step; the aug_* keys are its
+    # arguments (UNPINNED magnitudes: DESIGN.md section 6h).  The Philox key is (seed, epoch); validation batches are never augmented
+    "augment": False, "aug_flip_x_p": 0.5, "aug_flip_y_p": 0.5, "aug_yaw_deg": 0.0, "aug_height": 0.2, "aug_jitter_sigma": 0.01,
+    "aug_drop_p": 0.0,
     "stage_dir": "", "checkpoint": "", "save_checkpoint": "", "seed": 20240116, "wandb_mode": "disabled", "slurm_id": "", "log_every": 50,   # Lightning's log_every_n_steps default; each log line syncs
 }
 
@@ -123,6 +131,10 @@ def parse_overrides(argv: List[str]) -> Dict[str, Any]:
         raise SystemExit(f"unknown cluster_labels {cfg['cluster_labels']!r} (online)")
     if cfg["cluster_labels"] == "online" and cfg["loss_fn"] != "seflowLoss":
         raise SystemExit("cluster_labels=online computes the labels of loss_fn=seflowLoss: set loss_fn=seflowLoss")
+    if str(cfg["augment"]).lower() not in ("1", "0", "true", "false"):
+        raise SystemExit(f"augment must be true or false, got {cfg['augment']!r}")
+    cfg["augment"] = augment_on(cfg)
+    augmenter_from(cfg)
     gfs = cfg.pop("_grid_feature_size", None)
     if gfs is not None and list(gfs) != grid_from(cfg):
         raise SystemExit(f"model.target.grid_feature_size={gfs} does not match voxel_size / point_cloud_range ({grid_from(cfg)})")
@@ -140,6 +152,22 @@ def cluster_args(cfg):
         return None
     return {"eps": float(cfg["cluster_eps"]), "min_points": int(cfg["cluster_min_points"]),
             "min_cluster_size": int(cfg["cluster_min_size"]), "min_dynamic_frac": float(cfg["cluster_min_dynamic_frac"])}
+
+
+def augment_on(cfg) -> bool:
+    return str(cfg.get("augment", False)).lower() in ("1", "true")
+
+
+def augmenter_from(cfg):
+    """the Augmenter of the command line's keys, None unless augment=true; bad values end the command before anything runs"""
+    if not augment_on(cfg):
+        return None
+    from deflow_amd.augment import Augmenter
+    try:
+        return Augmenter(int(cfg["seed"]), flip_x_p=cfg["aug_flip_x_p"], flip_y_p=cfg["aug_flip_y_p"], yaw_deg=cfg["aug_yaw_deg"],
+                         height=cfg["aug_height"], jitter_sigma=cfg["aug_jitter_sigma"], drop_p=cfg["aug_drop_p"])
+    except (ValueError, TypeError) as e:
+        raise SystemExit(str(e))
 
 
 def build_model(cfg):
@@ -218,9 +246,12 @@ def main(argv=None):
                     sb["pc0_dufo"], sb["pc1_dufo"] = l0 > 0, l1 > 0
                 else:
                     sb["pc0_dynamic"], sb["pc1_dynamic"] = l0, l1
+            if augmenter is not None:               # the sample ids of synthetic pairs: the seed each pair was drawn with
+                sb["timestamp"] = list(range(seed, seed + B))
             yield sb
 
     steps_per_epoch = max(1, int(cfg["pairs_per_epoch"]) // (B * world))
+    augmenter = augmenter_from(cfg)
     train_loader = val_loader = None
     if cfg["train_data"] != "synthetic":
         train_loader, train_sampler = scene_loader(str(cfg["train_data"]), shuffle=True)
@@ -236,6 +267,9 @@ def main(argv=None):
         if train_loader is not None:
             train_sampler.set_epoch(epoch)
         for batch in (train_loader if train_loader is not None else synthetic_epoch(epoch)):
+            if augmenter is not None:
+                # one launch outside any capture: a captured step takes the augmented tensors as its static inputs / copies them in
+                batch = augmenter(batch, augmenter.sample_ids_of(batch), epoch)
             if use_graph:
                 # graph=true: the step is captured once as HIP graph(s) on the first batch (capture restores parameters, Adam
                 # state and BatchNorm buffers after its warm-up launches: the replay below IS the first training step) and

@@ -807,6 +807,41 @@ int64_t df_submit_body_stride(int N);
 int df_submit_pack(const float* flow_est, const uint8_t* dynamic, const int32_t* row_of, const int32_t* kept, int B, int N, int version,
                    uint8_t* body, void* stream);
 
+/* ------------------------------------------------------------------ training augmentation of a padded batch ----
+ * UNPINNED: upstream's later releases ship RandomFlip / RandomHeight / RandomJitter dataset transforms; the names are recalled, their
+ * magnitudes, probabilities and distributions are not (hence arguments), and the jitter bell and the random stream are this project's own
+ * (DESIGN.md section 6h).  Everything is a pure function of (seed, epoch, sample id, row): it does not depend on the batch a sample lands in,
+ * on its position there, on the world size or on the reader; nothing is read back.
+ *   words       Philox4x32-10, standard constants; key (seed & 0xffffffff, epoch & 0xffffffff); counter (id_lo, id_hi, row, purpose), id the
+ *               sample's int64 id as two u32.  u(w) = (w >> 8) 2^-24.
+ *   per sample  row = 0xffffffff, purpose = 0, words w0..w3: sx = u(w0) < flip_x_p ? -1 : 1; sy = u(w1) < flip_y_p ? -1 : 1;
+ *               theta = (2 u(w2) - 1) yaw_max, the product in double (radians); dz = fp32((2 u(w3) - 1) height_max).
+ *               c, s = the fp32 roundings of cos / sin of theta evaluated in double.  A: p' = L p + a, L = Rz(theta) diag(sx, sy, 1),
+ *               a = (0, 0, dz).
+ *   per row     purpose = 1 (pc0 rows) or 2 (pc1 rows), words w0..w3: the jitter of axis k is fp32(n_k sj), n_k = the sum of the four
+ *               bytes of w_k minus 510 (an Irwin-Hall bell of unit standard deviation once divided by 147.8, at most 3.46 of them) and
+ *               sj = fp32(jitter_sigma / 147.8) formed on the host in double; the row is dropped -- three fp32 NaNs of pattern
+ *               0x7FC00000, in place, no compaction -- when u(w3) < drop_p.  Input NaN propagates.
+ *   fp32 order  x1 = sx x, y1 = sy y; x2 = c x1 - s y1, y2 = s x1 + c y1 (each may be one FMA), z2 = z + dz; then + jitter (an FMA).
+ *               yaw_max == 0: x2 = x1, y2 = y1; jitter_sigma == 0: nothing is added: flips and height are bit-exact.  The per-row
+ *               words are drawn only when jitter_sigma > 0 or drop_p > 0.
+ *   flow        [B,N0,3], nullable with flow_out: flow' = L flow, the linear part only.
+ *   T, poses    [B,4,4] f32 each, nullable with their outputs: T' = A T A^-1, pose' = pose A^-1, composed in double with the double
+ *               cos / sin and rounded to fp32 once; A^-1 has linear part diag(sx, sy, 1) Rz(-theta) and translation (0, 0, -dz).
+ * df_augment: one launch for both clouds (separate padded lengths N0, N1), the flow and the matrices.  A cloud whose N % 4 == 0 and whose
+ *   buffers are 16-byte aligned moves 16 bytes per access; any other takes 4-byte accesses.  The inputs are not modified (an output that
+ *   is its input returns DF_E_ARG).
+ * df_augment_params: params [B,8] f32 = (sx, sy, c, s, dz, theta, 0, 0) per sample, for logging and tests.
+ * 1 <= B <= 65535, N0, N1 >= 1, B * N < 2^31: DF_E_SHAPE; NULL required buffers, an optional buffer without its output, a probability
+ * outside [0, 1], a negative or non-finite magnitude: DF_E_ARG.  No launch then.  The entries never allocate or synchronise; no
+ * atomics, two runs are bit-identical. */
+int df_augment(const float* pc0, const float* pc1, const float* flow /*nullable*/, const int64_t* sample_ids, int B, int N0, int N1,
+               int64_t seed, int64_t epoch, float flip_x_p, float flip_y_p, float yaw_max, float height_max, float jitter_sigma,
+               float drop_p, const float* T /*nullable*/, const float* pose0 /*nullable*/, const float* pose1 /*nullable*/, float* pc0_out,
+               float* pc1_out, float* flow_out, float* T_out, float* pose0_out, float* pose1_out, void* stream);
+int df_augment_params(const int64_t* sample_ids, int B, int64_t seed, int64_t epoch, float flip_x_p, float flip_y_p, float yaw_max,
+                      float height_max, float jitter_sigma, float drop_p, float* params, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
