@@ -11,3 +11,4 @@ from .metrics_device import DeviceMetrics  # noqa: F401
 from .sweeps import SweepFlow  # noqa: F401
 from .submit import SubmitFlow  # noqa: F401
 from .augment import Augmenter  # noqa: F401
+from .render import flow_vectors, render_rows  # noqa: F401

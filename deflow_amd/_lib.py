@@ -186,6 +186,8 @@ _SIGS = {
     "df_submit_pack": [P, P, P, P, I, I, I, P, P],
     "df_augment": [P, P, P, P, I, I, I, L, L, F, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P],
     "df_augment_params": [P, I, L, L, F, F, F, F, F, F, P, P],
+    "df_render_splat": [P, P, P, P, I, I, F, F, F, I, I, F, I, P, P],
+    "df_render_resolve": [P, I, I, I, I, I, P, P],
     "df_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
     "df_adam_step_dev": [P, P, P, P, L, F, F, F, F, P, F, P],
 }

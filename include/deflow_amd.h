@@ -842,6 +842,40 @@ int df_augment(const float* pc0, const float* pc1, const float* flow /*nullable*
 int df_augment_params(const int64_t* sample_ids, int B, int64_t seed, int64_t epoch, float flip_x_p, float flip_y_p, float yaw_max,
                       float height_max, float jitter_sigma, float drop_p, float* params, void* stream);
 
+/* ------------------------------------------------------------------ bird's-eye-view flow images (the vis command) ----
+ * UNPINNED: upstream's viewer (tools/visualization.py) is an interactive window whose source is absent; its colour wheel and camera cannot be
+ * compared, so this definition is the project's own.  Every floating-point step below is ONE correctly rounded fp32
+ * operation (written fp32(.)), never contracted, so that numpy float32 restates the image byte for byte.
+ *   view          (xmin, ymin, inv_res), image W x H.  For a row (x, y, z): fx = floor(fp32(fp32(x - xmin) inv_res)), fy = floor(fp32(fp32(y -
+ *                 ymin) inv_res)); the row is drawn when 0 <= fx < W and 0 <= fy < H (compared on the floats); px = fx, py = H - 1 - fy: x to
+ *                 the right, y up, line 0 on top
+ *   rows          i < count[b] (clamped to [0, N]).  A row is skipped when cls == 0 or when any of its six floats (point and vector) is not
+ *                 finite.  cls == 1 draws the colour of its vector; every other non-zero cls (2 by convention: ground) draws grey (128, 128, 128)
+ *   colour(vx, vy, vmax)   m = sqrt(fp32(fp32(vx vx) + fp32(vy vy))); s = min(fp32(m / vmax), 1); a = fp32(|vx| + |vy|).  The hue is the
+ *                 diamond angle t in [0, 4]: a == 0: t = 0; else
+ *                     vy >= 0 and vx >= 0: t = fp32(vy / a)                      vy >= 0 and vx < 0: t = fp32(1 + fp32(-vx / a))
+ *                     vy <  0 and vx <  0: t = fp32(2 + fp32(-vy / a))           vy <  0 and vx >= 0: t = fp32(3 + fp32(vx / a))
+ *                 (-0.0 >= 0 holds).  h6 = fp32(1.5 t); k = floor(h6), f = fp32(h6 - k), k == 6 counts as 0; p = fp32(1 - s),
+ *                 q = fp32(1 - fp32(s f)), u = fp32(1 - fp32(s fp32(1 - f))); (R, G, B) for k = 0 .. 5: (1, u, p), (q, 1, p), (p, 1, u),
+ *                 (p, q, 1), (u, p, 1), (1, p, q); each channel c becomes the byte floor(fp32(fp32(c 255) + 0.5)).  +x is red, +y yellow-green,
+ *                 -x cyan, -y violet; the zero vector is white, |v| >= vmax fully saturated
+ *   word          u64 = [cls == 1 : 1 bit][top 31 bits of key(z)][R G B : 24 bits][0xFF], key(z) = the order-preserving unsigned form of z's
+ *                 bits (negative: all bits inverted; otherwise the sign bit set).  Never 0.  The row writes its word into the (2r+1)^2 square
+ *                 of pixels around (px, py), clipped to the image, with a 64-bit integer atomic max: coloured rows win over grey ones, within
+ *                 a class the highest row wins, equal heights (to 31 bits) are decided by the colour bits.  A maximum does not depend on the
+ *                 order it is taken in: two calls are bit-identical
+ * df_render_splat: points, vec [B,N,3] f32, cls [B,N] u8, count [B] i32 -> image u64 [B,H,W], which the CALLER zeroes beforehand (0 = empty).
+ * df_render_resolve: image -> scanlines u8 [B, H, 1 + 3W]: per line a 0 byte (PNG filter type None), then R G B per pixel; an empty word gives
+ *   bg_rgb (0xRRGGBB).  legend = L > 0 draws a colour-wheel disc over whatever lies under it: centre (cx, cy) = (W - 3 - L, L + 2), and a
+ *   pixel with integers dx = x - cx, dy = y - cy, dx dx + dy dy <= L L gets colour(dx, -dy, L).  Every output byte is written exactly once.
+ * 1 <= B <= 65535, N >= 1, B N < 2^31, 1 <= W, H <= 4096, B H (1 + 3W) < 2^31: violations return DF_E_SHAPE.  NULL buffers, a radius outside
+ * [0, 4], vmax or inv_res not positive and finite, a non-finite xmin / ymin, bg_rgb outside [0, 0xFFFFFF], legend < 0 or 2 L + 5 > min(W, H)
+ * return DF_E_ARG.  image 8-byte, scanlines 4-byte aligned (DF_E_ALIGN).  No launch then.  The grids come from N, W, H, never from a device
+ * value; the entries never allocate or synchronise and read nothing back. */
+int df_render_splat(const float* points, const float* vec, const uint8_t* cls, const int32_t* count, int B, int N, float xmin, float ymin,
+                    float inv_res, int W, int H, float vmax, int radius, uint64_t* image, void* stream);
+int df_render_resolve(const uint64_t* image, int B, int W, int H, int bg_rgb, int legend, uint8_t* scanlines, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
