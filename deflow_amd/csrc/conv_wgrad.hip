@@ -1,6 +1,10 @@
 // Weight gradients of the BEV convolutions (split from conv.hip in round 6; kernels unchanged): dw[co, tap, ci] = sum_m dy[m, co] * x[pix(m, tap), ci]
 // for every kernel size / stride / storage form of the UNet ([REF decoder.py:202-220] differentiated w.r.t. the Conv2d weights),
 // the split-K reductions and the weight transpose.
+// Layout: the kernels; then the host part.  Every launch entry point there is (1) its own argument checks, (2) wgrad_params(), the one
+// place that fills the kernel argument (buffer extents, chunks per split, DF_WGRAD_XCD), and (3) its choice of kernel instance and LDS
+// bytes; every *_splits query is a target, a tile count and a chunk width given to wgrad_split_count(); every *_ok query ends in
+// dma_addressable().  A new form is one _ok, one _splits and one launch line.
 #include "conv_common.h"
 
 namespace {
@@ -2162,8 +2166,9 @@ static int launch_wgrad_dma(K kern, dim3 grid, size_t lds_bytes, hipStream_t s, 
   return DF_OK;
 }
 
-__global__ void wgrad_reduce_kernel(const float* __restrict__ ws, int splits, int64_t per_split, int row_len,
-                                    float* __restrict__ dw, int64_t ld_co, int accumulate) {
+// dw[co][r] (+)= sum over the splits of ws[k][i], i = co * row_len + r: one thread per element, four loads in flight
+__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ ws, int splits, int64_t per_split, int row_len,
+                                                  float* __restrict__ dw, int64_t ld_co, int accumulate) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= per_split) return;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -2179,6 +2184,11 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, int splits, in
   const int64_t co = i / row_len, r = i - co * row_len;
   float* o = dw + co * ld_co + r;
   *o = accumulate ? (*o + s) : s;
+}
+
+__global__ void wgrad_reduce_kernel(const float* __restrict__ ws, int splits, int64_t per_split, int row_len,
+                                    float* __restrict__ dw, int64_t ld_co, int accumulate) {
+  wgrad_reduce_body(ws, splits, per_split, row_len, dw, ld_co, accumulate);
 }
 
 // ... and the bias partials of the same split-K pass in the SAME launch (round 4, second session: a conv layer's weight gradient
@@ -2209,21 +2219,7 @@ __global__ void wgrad_reduce_bias_kernel(const float* __restrict__ ws, int split
     }
     return;
   }
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= per_split) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int k = 0;
-  for (; k + 4 <= splits; k += 4) {
-    s0 += ws[(int64_t)k * per_split + i];
-    s1 += ws[(int64_t)(k + 1) * per_split + i];
-    s2 += ws[(int64_t)(k + 2) * per_split + i];
-    s3 += ws[(int64_t)(k + 3) * per_split + i];
-  }
-  for (; k < splits; ++k) s0 += ws[(int64_t)k * per_split + i];
-  const float s = (s0 + s1) + (s2 + s3);
-  const int64_t co = i / row_len, r = i - co * row_len;
-  float* o = dw + co * ld_co + r;
-  *o = accumulate ? (*o + s) : s;
+  wgrad_reduce_body(ws, splits, per_split, row_len, dw, ld_co, accumulate);
 }
 
 __global__ void weight_transpose_kernel(const float* __restrict__ w, float* __restrict__ wt, int cout, int taps,
@@ -2259,20 +2255,53 @@ static inline int wgrad_chunk(int ksize, int stride) {   // output pixels per ch
   return (ksize == 3 && stride == 2 && wgrad_ring_s2()) ? 16 : 32;
 }
 
-extern "C" int df_conv2d_wgrad_splits(df_img x, df_img dy, int ksize, int stride) {
-  const int P = wgrad_chunk(ksize, stride);
-  const int tiles = wgrad_use_1x1(ksize, dy.c) ? ((x.c + wgrad_cit(x.c) - 1) / wgrad_cit(x.c)) * (dy.c / 128)
-                                               : ((x.c + 63) / 64) * (dy.c / 64);
-  const int64_t chunks = (int64_t)dy.n * dy.h * ((dy.w + P - 1) / P);
-  static const int target = getenv("DF_WGRAD_BLOCKS") ? atoi(getenv("DF_WGRAD_BLOCKS")) : 512;  // = one resident round at 2 workgroups per CU (1024: +0.6 ms of partial-sum traffic, 768: a ragged second round)
-  const int tgt = wgrad_ring_depth(ksize, stride) == 3 ? target / 2 : target;   // one resident workgroup per CU
-  int64_t splits = (tgt + tiles - 1) / tiles;
+// ---- the host-side plan every entry point below shares ----
+// bytes from a descriptor's first element to behind its last one
+static inline int64_t img_extent_bytes(const df_img& d, int elt_bytes) {
+  return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * elt_bytes;
+}
+// a DMA-fed kernel can address the whole tensor through one buffer descriptor (call after img_ok: grp_size > 0)
+static inline bool dma_addressable(const df_img& d, int elt_bytes) {
+  return d.img_stride >= 0 && d.grp_off >= 0 && img_extent_bytes(d, elt_bytes) < (int64_t)DMA_BAD;
+}
+// chunks = output-row segments of P pixels
+static inline int64_t wgrad_chunks(const df_img& dy, int P) { return (int64_t)dy.n * dy.h * ((dy.w + P - 1) / P); }
+// split-K count: `target` workgroups over `tiles` (ci, co) tiles, at most one split per chunk, every split non-empty
+static inline int wgrad_split_count(int target, int tiles, int64_t chunks) {
+  int64_t splits = (target + tiles - 1) / tiles;
   if (splits > chunks) splits = chunks;
   if (splits < 1) splits = 1;
-  // make every split non-empty
   const int64_t cps = (chunks + splits - 1) / splits;
-  splits = (chunks + cps - 1) / cps;
-  return (int)splits;
+  return (int)((chunks + cps - 1) / cps);
+}
+// Fills EVERY field of the kernel argument: the DMA forms' values (buffer extents at elt_bytes per element, no row list, fp32 MFMA
+// operands); df_conv2d_wgrad_mp adjusts the three it differs in afterwards.  DF_E_SHAPE when the chunks do not fit `splits`.
+static int wgrad_params(WgradParams& p, const df_img& x, const df_img& dy, int elt_bytes, int stride, int pad, int P, float* ws,
+                        int splits, float* bias_ws, const float* amax_x = nullptr, const float* amax_dy = nullptr) {
+  p = WgradParams{};
+  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = nullptr; p.rows_per_seg = 1; p.bias_ws = bias_ws; p.bf16 = 0;
+  p.amax_x = amax_x; p.amax_dy = amax_dy;
+  p.stride = stride; p.pad = pad; p.K = x.c; p.N = dy.c;
+  p.x_bytes = (unsigned)img_extent_bytes(x, elt_bytes);
+  p.dy_bytes = (unsigned)img_extent_bytes(dy, elt_bytes);
+  p.chunks_per_row = (dy.w + P - 1) / P;
+  const int64_t chunks = wgrad_chunks(dy, P);
+  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
+  p.total_chunks = (int)chunks;
+  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
+  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
+  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
+  p.xcd_map = xcd_map;
+  return DF_OK;
+}
+static inline dim3 wgrad_grid64(const df_img& x, const df_img& dy, int splits) { return dim3((x.c + 63) / 64, dy.c / 64, splits); }
+
+extern "C" int df_conv2d_wgrad_splits(df_img x, df_img dy, int ksize, int stride) {
+  const int tiles = wgrad_use_1x1(ksize, dy.c) ? ((x.c + wgrad_cit(x.c) - 1) / wgrad_cit(x.c)) * (dy.c / 128)
+                                               : ((x.c + 63) / 64) * (dy.c / 64);
+  static const int target = getenv("DF_WGRAD_BLOCKS") ? atoi(getenv("DF_WGRAD_BLOCKS")) : 512;  // = one resident round at 2 workgroups per CU (1024: +0.6 ms of partial-sum traffic, 768: a ragged second round)
+  const int tgt = wgrad_ring_depth(ksize, stride) == 3 ? target / 2 : target;   // one resident workgroup per CU
+  return wgrad_split_count(tgt, tiles, wgrad_chunks(dy, wgrad_chunk(ksize, stride)));
 }
 
 extern "C" int df_conv2d_wgrad(df_img x, df_img dy, int ksize, int stride, int pad, float* ws, int splits,
@@ -2289,33 +2318,13 @@ extern "C" int df_conv2d_wgrad_mp(df_img x, df_img dy, int ksize, int stride, in
   DF_REQUIRE((ksize == 1 && stride == 1 && pad == 0) || (ksize == 3 && pad == 1 && (stride == 1 || stride == 2)), DF_E_SHAPE);
   DF_REQUIRE(dy.h == (x.h + 2 * pad - ksize) / stride + 1 && dy.w == (x.w + 2 * pad - ksize) / stride + 1, DF_E_SHAPE);
   WgradParams p;
-  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = row_counts; p.rows_per_seg = rows_per_seg > 0 ? rows_per_seg : 1;
-  p.bias_ws = bias_ws;
+  DF_REQUIRE(wgrad_params(p, x, dy, 4, stride, pad, wgrad_chunk(ksize, stride), ws, splits, bias_ws) == DF_OK, DF_E_SHAPE);
+  p.row_counts = row_counts;
+  if (rows_per_seg > 0) p.rows_per_seg = rows_per_seg;
   p.bf16 = mfma_bf16 != 0;
-  p.stride = stride; p.pad = pad; p.K = x.c; p.N = dy.c;
-  p.x_bytes = p.dy_bytes = 0;
-  {
-    static const int no_dma = getenv("DF_CONV_NO_DMA") ? atoi(getenv("DF_CONV_NO_DMA")) : 0;
-    auto extent = [](const df_img& d) {
-      return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-    };
-    const int64_t ex = extent(x), ey = extent(dy);
-    if (!no_dma && x.img_stride >= 0 && dy.img_stride >= 0 && x.grp_off >= 0 && dy.grp_off >= 0 &&
-        ex < (int64_t)DMA_BAD && ey < (int64_t)DMA_BAD) {
-      p.x_bytes = (unsigned)ex;
-      p.dy_bytes = (unsigned)ey;
-    }
-  }
-  const int P = wgrad_chunk(ksize, stride);
-  p.chunks_per_row = (dy.w + P - 1) / P;
-  const int64_t chunks = (int64_t)dy.n * dy.h * p.chunks_per_row;
-  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
-  p.total_chunks = (int)chunks;
-  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
-  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
-  dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
-  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
-  p.xcd_map = xcd_map;
+  static const int no_dma = getenv("DF_CONV_NO_DMA") ? atoi(getenv("DF_CONV_NO_DMA")) : 0;
+  if (no_dma || !dma_addressable(x, 4) || !dma_addressable(dy, 4)) p.x_bytes = p.dy_bytes = 0;   // -> the register-staged kernels
+  const dim3 grid = wgrad_grid64(x, dy, splits);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // Measured on MI355X (bs16 step): DMA-fed kernels win for 3x3 stride 1 (register-staged 124.7 -> 4-wave DMA 128.4 ->
   // 12-wave 131-132 TFLOP/s); for 1x1 and stride 2 the register-prefetch kernels are faster (1x1: 12.0 vs 14.8 ms/step;
@@ -2375,16 +2384,19 @@ extern "C" int df_conv2d_wgrad_mp(df_img x, df_img dy, int ksize, int stride, in
 // workspace / reduce as df_conv2d_wgrad_mp.  DF_WGRAD_X3=0 switches it off (df_conv2d_wgrad_x3_ok -> 0).
 extern "C" int df_conv2d_wgrad_x3_ok(df_img x, df_img dy, int ksize, int stride) {
   static const int on = getenv("DF_WGRAD_X3") ? atoi(getenv("DF_WGRAD_X3")) : 1;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
   return on && ksize == 3 && stride == 1 && x.elt == 0 && dy.elt == 0 && img_ok(x) && img_ok(dy) && x.n == dy.n && x.h == dy.h &&
-         x.w == dy.w && (x.c % 32) == 0 && (dy.c % 64) == 0 && (dy.w % 32) == 0 && x.img_stride >= 0 && dy.img_stride >= 0 &&
-         x.grp_off >= 0 && dy.grp_off >= 0 && extent(x) < (int64_t)DMA_BAD && extent(dy) < (int64_t)DMA_BAD;
+         x.w == dy.w && (x.c % 32) == 0 && (dy.c % 64) == 0 && (dy.w % 32) == 0 && dma_addressable(x, 4) && dma_addressable(dy, 4);
 }
 
 static int wgrad_x3_impl(df_img x, df_img dy, const float* x_amax, const float* dy_amax, int ksize, int stride, int pad, float* ws,
-                         int splits, float* bias_ws, void* stream);
+                         int splits, float* bias_ws, void* stream) {
+  DF_REQUIRE(ws && df_aligned16(ws) && pad == 1 && df_conv2d_wgrad_x3_ok(x, dy, ksize, stride) == 1, DF_E_SHAPE);
+  WgradParams p;
+  DF_REQUIRE(wgrad_params(p, x, dy, 4, 1, 1, 32, ws, splits, bias_ws, x_amax, dy_amax) == DF_OK, DF_E_SHAPE);
+  const dim3 grid = wgrad_grid64(x, dy, splits);
+  if (x_amax) return launch_wgrad_dma(wgrad3_x3_kernel<2>, grid, 2 * 2 * 17152, reinterpret_cast<hipStream_t>(stream), p, 768);
+  return launch_wgrad_dma(wgrad3_x3_kernel<3>, grid, 2 * 3 * 17152, reinterpret_cast<hipStream_t>(stream), p, 768);
+}
 
 extern "C" int df_conv2d_wgrad_x3(df_img x, df_img dy, int ksize, int stride, int pad, float* ws, int splits, float* bias_ws,
                                   void* stream) {
@@ -2398,31 +2410,6 @@ extern "C" int df_conv2d_wgrad_h2(df_img x, df_img dy, const float* x_amax, cons
   return wgrad_x3_impl(x, dy, x_amax, dy_amax, ksize, stride, pad, ws, splits, bias_ws, stream);
 }
 
-static int wgrad_x3_impl(df_img x, df_img dy, const float* x_amax, const float* dy_amax, int ksize, int stride, int pad, float* ws,
-                         int splits, float* bias_ws, void* stream) {
-  DF_REQUIRE(ws && df_aligned16(ws) && pad == 1 && df_conv2d_wgrad_x3_ok(x, dy, ksize, stride) == 1, DF_E_SHAPE);
-  WgradParams p;
-  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = nullptr; p.rows_per_seg = 1; p.bias_ws = bias_ws; p.bf16 = 0;
-  p.amax_x = x_amax; p.amax_dy = dy_amax;
-  p.stride = 1; p.pad = 1; p.K = x.c; p.N = dy.c;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
-  p.x_bytes = (unsigned)extent(x);
-  p.dy_bytes = (unsigned)extent(dy);
-  p.chunks_per_row = dy.w / 32;
-  const int64_t chunks = (int64_t)dy.n * dy.h * p.chunks_per_row;
-  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
-  p.total_chunks = (int)chunks;
-  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
-  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
-  dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
-  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
-  p.xcd_map = xcd_map;
-  if (x_amax) return launch_wgrad_dma(wgrad3_x3_kernel<2>, grid, 2 * 2 * 17152, reinterpret_cast<hipStream_t>(stream), p, 768);
-  return launch_wgrad_dma(wgrad3_x3_kernel<3>, grid, 2 * 3 * 17152, reinterpret_cast<hipStream_t>(stream), p, 768);
-}
-
 // 1x1 weight gradient, fp32 tensors, fp16x2 products (wgrad1_h2_kernel; round 5).  _ok: shapes it takes (DF_WGRAD1_H2=0 switches it
 // off); _splits: split-K count (two 4-wave workgroups per CU: one resident round = 512); workspace [splits][Cout][Cin] and the reduce
 // as df_conv2d_wgrad_mp.  x_amax / dy_amax = upper bounds of max|x| / max|dy| (device scalars).
@@ -2430,24 +2417,14 @@ static inline int wgrad1_cot(int cout) { return (cout % 128) == 0 ? 128 : 64; }
 static inline int wgrad1_cit(int cin) { return cin >= 128 ? 128 : 64; }
 extern "C" int df_conv2d_wgrad1_h2_ok(df_img x, df_img dy) {
   static const int on = getenv("DF_WGRAD1_H2") ? atoi(getenv("DF_WGRAD1_H2")) : 1;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
   return on && x.elt == 0 && dy.elt == 0 && img_ok(x) && img_ok(dy) && x.n == dy.n && x.h == dy.h && x.w == dy.w && (x.c % 32) == 0 &&
-         (dy.c % 64) == 0 && (x.ld % 4) == 0 && (dy.ld % 4) == 0 && x.img_stride >= 0 && dy.img_stride >= 0 && x.grp_off >= 0 &&
-         dy.grp_off >= 0 && extent(x) < (int64_t)DMA_BAD && extent(dy) < (int64_t)DMA_BAD;
+         (dy.c % 64) == 0 && (x.ld % 4) == 0 && (dy.ld % 4) == 0 && dma_addressable(x, 4) && dma_addressable(dy, 4);
 }
 
 extern "C" int df_conv2d_wgrad1_h2_splits(df_img x, df_img dy) {
   static const int target = getenv("DF_WGRAD1_H2_BLOCKS") ? atoi(getenv("DF_WGRAD1_H2_BLOCKS")) : 512;
   const int cot = wgrad1_cot(dy.c), cit = wgrad1_cit(x.c);
-  const int tiles = ((x.c + cit - 1) / cit) * (dy.c / cot);
-  const int64_t chunks = (int64_t)dy.n * dy.h * ((dy.w + 31) / 32);
-  int64_t splits = (target + tiles - 1) / tiles;
-  if (splits > chunks) splits = chunks;
-  if (splits < 1) splits = 1;
-  const int64_t cps = (chunks + splits - 1) / splits;
-  return (int)((chunks + cps - 1) / cps);
+  return wgrad_split_count(target, ((x.c + cit - 1) / cit) * (dy.c / cot), wgrad_chunks(dy, 32));
 }
 
 extern "C" int df_conv2d_wgrad1_h2(df_img x, df_img dy, const float* x_amax, const float* dy_amax, float* ws, int splits, float* bias_ws,
@@ -2455,24 +2432,9 @@ extern "C" int df_conv2d_wgrad1_h2(df_img x, df_img dy, const float* x_amax, con
   DF_REQUIRE(((x_amax && dy_amax) || (!x_amax && !dy_amax)) && ws && df_aligned16(ws), DF_E_ARG);   // both NULL: the bf16 one-plane form
   DF_REQUIRE(df_conv2d_wgrad1_h2_ok(x, dy) == 1, DF_E_SHAPE);
   WgradParams p;
-  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = nullptr; p.rows_per_seg = 1; p.bias_ws = bias_ws; p.bf16 = 0;
-  p.amax_x = x_amax; p.amax_dy = dy_amax;
-  p.stride = 1; p.pad = 0; p.K = x.c; p.N = dy.c;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
-  p.x_bytes = (unsigned)extent(x);
-  p.dy_bytes = (unsigned)extent(dy);
-  p.chunks_per_row = (dy.w + 31) / 32;
-  const int64_t chunks = (int64_t)dy.n * dy.h * p.chunks_per_row;
-  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
-  p.total_chunks = (int)chunks;
-  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
-  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
+  DF_REQUIRE(wgrad_params(p, x, dy, 4, 1, 0, 32, ws, splits, bias_ws, x_amax, dy_amax) == DF_OK, DF_E_SHAPE);
   const int cot = wgrad1_cot(dy.c), cit = wgrad1_cit(x.c);
   dim3 grid((x.c + cit - 1) / cit, dy.c / cot, splits);
-  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
-  p.xcd_map = xcd_map;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t lds = (size_t)2 * 2 * (cot + cit) * 64;      // two stages x two planes x (COT + CIT) / 32 halves x 32 px x 64 B
   if (!x_amax) {
@@ -2491,23 +2453,13 @@ extern "C" int df_conv2d_wgrad1_h2(df_img x, df_img dy, const float* x_amax, con
 // stride-2 case (pad 1; Hout = (H - 1) / 2 + 1); DF_WGRAD_S2_H2=0 switches it off.  Workspace [splits][Cout][9][Cin].
 extern "C" int df_conv2d_wgrad_s2_h2_ok(df_img x, df_img dy) {
   static const int on = getenv("DF_WGRAD_S2_H2") ? atoi(getenv("DF_WGRAD_S2_H2")) : 1;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
   return on && x.elt == 0 && dy.elt == 0 && img_ok(x) && img_ok(dy) && x.n == dy.n && dy.h == (x.h - 1) / 2 + 1 && dy.w == (x.w - 1) / 2 + 1 &&
-         (x.c % 32) == 0 && (dy.c % 64) == 0 && (x.ld % 4) == 0 && (dy.ld % 4) == 0 && x.img_stride >= 0 && dy.img_stride >= 0 &&
-         x.grp_off >= 0 && dy.grp_off >= 0 && extent(x) < (int64_t)DMA_BAD && extent(dy) < (int64_t)DMA_BAD;
+         (x.c % 32) == 0 && (dy.c % 64) == 0 && (x.ld % 4) == 0 && (dy.ld % 4) == 0 && dma_addressable(x, 4) && dma_addressable(dy, 4);
 }
 
 extern "C" int df_conv2d_wgrad_s2_h2_splits(df_img x, df_img dy) {
   static const int target = getenv("DF_WGRAD_S2_H2_BLOCKS") ? atoi(getenv("DF_WGRAD_S2_H2_BLOCKS")) : 256;   // one 12-wave workgroup per CU
-  const int tiles = ((x.c + 63) / 64) * (dy.c / 64);
-  const int64_t chunks = (int64_t)dy.n * dy.h * ((dy.w + 15) / 16);
-  int64_t splits = (target + tiles - 1) / tiles;
-  if (splits > chunks) splits = chunks;
-  if (splits < 1) splits = 1;
-  const int64_t cps = (chunks + splits - 1) / splits;
-  return (int)((chunks + cps - 1) / cps);
+  return wgrad_split_count(target, ((x.c + 63) / 64) * (dy.c / 64), wgrad_chunks(dy, 16));
 }
 
 extern "C" int df_conv2d_wgrad_s2_h2(df_img x, df_img dy, const float* x_amax, const float* dy_amax, float* ws, int splits,
@@ -2515,23 +2467,8 @@ extern "C" int df_conv2d_wgrad_s2_h2(df_img x, df_img dy, const float* x_amax, c
   DF_REQUIRE(((x_amax && dy_amax) || (!x_amax && !dy_amax)) && ws && df_aligned16(ws), DF_E_ARG);   // both NULL: the bf16 one-plane form
   DF_REQUIRE(df_conv2d_wgrad_s2_h2_ok(x, dy) == 1, DF_E_SHAPE);
   WgradParams p;
-  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = nullptr; p.rows_per_seg = 1; p.bias_ws = bias_ws; p.bf16 = 0;
-  p.amax_x = x_amax; p.amax_dy = dy_amax;
-  p.stride = 2; p.pad = 1; p.K = x.c; p.N = dy.c;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
-  p.x_bytes = (unsigned)extent(x);
-  p.dy_bytes = (unsigned)extent(dy);
-  p.chunks_per_row = (dy.w + 15) / 16;
-  const int64_t chunks = (int64_t)dy.n * dy.h * p.chunks_per_row;
-  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
-  p.total_chunks = (int)chunks;
-  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
-  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
-  dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
-  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
-  p.xcd_map = xcd_map;
+  DF_REQUIRE(wgrad_params(p, x, dy, 4, 2, 1, 16, ws, splits, bias_ws, x_amax, dy_amax) == DF_OK, DF_E_SHAPE);
+  const dim3 grid = wgrad_grid64(x, dy, splits);
   if (!x_amax) return launch_wgrad_dma(wgrad3s2_h2_kernel<true>, grid, 2 * 15104, reinterpret_cast<hipStream_t>(stream), p, 768);
   return launch_wgrad_dma(wgrad3s2_h2_kernel<false>, grid, 2 * 2 * 15104, reinterpret_cast<hipStream_t>(stream), p, 768);
 }
@@ -2552,13 +2489,7 @@ extern "C" int df_conv2d_wgrad_h2p_ok(df_img x, df_img dy, int ksize, int stride
 // workgroups (DF_WGRAD_H2P_BLOCKS); every split non-empty
 extern "C" int df_conv2d_wgrad_h2p_splits(df_img x, df_img dy) {
   static const int target = getenv("DF_WGRAD_H2P_BLOCKS") ? atoi(getenv("DF_WGRAD_H2P_BLOCKS")) : 256;
-  const int tiles = ((x.c + 63) / 64) * (dy.c / 64);
-  const int64_t chunks = (int64_t)dy.n * dy.h * ((dy.w + 31) / 32);
-  int64_t splits = (target + tiles - 1) / tiles;
-  if (splits > chunks) splits = chunks;
-  if (splits < 1) splits = 1;
-  const int64_t cps = (chunks + splits - 1) / splits;
-  return (int)((chunks + cps - 1) / cps);
+  return wgrad_split_count(target, ((x.c + 63) / 64) * (dy.c / 64), wgrad_chunks(dy, 32));
 }
 
 extern "C" int df_conv2d_wgrad_h2p(df_img x, df_img dy, const float* x_bound, const float* dy_bound, int ksize, int stride, int pad,
@@ -2566,23 +2497,8 @@ extern "C" int df_conv2d_wgrad_h2p(df_img x, df_img dy, const float* x_bound, co
   DF_REQUIRE(x_bound && dy_bound && ws && df_aligned16(ws), DF_E_ARG);
   DF_REQUIRE(pad == 1 && df_conv2d_wgrad_h2p_ok(x, dy, ksize, stride) == 1, DF_E_SHAPE);
   WgradParams p;
-  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = nullptr; p.rows_per_seg = 1; p.bias_ws = bias_ws; p.bf16 = 0;
-  p.amax_x = x_bound; p.amax_dy = dy_bound;
-  p.stride = 1; p.pad = 1; p.K = x.c; p.N = dy.c;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 4;
-  };
-  p.x_bytes = (unsigned)extent(x);
-  p.dy_bytes = (unsigned)extent(dy);
-  p.chunks_per_row = dy.w / 32;
-  const int64_t chunks = (int64_t)dy.n * dy.h * p.chunks_per_row;
-  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
-  p.total_chunks = (int)chunks;
-  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
-  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
-  dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
-  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
-  p.xcd_map = xcd_map;
+  DF_REQUIRE(wgrad_params(p, x, dy, 4, 1, 1, 32, ws, splits, bias_ws, x_bound, dy_bound) == DF_OK, DF_E_SHAPE);   // (4 bytes per element: above)
+  const dim3 grid = wgrad_grid64(x, dy, splits);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   static const int depth = getenv("DF_WGRAD_H2P_DEPTH") ? atoi(getenv("DF_WGRAD_H2P_DEPTH")) : 4;
   const size_t stage = 2 * 17408;
@@ -2600,26 +2516,11 @@ extern "C" int df_conv2d_wgrad_bf16(df_img x, df_img dy, int ksize, int stride, 
   DF_REQUIRE(img_ok(x, true) && img_ok(dy, true) && x.elt == 1 && dy.elt == 1 && ws && df_aligned16(ws), DF_E_ALIGN);
   DF_REQUIRE(ksize == 3 && stride == 1 && pad == 1, DF_E_SHAPE);
   DF_REQUIRE(x.n == dy.n && x.h == dy.h && x.w == dy.w && x.c % 32 == 0 && dy.c % 64 == 0 && (dy.w % 32) == 0, DF_E_SHAPE);
+  DF_REQUIRE(dma_addressable(x, 2) && dma_addressable(dy, 2), DF_E_SHAPE);
   WgradParams p;
-  p.x = x; p.dy = dy; p.ws = ws; p.row_counts = nullptr; p.rows_per_seg = 1; p.bias_ws = bias_ws; p.bf16 = 1;
-  p.stride = 1; p.pad = 1; p.K = x.c; p.N = dy.c;
-  auto extent = [](const df_img& d) {
-    return ((int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld) * 2;
-  };
-  const int64_t ex = extent(x), ey = extent(dy);
-  DF_REQUIRE(x.img_stride >= 0 && dy.img_stride >= 0 && x.grp_off >= 0 && dy.grp_off >= 0 && ex < (int64_t)DMA_BAD && ey < (int64_t)DMA_BAD,
-             DF_E_SHAPE);
-  p.x_bytes = (unsigned)ex;
-  p.dy_bytes = (unsigned)ey;
-  p.chunks_per_row = dy.w / 32;
-  const int64_t chunks = (int64_t)dy.n * dy.h * p.chunks_per_row;
-  DF_REQUIRE(chunks < (1ll << 31) && splits >= 1, DF_E_SHAPE);
-  p.total_chunks = (int)chunks;
-  p.chunks_per_split = (int)((chunks + splits - 1) / splits);
-  DF_REQUIRE((int64_t)p.chunks_per_split * splits >= chunks, DF_E_SHAPE);
-  dim3 grid((x.c + 63) / 64, dy.c / 64, splits);
-  static const int xcd_map = getenv("DF_WGRAD_XCD") ? atoi(getenv("DF_WGRAD_XCD")) : 1;
-  p.xcd_map = xcd_map;
+  DF_REQUIRE(wgrad_params(p, x, dy, 2, 1, 1, 32, ws, splits, bias_ws) == DF_OK, DF_E_SHAPE);
+  p.bf16 = 1;
+  const dim3 grid = wgrad_grid64(x, dy, splits);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   static const int depth = getenv("DF_WGRAD_TR_DEPTH") ? atoi(getenv("DF_WGRAD_TR_DEPTH")) : 4;
   const size_t stage = 4096 + 13 * 1024;

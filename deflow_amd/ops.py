@@ -956,11 +956,39 @@ def weight_transpose(w_ohwi: torch.Tensor) -> torch.Tensor:
     return wt
 
 
-def _wgrad3_name(stride: int) -> str:
-    ring = int(os.environ.get("DF_WGRAD_RING", "2"))   # mirrors df_conv2d_wgrad's dispatch for 3x3 kernels
+def _wgrad_mp_label(x: DfImg, dy: DfImg, ks: int, stride: int) -> str:      # mirrors df_conv2d_wgrad_mp's dispatch (DF_WGRAD_RING / _RING_S2)
+    if ks == 1:
+        return f"wgrad1x1_kernel<{128 if x.c >= 128 else 64}>" if dy.c % 128 == 0 else "wgrad_kernel<1,1,32>"
     if stride == 2:
         return "wgrad3_ring_kernel<16,2,2>" if os.environ.get("DF_WGRAD_RING_S2", "1") != "0" else "wgrad_kernel<3,2,32>"
+    ring = int(os.environ.get("DF_WGRAD_RING", "2"))
     return f"wgrad3_ring_kernel<32,{ring},1>" if ring in (2, 3) else "wgrad_dma_kernel<3,1,32>"
+
+
+def _wgrad_form(x: DfImg, dy: DfImg, ks: int, stride: int, row_counts: Optional[torch.Tensor]) -> tuple:
+    """The weight-gradient form that takes the layer and, in ONE place per form, what goes with it: -> (form, its _splits query (None:
+    df_conv2d_wgrad_splits), its entry point, dev -> that call's arguments between (x, dy) and (ws, splits, ..), its profiler label --
+    bench.py's roofline and the layer census match on these strings)"""
+    geom = (ks, stride, ks // 2)
+    amax = lambda dev: (None, None) if MFMA_BF16 else (ptr(amax_of(x, dev)), ptr(amax_of(dy, dev)))     # (bf16 mode: the one-plane forms)
+    if x.elt == 2 and dy.elt == 2:       # both operands pre-split (h2 images); their bounds are the ones that defined the planes' scales
+        assert ks == 3 and stride == 1 and row_counts is None and call("df_conv2d_wgrad_h2p_ok", x, dy, ks, stride) == 1
+        return "h2p", "df_conv2d_wgrad_h2p_splits", "df_conv2d_wgrad_h2p", lambda dev: (ptr(x._amax), ptr(dy._amax), *geom), "wgrad3_h2p_kernel<4>"
+    assert x.elt != 2 and dy.elt != 2, "a pre-split tensor meets an fp32 one in a weight gradient: unpack it (ops.h2_unpack) or keep both split"
+    if x.elt == 1 and dy.elt == 1:       # bf16-storage mode: both tensors bfloat16 in memory (transposing-read kernel, 3x3 stride 1 only)
+        return "bf16", None, "df_conv2d_wgrad_bf16", lambda dev: geom, "wgrad3_tr_kernel<4>"
+    # round 5: the 1x1 and stride-2 layers' fp32 tensors split in flight -- fp16x2 products instead of the fp32 MFMA (row lists: _mp only)
+    fly = row_counts is None and ((h2_active() and _h2_on()) or (MFMA_BF16 and os.environ.get("DF_WGRAD_BF_FLY", "1") != "0"))
+    if fly and ks == 1 and stride == 1 and call("df_conv2d_wgrad1_h2_ok", x, dy) == 1:
+        return ("w1h2", "df_conv2d_wgrad1_h2_splits", "df_conv2d_wgrad1_h2", amax,
+                f"wgrad1_h2_kernel<{128 if dy.c % 128 == 0 else 64},{128 if x.c >= 128 else 64}>")
+    if fly and ks == 3 and stride == 2 and call("df_conv2d_wgrad_s2_h2_ok", x, dy) == 1:
+        return "s2h2", "df_conv2d_wgrad_s2_h2_splits", "df_conv2d_wgrad_s2_h2", amax, "wgrad3s2_h2_kernel"
+    if row_counts is None and not MFMA_BF16 and ks == 3 and stride == 1 and call("df_conv2d_wgrad_x3_ok", x, dy, ks, stride) == 1:
+        if _h2_on():     # fp32 mode, fp32-accurate products: two scaled fp16 planes per operand, else three bf16 planes
+            return "h2", None, "df_conv2d_wgrad_h2", lambda dev: (*amax(dev), *geom), "wgrad3_x3_kernel<2>"
+        return "x3", None, "df_conv2d_wgrad_x3", lambda dev: geom, "wgrad3_x3_kernel<3>"
+    return "mp", None, "df_conv2d_wgrad_mp", lambda dev: geom, _wgrad_mp_label(x, dy, ks, stride)
 
 
 def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld_co: Optional[int] = None,
@@ -972,19 +1000,8 @@ def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld
     (WeightPrep.composed); dw and the bias sum are then taken apart into the four parameter gradients (df_u5u1_decompose)."""
     dev = dw.device
     assert decompose is None or (want_bias and ld_co is None and not accumulate and not dw_off)
-    pre = x.elt == 2 and dy.elt == 2       # both operands pre-split (h2 images): wgrad3_h2p_kernel
-    assert pre or (x.elt != 2 and dy.elt != 2), "a pre-split tensor meets an fp32 one in a weight gradient: unpack it (ops.h2_unpack) or keep both split"
-    if pre:
-        assert ks == 3 and stride == 1 and row_counts is None and call("df_conv2d_wgrad_h2p_ok", x, dy, ks, stride) == 1
-    t16 = bool(x.elt == 1 and dy.elt == 1)
-    # round 5: the 1x1 layers' fp32 tensors split in flight (wgrad1_h2_kernel) -- fp16x2 products instead of the fp32 MFMA
-    fly = (h2_active() and _h2_on()) or (MFMA_BF16 and os.environ.get("DF_WGRAD_BF_FLY", "1") != "0")   # (bf16 mode: the one-plane forms)
-    h2_1 = bool(not pre and not t16 and ks == 1 and stride == 1 and row_counts is None and fly
-                and call("df_conv2d_wgrad1_h2_ok", x, dy) == 1)
-    h2_s2 = bool(not pre and not t16 and ks == 3 and stride == 2 and row_counts is None and fly
-                 and call("df_conv2d_wgrad_s2_h2_ok", x, dy) == 1)       # the stride-2 3x3 layers likewise (wgrad3s2_h2_kernel)
-    splits = (call("df_conv2d_wgrad_h2p_splits", x, dy) if pre else call("df_conv2d_wgrad1_h2_splits", x, dy) if h2_1
-              else call("df_conv2d_wgrad_s2_h2_splits", x, dy) if h2_s2 else call("df_conv2d_wgrad_splits", x, dy, ks, stride))
+    form, query, entry, mid, name = _wgrad_form(x, dy, ks, stride, row_counts)
+    splits = call(query, x, dy) if query else call("df_conv2d_wgrad_splits", x, dy, ks, stride)
     taps = ks * ks
     ws = _f32(splits * dy.c * taps * x.c, device=dev)
     prof = PROFILER
@@ -992,32 +1009,10 @@ def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     bias_ws = _f32(splits, dy.c, device=dev) if want_bias else None
-    x3 = (not pre and not t16 and not MFMA_BF16 and ks == 3 and stride == 1 and row_counts is None
-          and call("df_conv2d_wgrad_x3_ok", x, dy, ks, stride) == 1)
-    h2 = x3 and _h2_on()
-    if pre:
-        call("df_conv2d_wgrad_h2p", x, dy, ptr(x._amax), ptr(dy._amax), ks, stride, ks // 2, ptr(ws), splits, ptr(bias_ws), stream())
-    elif t16:      # bf16-storage mode: both tensors bfloat16 in memory (transposing-read kernel, 3x3 stride 1 only)
-        call("df_conv2d_wgrad_bf16", x, dy, ks, stride, ks // 2, ptr(ws), splits, ptr(bias_ws), stream())
-    elif h2_1:
-        call("df_conv2d_wgrad1_h2", x, dy, None if MFMA_BF16 else ptr(amax_of(x, dev)), None if MFMA_BF16 else ptr(amax_of(dy, dev)),
-             ptr(ws), splits, ptr(bias_ws), stream())
-    elif h2_s2:
-        call("df_conv2d_wgrad_s2_h2", x, dy, None if MFMA_BF16 else ptr(amax_of(x, dev)), None if MFMA_BF16 else ptr(amax_of(dy, dev)),
-             ptr(ws), splits, ptr(bias_ws), stream())
-    elif h2:     # fp32 mode: fp32-accurate product from two scaled fp16 planes per operand (wgrad3_x3_kernel<2>)
-        call("df_conv2d_wgrad_h2", x, dy, ptr(amax_of(x, dev)), ptr(amax_of(dy, dev)), ks, stride, ks // 2, ptr(ws), splits, ptr(bias_ws),
-             stream())
-    elif x3:     # fp32 mode: fp32-accurate product from three bf16 planes per operand (wgrad3_x3_kernel)
-        call("df_conv2d_wgrad_x3", x, dy, ks, stride, ks // 2, ptr(ws), splits, ptr(bias_ws), stream())
-    else:
-        call("df_conv2d_wgrad_mp", x, dy, ks, stride, ks // 2, ptr(ws), splits, ptr(row_counts), rows_per_seg, ptr(bias_ws),
-             int(MFMA_BF16), stream())
+    tail = (ptr(row_counts), rows_per_seg, ptr(bias_ws), int(MFMA_BF16)) if form == "mp" else (ptr(bias_ws),)
+    call(entry, x, dy, *mid(dev), ptr(ws), splits, *tail, stream())
     if prof is not None:
         e1.record()
-        name = ("wgrad3_h2p_kernel<4>" if pre else f"wgrad1_h2_kernel<{128 if dy.c % 128 == 0 else 64},{128 if x.c >= 128 else 64}>" if h2_1 else "wgrad3s2_h2_kernel" if h2_s2 else "wgrad3_tr_kernel<4>" if t16 else "wgrad3_x3_kernel<2>" if h2 else "wgrad3_x3_kernel<3>" if x3 else f"wgrad1x1_kernel<{128 if x.c >= 128 else 64}>" if ks == 1 and dy.c % 128 == 0
-                else (_wgrad3_name(stride) if ks == 3 else f"wgrad_kernel<{ks},{stride},32>"))
-        # ^ mirrors df_conv2d_wgrad's dispatch (DMA form for 3x3 stride 1)
         tag = f"wgrad {ks}x{ks} s{stride} {x.c}->{dy.c} @{dy.h}x{dy.w} x{dy.n} {'fbh'[x.elt]}{'fbh'[dy.elt]}"
         esz = lambda d: (4, 2, 4)[d.elt]
         prof.records.append((name + ("/bf16" if MFMA_BF16 else ""), 2.0 * dy.n * dy.h * dy.w * taps * x.c * dy.c, e0, e1, tag,

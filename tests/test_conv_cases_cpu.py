@@ -174,6 +174,118 @@ def test_weight_gradient_form_queries_and_splits():
                 assert own in CC.wsplits(p, form, x, dy)
 
 
+def test_pre_split_weight_gradient_query_and_splits():
+    """df_conv2d_wgrad_h2p_ok / _splits on the w_x3 problems as h2 images (elt = 2): one 12-wave workgroup per CU = 256 workgroups over
+    64 x 64 tiles, 32-pixel chunks, at most one split per chunk, every split non-empty"""
+    from deflow_amd._lib import call
+    for p in CC.WPROBS["w_x3"]:
+        xs, ds = (p.n, p.h, p.w, p.cin), (p.n, p.ho, p.wo, p.cout)
+        x, dy = _desc(xs, CC.layout(xs, p.grp, p.views, "x"), 2), _desc(ds, CC.layout(ds, p.grp, p.views, "y"), 2)
+        assert call("df_conv2d_wgrad_h2p_ok", x, dy, p.k, p.stride) == 1, p.pid
+        tiles, chunks = (p.cin + 63) // 64 * (p.cout // 64), p.n * p.ho * ((p.wo + 31) // 32)
+        s = max(1, min(-(-256 // tiles), chunks))
+        cps = -(-chunks // s)
+        assert call("df_conv2d_wgrad_h2p_splits", x, dy) == -(-chunks // cps) == 12, p.pid
+        assert call("df_conv2d_wgrad_h2p_ok", *_wdescs(p), p.k, p.stride) == 0                      # fp32 images are not its operands
+        assert call("df_conv2d_wgrad_h2p_ok", x, dy, 3, 2) == 0 and call("df_conv2d_wgrad_h2p_ok", x, dy, 1, 1) == 0
+
+
+# ---- what a DMA-fed weight-gradient kernel can address -----------------------------------------------------------------------------
+DMA_BAD = 0xFFFFFFFF - (8 << 20)          # conv_common.h: buffer extents at or above it are refused
+E_ALIGN = -2
+
+
+def _pair(stride, elt=0, **kw):
+    """x [2,4,32,64] -> dy [2,4,32,64] (stride 1) or [2,2,16,64] (stride 2), both one group of two images: `img_stride` counts in the
+    extent, `grp_off` does not.  kw: fields to overwrite, as x_<field> / y_<field>; nobody dereferences the address"""
+    from deflow_amd._lib import DfImg
+    probe = torch.empty(64, dtype=torch.float32)
+    base = (probe.data_ptr() + 127) // 128 * 128
+    out = []
+    for side, (h, w) in (("x", (4, 32)), ("y", (4, 32) if stride == 1 else (2, 16))):
+        f = dict(ptr=base, n=2, h=h, w=w, c=64, ld=64, grp_size=2, img_stride=h * w * 64, grp_off=2 * h * w * 64, elt=elt, reserved=0)
+        f.update({k[2:]: v for k, v in kw.items() if k.startswith(side + "_")})
+        out.append(DfImg(*(f[k] for k, _ in DfImg._fields_)))
+    return out
+
+
+def _edge_stride(hw, elt_bytes, gran):
+    """the largest img_stride (a multiple of gran elements) whose extent (img_stride + hw * 64) * elt_bytes stays below DMA_BAD"""
+    s = ((DMA_BAD - 1) // elt_bytes - hw * 64) // gran * gran
+    assert (s + hw * 64) * elt_bytes < DMA_BAD <= (s + gran + hw * 64) * elt_bytes
+    return s
+
+
+def _not_addressable(hw_x, hw_y, elt_bytes, gran):
+    """descriptor changes after which one side is out of a buffer descriptor's reach"""
+    out = []
+    for side, hw in (("x", hw_x), ("y", hw_y)):
+        out += [{side + "_img_stride": -hw * 64}, {side + "_grp_off": -2 * hw * 64}, {side + "_img_stride": _edge_stride(hw, elt_bytes, gran) + gran}]
+    return out
+
+
+def test_weight_gradient_dma_addressability():
+    from ctypes import c_void_p as P
+    from deflow_amd._lib import call, load
+    ws = _pair(1)[0].ptr
+    queries = (("df_conv2d_wgrad_x3_ok", 1, (3, 1)), ("df_conv2d_wgrad1_h2_ok", 1, ()), ("df_conv2d_wgrad_s2_h2_ok", 2, ()))
+    for name, stride, tail in queries:
+        hw_y = 128 if stride == 1 else 32
+        assert call(name, *_pair(stride), *tail) == 1, name
+        for kw in _not_addressable(128, hw_y, 4, 4):
+            assert call(name, *_pair(stride, **kw), *tail) == 0, (name, kw)
+        for kw in ({"x_img_stride": _edge_stride(128, 4, 4)}, {"y_img_stride": _edge_stride(hw_y, 4, 4)}):
+            assert call(name, *_pair(stride, **kw), *tail) == 1, (name, kw)                          # just below DMA_BAD
+    for name, stride, tail in queries[1:]:
+        for kw in ({"x_ld": 66}, {"y_ld": 66}):
+            assert call(name, *_pair(stride, **kw), *tail) == 0, (name, kw)
+    # the pre-split form: geometry and extents of the fp32 tensor (4 bytes per element), 128-byte lines
+    assert call("df_conv2d_wgrad_h2p_ok", *_pair(1, 2), 3, 1) == 1
+    for kw in _not_addressable(128, 128, 4, 32):
+        assert call("df_conv2d_wgrad_h2p_ok", *_pair(1, 2, **kw), 3, 1) == 0, kw
+    for kw in ({"x_img_stride": _edge_stride(128, 4, 32)}, {"y_img_stride": _edge_stride(128, 4, 32)}):
+        assert call("df_conv2d_wgrad_h2p_ok", *_pair(1, 2, **kw), 3, 1) == 1, kw
+    for side in "xy":
+        for kw in ({side + "_ld": 68}, {side + "_img_stride": 128 * 64 + 4}, {side + "_ptr": ws + 16}):
+            assert call("df_conv2d_wgrad_h2p_ok", *_pair(1, 2, **kw), 3, 1) == 0, kw
+    # bfloat16 tensors: 2 bytes per element; the entry point itself refuses (nothing is launched)
+    for kw in _not_addressable(128, 128, 2, 8):
+        x, dy = _pair(1, 1, **kw)
+        assert load().df_conv2d_wgrad_bf16(x, dy, 3, 1, 1, P(ws), 1, P(0), P(0)) == CC.E_SHAPE, kw
+
+
+def test_weight_gradient_entry_points_refuse_before_launching():
+    """per launch entry point, the status for (ws = NULL, splits = 0, both): the first failing check decides, in the order of its
+    DF_REQUIREs; wgrad1_h2 / s2_h2 also for one bound without the other.  Every call returns before a launch."""
+    import ctypes
+    from deflow_amd._lib import load
+    lib, P = load(), ctypes.c_void_p
+    x, dy = _pair(1)
+    x2, dy2 = _pair(2)
+    xh, dyh = _pair(1, 2)
+    xb, dyb = _pair(1, 1)
+    a = x.ptr                  # an aligned non-NULL address for ws and the bounds
+    entries = {     # name: (call with (ws, splits), (code for ws = NULL, for splits = 0, for both))
+        "df_conv2d_wgrad_mp": (lambda ws, s: lib.df_conv2d_wgrad_mp(x, dy, 3, 1, 1, P(ws), s, P(0), 0, P(0), 0, P(0)), (E_ALIGN, CC.E_SHAPE, E_ALIGN)),
+        "df_conv2d_wgrad": (lambda ws, s: lib.df_conv2d_wgrad(x, dy, 3, 1, 1, P(ws), s, P(0), 0, P(0), P(0)), (E_ALIGN, CC.E_SHAPE, E_ALIGN)),
+        "df_conv2d_wgrad_x3": (lambda ws, s: lib.df_conv2d_wgrad_x3(x, dy, 3, 1, 1, P(ws), s, P(0), P(0)), (CC.E_SHAPE,) * 3),
+        "df_conv2d_wgrad_h2": (lambda ws, s: lib.df_conv2d_wgrad_h2(x, dy, P(a), P(a), 3, 1, 1, P(ws), s, P(0), P(0)), (CC.E_SHAPE,) * 3),
+        "df_conv2d_wgrad1_h2": (lambda ws, s: lib.df_conv2d_wgrad1_h2(x, dy, P(a), P(a), P(ws), s, P(0), P(0)), (CC.E_ARG, CC.E_SHAPE, CC.E_ARG)),
+        "df_conv2d_wgrad_s2_h2": (lambda ws, s: lib.df_conv2d_wgrad_s2_h2(x2, dy2, P(a), P(a), P(ws), s, P(0), P(0)), (CC.E_ARG, CC.E_SHAPE, CC.E_ARG)),
+        "df_conv2d_wgrad_h2p": (lambda ws, s: lib.df_conv2d_wgrad_h2p(xh, dyh, P(a), P(a), 3, 1, 1, P(ws), s, P(0), P(0)), (CC.E_ARG, CC.E_SHAPE, CC.E_ARG)),
+        "df_conv2d_wgrad_bf16": (lambda ws, s: lib.df_conv2d_wgrad_bf16(xb, dyb, 3, 1, 1, P(ws), s, P(0), P(0)), (E_ALIGN, CC.E_SHAPE, E_ALIGN)),
+    }
+    for name, (fn, codes) in entries.items():
+        got = (fn(0, 1), fn(a, 0), fn(0, 0))
+        print(f"[wgrad refusals] {name}: ws NULL {got[0]}, splits 0 {got[1]}, both {got[2]}")
+        assert got == codes, (name, got)
+    for b in ((a, 0), (0, a)):
+        assert lib.df_conv2d_wgrad1_h2(x, dy, P(b[0]), P(b[1]), P(a), 1, P(0), P(0)) == CC.E_ARG
+        assert lib.df_conv2d_wgrad_s2_h2(x2, dy2, P(b[0]), P(b[1]), P(a), 1, P(0), P(0)) == CC.E_ARG
+        assert lib.df_conv2d_wgrad_h2(x, dy, P(b[0]), P(b[1]), 3, 1, 1, P(a), 1, P(0), P(0)) == CC.E_ARG
+        assert lib.df_conv2d_wgrad_h2p(xh, dyh, P(b[0]), P(b[1]), 3, 1, 1, P(a), 1, P(0), P(0)) == CC.E_ARG
+
+
 # ---- chunks and splits ----------------------------------------------------------------------------------------------------------
 def _split_facts(p, splits):
     P, cpr, chunks = CC.wchunks(p)
