@@ -34,7 +34,8 @@ from .h5scene import H5File
 
 class HDF5Dataset:
     def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False, dynamic_key: str = "dufo_label",
-                 dynamic_sidecar: Optional[str] = ".dufo.npz", ground_sidecar: str = ".ground.npz", ground_source: str = "auto"):
+                 dynamic_sidecar: Optional[str] = ".dufo.npz", ground_sidecar: str = ".ground.npz", ground_source: str = "auto",
+                 flow_sidecar: Optional[str] = None):
         """``dynamic_key``: the per-sweep dataset holding the per-point dynamic flag (non-zero = dynamic) that online cluster labels
         start from (``Trainer(cluster_labels=...)``).  UNPINNED: ``dufo_label`` is the name recalled from upstream's process.py (the
         DUFO pass writes it before HDBSCAN turns it into ``label``), hence an argument.  When both sweeps of a pair hold it, the item
@@ -49,6 +50,11 @@ class HDF5Dataset:
         segmenter of DESIGN.md section 6d (UNPINNED) -- and when neither exists a KeyError names that command.  "file": the dataset only.
         "sidecar": the sidecar only, which must exist; the datasets are ignored.  An array whose length differs from the sweep's rows is
         a ValueError.  A directory whose files carry ``ground_mask`` gives the items it always gave.
+        ``flow_sidecar``: a ``res_name``.  A pair whose first group holds no ``flow`` dataset takes ``flow`` from
+        ``<directory>/<scene_id>.<res_name>.flow.npz`` -- the file ``python -m deflow_amd.save`` writes: the total flow of every raw row
+        per timestamp (pseudo labels, e.g. of ``save model=icpflow``) -- with ``flow_is_valid`` all true and
+        ``flow_category_indices`` all zero.  A missing file or timestamp is a KeyError naming that command, an array whose length differs
+        from the sweep's rows a ValueError.  A group that has ``flow`` keeps it.  None: the items the directory always gave.
         ``eval=True`` (the evaluation entry): read ``index_eval.pkl`` -- the frames of the official validation benchmark, the ones
         that carry an ``eval_mask`` -- when the directory has one, as upstream's dataset does for ``av2_mode=val`` (recalled: the
         module is in the absent submodule); ``index_total.pkl`` lists every sweep of every scene."""
@@ -61,6 +67,10 @@ class HDF5Dataset:
             raise ValueError("ground_source='sidecar' needs a ground_sidecar suffix")
         self.ground_sidecar = ground_sidecar
         self.ground_source = ground_source
+        if flow_sidecar is not None and (not flow_sidecar or os.sep in str(flow_sidecar)):
+            raise ValueError(f"flow_sidecar must be the res_name of a flow file, got {flow_sidecar!r}")
+        self.flow_sidecar = flow_sidecar
+        self._flow_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
         self._sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()       # cached per scene like the open files (None: no file)
         self._ground_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
         name = "index_total.pkl"
@@ -108,6 +118,32 @@ class HDF5Dataset:
                 cache.popitem(last=False)
         return side
 
+    def _pseudo_flow(self, scene_id: str, ts: str, rows: int) -> torch.Tensor:
+        """the flow of one sweep's raw rows from ``<scene_id>.<flow_sidecar>.flow.npz``"""
+        name = f"{scene_id}.{self.flow_sidecar}.flow.npz"
+        with self._lock:
+            known = scene_id in self._flow_sidecars
+            side = self._flow_sidecars.get(scene_id)
+        if not known:
+            path = os.path.join(self.directory, name)
+            if os.path.exists(path):
+                import numpy as np
+                with np.load(path, allow_pickle=False) as z:
+                    side = {k: z[k] for k in z.files if k != "meta" and not k.endswith(".dynamic")}
+            with self._lock:
+                self._flow_sidecars[scene_id] = side
+                while len(self._flow_sidecars) > self._max_open:
+                    self._flow_sidecars.popitem(last=False)
+        if side is None or ts not in side:
+            what = "does not exist" if side is None else f"has no entry for sweep {ts}"
+            raise KeyError(f"{scene_id}: sweep {ts} has no flow dataset and {name} {what}; write it with  python -m deflow_amd.save "
+                           f"dataset_path={self.directory} res_name={self.flow_sidecar} (model=icpflow needs no checkpoint)")
+        flow = torch.from_numpy(side[ts])
+        if flow.dim() != 2 or flow.shape[1] != 3 or flow.shape[0] != rows:
+            raise ValueError(f"{name}: flow of shape {tuple(flow.shape)} for sweep {ts}, which has {rows} rows: the file belongs to "
+                             "another version of the scene file")
+        return flow.float()
+
     def _ground(self, scene_id: str, ts: str, group, rows: int) -> torch.Tensor:
         """the ground mask of one sweep, by ``ground_source``"""
         if self.ground_source == "file" or (self.ground_source == "auto" and "ground_mask" in group):
@@ -143,6 +179,10 @@ class HDF5Dataset:
         if "flow" in g0:
             item.update(flow=t(g0["flow"]), flow_is_valid=t(g0["flow_is_valid"]),
                         flow_category_indices=t(g0["flow_category_indices"]))
+        elif getattr(self, "flow_sidecar", None):      # pseudo labels: every row valid, no classes
+            n = int(pc0.shape[0])
+            item.update(flow=self._pseudo_flow(scene_id, timestamp, n), flow_is_valid=torch.ones(n, dtype=torch.bool),
+                        flow_category_indices=torch.zeros(n, dtype=torch.uint8))
         if "ego_motion" in g0:
             item["ego_motion"] = t(g0["ego_motion"])
         if "label" in g0 and "label" in g1:      # cluster labels of the self-supervised mode (upstream's process.py: DUFO + HDBSCAN; 0 = static)

@@ -163,18 +163,39 @@ def main_test(argv: List[str]) -> Dict[str, Any]:
     return result
 
 
+def icpflow_config(given: Dict[str, str]):
+    """``model=icpflow``: (configuration, rigid parameters) from the command line alone -- the defaults of deflow_amd.train under the keys
+    as typed ({key: "key=value"}), the ``icp_*`` keys validated by deflow_amd.rigid.  Needs no GPU and reads no file."""
+    from .rigid import COMMAND_KEYS, params_from_command
+    for k in ("checkpoint", "inference_dtype"):
+        if k in given:
+            raise SystemExit(f"model=icpflow has no weights: it takes no {k}=")
+    icp = {k: a.split("=", 1)[1] for k, a in given.items() if k in COMMAND_KEYS}
+    cfg = parse_overrides([a for k, a in given.items() if k not in COMMAND_KEYS and k != "model"])
+    cfg["model"] = "icpflow"
+    return cfg, params_from_command(icp)
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
+    icpflow = given.get("model") == "model=icpflow"
+    if icpflow and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        raise SystemExit("model=icpflow writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
+                         "metrics, python -m deflow_amd.save model=icpflow writes its flow")
     if given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         return main_test(args)          # the leaderboard submission: no metrics (the test split has no labels)
     if given.get("av2_mode", "av2_mode=val") != "av2_mode=val":
         raise SystemExit(f"unknown {given['av2_mode']} (val: the metrics, test: the leaderboard submission)")
-    if "checkpoint" not in given:
-        raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE)
-    path = given["checkpoint"].split("=", 1)[1]
-    cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
+    if icpflow:
+        (cfg, icp_params), path = icpflow_config(given), None
+    elif "checkpoint" not in given:
+        raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE +
+                         "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]")
+    else:
+        path = given["checkpoint"].split("=", 1)[1]
+        cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
     if not any(k in given for k in DATA_KEYS):
         print("[deflow_amd.eval] NOTE: no dataset_path= / val_data= given -- evaluating on seeded SYNTHETIC pairs, not on a "
               "dataset (the reference reads its config's dataset_path default here)", file=sys.stderr)
@@ -192,14 +213,18 @@ def main(argv=None):
         official = DeviceMetrics(dev)
     else:
         official = OfficialMetrics()
-    model = build_model(cfg).to(dev)
-    res = model.load_from_checkpoint(path)
-    if res.missing_keys or res.unexpected_keys:   # strict=False as the reference loads [REF deflow.py:47] -- but never silently
-        print(f"[deflow_amd.eval] WARNING: checkpoint / model mismatch (model={cfg['model']}): {len(res.missing_keys)} missing keys "
-              f"{res.missing_keys[:4]}..., {len(res.unexpected_keys)} unexpected keys {res.unexpected_keys[:4]}...", file=sys.stderr)
-    model.eval()
-    if "inference_dtype" in given:
-        model.inference_dtype = given["inference_dtype"].split("=", 1)[1]
+    if icpflow:
+        from .rigid import IcpFlow
+        model = IcpFlow(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **icp_params)
+    else:
+        model = build_model(cfg).to(dev)
+        res = model.load_from_checkpoint(path)
+        if res.missing_keys or res.unexpected_keys:   # strict=False as the reference loads [REF deflow.py:47] -- but never silently
+            print(f"[deflow_amd.eval] WARNING: checkpoint / model mismatch (model={cfg['model']}): {len(res.missing_keys)} missing keys "
+                  f"{res.missing_keys[:4]}..., {len(res.unexpected_keys)} unexpected keys {res.unexpected_keys[:4]}...", file=sys.stderr)
+        model.eval()
+        if "inference_dtype" in given:
+            model.inference_dtype = given["inference_dtype"].split("=", 1)[1]
     B = int(cfg["batch_size"])
     if cfg["val_data"] != "synthetic":
         from .data import HDF5Dataset, SceneLoader, ShardedSampler

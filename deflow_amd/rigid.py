@@ -1,0 +1,276 @@
+"""Training-free rigid cluster flow on the GPU (``model=icpflow``): the flow of the first sweep's rows from a per-cluster rigid
+registration onto the second sweep, with no weights and no checkpoint.
+
+UNPINNED: the recipe is ICP-Flow's (Lin & Caesar, CVPR'24) -- ego-compensate, cluster both sweeps together, register every cluster
+rigidly, read the flow off the transform -- but upstream's source is absent, and every choice here is this project's own.  The definition
+is in include/deflow_amd.h and DESIGN.md section 6j; tests/helpers/rigid_ref.py restates it in numpy.  Joint clusters come from
+``cluster.dbscan`` over the concatenated rows; csrc/rigid.hip builds the ordered row lists per cluster, votes for a translation over all
+point pairs (integer counters: exact), refines yaw + translation by a fixed number of ICP iterations and writes the per-row flow.
+
+CUDA tensors only, like the rest of the library: there is no CPU fallback.  Nothing here reads a device value back."""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from ._lib import call, ptr, stream
+
+STATUS_NAMES = {0: "empty", 1: "registered", 2: "one-sided", 3: "too large", 4: "inlier fraction", 5: "no vote / yaw / displacement"}
+R_MAX = 64
+
+# every default of section 6j; all of them are arguments of rigid_cluster_flow and IcpFlow, and `icp_<name>=` keys of the commands
+DEFAULTS: Dict[str, object] = {"eps": 0.7, "min_points": 4, "min_cluster_size": 20, "min_side": 8, "max_cluster_points": 8192,
+                               "vote_cap": 1024, "vote_bin": 0.2, "max_disp": 3.4, "icp_cap": 2048, "icp_iters": 8, "icp_max_dist": 0.5,
+                               "min_inlier_frac": 0.6, "max_yaw": 0.35}
+
+
+# the commands' keys (save, eval): icp_<name>, the three names that start with icp_ already as they are
+COMMAND_KEYS: Dict[str, str] = {(k if k.startswith("icp_") else "icp_" + k): k for k in DEFAULTS}
+
+
+def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
+    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
+    import ast
+    p: Dict[str, object] = {}
+    for k, v in given.items():
+        try:
+            p[COMMAND_KEYS[k]] = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            raise SystemExit(f"bad value for {k}: {v!r}")
+    try:
+        return check_params(p)
+    except (ValueError, TypeError) as e:
+        raise SystemExit(f"bad value among the icp_* keys: {e}")
+
+
+def vote_radius(max_disp: float, vote_bin: float) -> int:
+    """R = ceil(max_disp / vote_bin) with both rounded to fp32 first and the quotient taken in double (3.4 / 0.2: 17)"""
+    import numpy as np
+    q = float(np.float32(max_disp)) / float(np.float32(vote_bin))
+    return int(math.ceil(q - 1e-6))
+
+
+def check_params(p: Dict[str, object]) -> Dict[str, object]:
+    """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
+    out = dict(DEFAULTS)
+    for k, v in p.items():
+        if k not in DEFAULTS:
+            raise ValueError(f"rigid_cluster_flow: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
+        out[k] = v
+    for k in ("min_points", "min_cluster_size", "min_side", "max_cluster_points", "vote_cap", "icp_cap"):
+        if isinstance(out[k], bool) or int(out[k]) != out[k] or int(out[k]) < 1:
+            raise ValueError(f"rigid_cluster_flow: {k} must be an integer >= 1, got {out[k]!r}")
+        out[k] = int(out[k])
+    for k in ("vote_cap", "icp_cap"):
+        if out[k] > 1 << 20:
+            raise ValueError(f"rigid_cluster_flow: {k} must be at most 2^20, got {out[k]}")
+    if isinstance(out["icp_iters"], bool) or int(out["icp_iters"]) != out["icp_iters"] or not 0 <= int(out["icp_iters"]) <= 1024:
+        raise ValueError(f"rigid_cluster_flow: icp_iters must be an integer in [0, 1024], got {out['icp_iters']!r}")
+    out["icp_iters"] = int(out["icp_iters"])
+    for k in ("eps", "vote_bin", "icp_max_dist"):
+        if not (math.isfinite(float(out[k])) and float(out[k]) > 0):
+            raise ValueError(f"rigid_cluster_flow: {k} must be positive and finite, got {out[k]!r}")
+        out[k] = float(out[k])
+    for k in ("max_disp", "max_yaw", "min_inlier_frac"):
+        if not (math.isfinite(float(out[k])) and float(out[k]) >= 0):
+            raise ValueError(f"rigid_cluster_flow: {k} must be finite and >= 0, got {out[k]!r}")
+        out[k] = float(out[k])
+    if vote_radius(out["max_disp"], out["vote_bin"]) > R_MAX:
+        raise ValueError(f"rigid_cluster_flow: max_disp / vote_bin must be at most {R_MAX} bins, got max_disp = {out['max_disp']}, "
+                         f"vote_bin = {out['vote_bin']}")
+    return out
+
+
+def _check(name: str, t, shape, dtype, device=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"rigid_cluster_flow: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    if device is not None and t.device != device:
+        raise ValueError(f"rigid_cluster_flow: {name} is on {t.device}, pc0s is on {device}")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"rigid_cluster_flow: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def _cloud(name: str, t) -> int:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"rigid_cluster_flow: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"rigid_cluster_flow: {name} must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got "
+                         f"{t.dtype} {tuple(t.shape)}")
+    return int(t.shape[1])
+
+
+def kcap(N0: int, N1: int, min_cluster_size: int) -> int:
+    """cluster slots per sample: every cluster has at least min_cluster_size rows, so no more than this many exist"""
+    return max((N0 + N1) // int(min_cluster_size), 1)
+
+
+def joint_labels(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *, eps: float, min_points: int,
+                 min_cluster_size: int, grid_range: Optional[Sequence[float]] = None, status: Optional[torch.Tensor] = None):
+    """DBSCAN labels [B,N0+N1] i32 of the concatenation (pc0s rows, then pc1 rows); rows behind either count take no part"""
+    from .cluster import dbscan
+    B, N0, N1 = pc0s.shape[0], pc0s.shape[1], pc1.shape[1]
+    dev = pc0s.device
+    pts = torch.cat([pc0s, pc1], dim=1)
+    r0 = torch.arange(N0, device=dev, dtype=torch.int32)
+    r1 = torch.arange(N1, device=dev, dtype=torch.int32)
+    mask = torch.cat([r0[None, :] < count0[:, None], r1[None, :] < count1[:, None]], dim=1)
+    full = torch.full((B,), N0 + N1, dtype=torch.int32, device=dev)
+    labels, _ = dbscan(pts, full, mask, eps=eps, min_points=min_points, min_cluster_size=min_cluster_size, grid_range=grid_range,
+                       status=status)
+    return labels
+
+
+def rigid_cluster_flow(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *, eps: float = 0.7,
+                       min_points: int = 4, min_cluster_size: int = 20, min_side: int = 8, max_cluster_points: int = 8192,
+                       vote_cap: int = 1024, vote_bin: float = 0.2, max_disp: float = 3.4, icp_cap: int = 2048, icp_iters: int = 8,
+                       icp_max_dist: float = 0.5, min_inlier_frac: float = 0.6, max_yaw: float = 0.35,
+                       grid_range: Optional[Sequence[float]] = None, labels: Optional[torch.Tensor] = None, return_hist: bool = False):
+    """pc0s [B,N0,3] f32 (first sweep, ground removed, in the second sweep's frame) with count0 [B] i32 valid leading rows; pc1 [B,N1,3],
+    count1 alike.  -> flow [B,N0,3] f32 (the residual flow on top of the pose flow; 0 for rows of no registered cluster), rigid_id [B,N0] i32
+    (the cluster slot 1..Kcap of a registered row, else 0), table [B,Kcap,8] f32 (theta, tx, ty, tz, inlier_frac, n_src, n_dst, status),
+    vote [B,Kcap,3] i32 (ix, iy, count), status i32[1] (0 unless a bounded loop hit its bound); with return_hist also the whole vote
+    histogram [B,Kcap,2R+1,2R+1] i32 as a sixth value.  Kcap = max((N0+N1) // min_cluster_size, 1).
+    labels: the joint labels [B,N0+N1] i32 when the caller has them already (else cluster.dbscan computes them); grid_range as in dbscan.
+    No host synchronisation; workspaces come from torch's allocator; two calls are bit-identical."""
+    N0, N1 = _cloud("pc0s", pc0s), _cloud("pc1", pc1)
+    B, dev = int(pc0s.shape[0]), pc0s.device
+    if pc1.shape[0] != B:
+        raise ValueError(f"rigid_cluster_flow: pc1 must have the batch size of pc0s ({B}), got {tuple(pc1.shape)}")
+    if pc1.device != dev:
+        raise ValueError(f"rigid_cluster_flow: pc1 is on {pc1.device}, pc0s is on {dev}")
+    _check("count0", count0, (B,), torch.int32, dev)
+    _check("count1", count1, (B,), torch.int32, dev)
+    p = check_params({"eps": eps, "min_points": min_points, "min_cluster_size": min_cluster_size, "min_side": min_side,
+                      "max_cluster_points": max_cluster_points, "vote_cap": vote_cap, "vote_bin": vote_bin, "max_disp": max_disp,
+                      "icp_cap": icp_cap, "icp_iters": icp_iters, "icp_max_dist": icp_max_dist, "min_inlier_frac": min_inlier_frac,
+                      "max_yaw": max_yaw})
+    N = N0 + N1
+    if B > 65535 or B * N >= 2 ** 31:
+        raise ValueError(f"rigid_cluster_flow: 1 <= B <= 65535 and B * (N0 + N1) < 2^31 expected, got B = {B}, N0 = {N0}, N1 = {N1}")
+    K = kcap(N0, N1, p["min_cluster_size"])
+    R = vote_radius(p["max_disp"], p["vote_bin"])
+    if labels is not None:
+        _check("labels", labels, (B, N), torch.int32, dev)
+    pc0s, pc1 = pc0s.detach().contiguous(), pc1.detach().contiguous()
+    count0, count1 = count0.contiguous(), count1.contiguous()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if labels is None:
+        labels = joint_labels(pc0s, count0, pc1, count1, eps=p["eps"], min_points=p["min_points"],
+                              min_cluster_size=p["min_cluster_size"], grid_range=grid_range, status=status)
+    labels = labels.contiguous()
+
+    def ws(entry, *a):
+        need = int(call(entry, *a))
+        if need < 0:
+            raise ValueError(f"rigid_cluster_flow: {entry} refused B = {B}, N0 = {N0}, N1 = {N1}")
+        return torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
+
+    seg_ws, icp_ws = ws("df_rigid_segments_ws_bytes", B, N0, N1, K), ws("df_rigid_icp_ws_bytes", B, N0, N1)
+    seg_off = torch.empty(B, 2 * K + 1, dtype=torch.int32, device=dev)
+    seg_rows = torch.empty(B, N, dtype=torch.int32, device=dev)
+    vote = torch.empty(B, K, 3, dtype=torch.int32, device=dev)
+    hist = torch.empty(B, K, 2 * R + 1, 2 * R + 1, dtype=torch.int32, device=dev) if return_hist else None
+    table = torch.empty(B, K, 8, dtype=torch.float32, device=dev)
+    flow = torch.empty(B, N0, 3, dtype=torch.float32, device=dev)
+    rigid_id = torch.empty(B, N0, dtype=torch.int32, device=dev)
+    s = stream()
+    call("df_rigid_segments", ptr(labels), B, N0, N1, K, ptr(seg_off), ptr(seg_rows), ptr(status), ptr(seg_ws), s)
+    call("df_rigid_vote", ptr(pc0s), ptr(pc1), ptr(seg_off), ptr(seg_rows), B, N0, N1, K, p["min_side"], p["max_cluster_points"],
+         p["vote_cap"], p["vote_bin"], R, ptr(vote), ptr(hist), s)
+    call("df_rigid_icp", ptr(pc0s), ptr(pc1), ptr(seg_off), ptr(seg_rows), ptr(vote), B, N0, N1, K, p["min_side"], p["max_cluster_points"],
+         p["icp_cap"], p["icp_iters"], p["vote_bin"], p["icp_max_dist"], p["min_inlier_frac"], p["max_yaw"], p["max_disp"], ptr(table),
+         ptr(icp_ws), s)
+    call("df_rigid_apply", ptr(pc0s), ptr(count0), ptr(labels), ptr(seg_off), ptr(seg_rows), ptr(table), B, N0, N1, K, ptr(flow),
+         ptr(rigid_id), s)
+    if return_hist:
+        return flow, rigid_id, table, vote, status, hist
+    return flow, rigid_id, table, vote, status
+
+
+class IcpFlow:
+    """``model=icpflow``: an object with the two methods of ``DeFlow`` the commands use -- ``forward_padded`` and ``forward`` -- and no
+    weights.  ``sweeps.SweepFlow``, ``metrics.evaluate_batch`` and ``metrics_device.evaluate_batch_device`` take it as they take the model.
+    point_cloud_range / voxel_size decide which rows count as decoded, by the voxeliser's rule (floor((p - min) / voxel) inside the grid on
+    all three axes, on the ego-compensated rows); every other keyword is a parameter of ``rigid_cluster_flow``."""
+
+    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
+        if len(point_cloud_range) != 6 or len(voxel_size) != 3:
+            raise ValueError("IcpFlow: point_cloud_range has 6 values and voxel_size 3")
+        self.point_cloud_range = [float(v) for v in point_cloud_range]
+        self.voxel_size = [float(v) for v in voxel_size]
+        if not all(v > 0 for v in self.voxel_size):
+            raise ValueError(f"IcpFlow: voxel_size must be positive, got {voxel_size}")
+        self.grid = [int(round((self.point_cloud_range[3 + i] - self.point_cloud_range[i]) / self.voxel_size[i])) for i in range(3)]
+        if not all(g >= 1 for g in self.grid):
+            raise ValueError(f"IcpFlow: empty point_cloud_range {point_cloud_range}")
+        self.params = check_params(params)
+        self.training = False
+        self.last_state: Optional[dict] = None
+
+    # (the commands treat the model as an nn.Module)
+    def eval(self):
+        return self
+
+    def to(self, *a, **k):
+        return self
+
+    def parameters(self):
+        return iter(())
+
+    def _decoded(self, pts: torch.Tensor) -> torch.Tensor:
+        """[B,N] bool: the rows the voxeliser would keep (csrc/pillar_common.h: NaN rows and rows outside the grid are not decoded)"""
+        ok = ~torch.isnan(pts).any(dim=2)
+        for i in range(3):
+            f = torch.floor((pts[..., i] - self.point_cloud_range[i]) / self.voxel_size[i])
+            ok &= (f >= 0) & (f < float(self.grid[i]))
+        return ok
+
+    @staticmethod
+    def _compact(valid: torch.Tensor):
+        """stable: idx [B,N] i64 with the valid rows first in ascending order, counts [B] i32"""
+        idx = torch.argsort((~valid).to(torch.uint8), dim=1, stable=True)
+        return idx, valid.sum(dim=1).to(torch.int32)
+
+    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
+        """flow [B,N,3]: row i < counts0[b] is the flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind them;
+        pose_flow [B,N,3] of every input row; pc0s the ego-compensated rows.  Reads nothing back."""
+        from .deflow import batch_transform
+        pc0 = batch["pc0"].contiguous().float()
+        pc1 = batch["pc1"].contiguous().float()
+        if not pc0.is_cuda or not pc1.is_cuda:
+            raise TypeError("IcpFlow: pc0 and pc1 must be CUDA tensors (deflow_amd has no CPU fallback)")
+        B, N, _ = pc0.shape
+        T = batch_transform(batch, pc0.device)
+        pc0s = torch.empty_like(pc0)
+        pose_flow = torch.empty_like(pc0)
+        call("df_ego_transform", ptr(pc0), ptr(T), B, N, ptr(pc0s), ptr(pose_flow), stream())
+        v0, v1 = self._decoded(pc0s), self._decoded(pc1)
+        idx0, counts0 = self._compact(v0)
+        idx1, counts1 = self._compact(v1)
+        g0 = torch.gather(pc0s, 1, idx0[..., None].expand(-1, -1, 3))
+        g1 = torch.gather(pc1, 1, idx1[..., None].expand(-1, -1, 3))
+        r = self.point_cloud_range
+        flow, rigid_id, table, vote, status = rigid_cluster_flow(g0, counts0, g1, counts1, grid_range=(r[0], r[1], r[3], r[4]), **self.params)
+        self.last_state = {"flow": flow, "pose_flow": pose_flow, "counts0": counts0, "counts1": counts1, "idx_c0": idx0, "idx_c1": idx1,
+                           "pc0s": pc0s, "points_c0": g0, "points_c1": g1, "rigid_id": rigid_id, "table": table, "vote": vote,
+                           "status": status}
+        return self.last_state
+
+    def forward(self, batch: Dict[str, torch.Tensor]):
+        """the dict of lists ``DeFlow.forward`` returns (one host read: the per-sample counts)"""
+        st = self.forward_padded(batch)
+        B = st["flow"].shape[0]
+        m = torch.stack([st["counts0"], st["counts1"]]).tolist()
+        m0, m1 = m[0], m[1]
+        return {
+            "flow": [st["flow"][b, :m0[b]] for b in range(B)],
+            "pose_flow": [st["pose_flow"][b] for b in range(B)],
+            "pc0_valid_point_idxes": [st["idx_c0"][b, :m0[b]] for b in range(B)],
+            "pc0_points_lst": [st["points_c0"][b, :m0[b]] for b in range(B)],
+            "pc1_valid_point_idxes": [st["idx_c1"][b, :m1[b]] for b in range(B)],
+            "pc1_points_lst": [st["points_c1"][b, :m1[b]] for b in range(B)],
+        }
+
+    __call__ = forward

@@ -12,7 +12,12 @@ one copy per batch and output array comes back.  Per scene ``<scene_id>.<res_nam
 The configuration is the checkpoint's, overridden by the command line, exactly as ``deflow_amd.eval`` resolves it.  ``res_name`` defaults
 to the checkpoint's file stem; ``ground_source=auto|file|sidecar`` as ``HDF5Dataset`` reads masks, ``online`` computes them on the GPU per
 batch (``ground.GroundSegmenter``) and needs no mask on disk.  ``av2_mode`` is refused: the leaderboard submission (a zip of feather files) is
-``python -m deflow_amd.eval checkpoint=<ckpt> av2_mode=test dataset_path=<root>``."""
+``python -m deflow_amd.eval checkpoint=<ckpt> av2_mode=test dataset_path=<root>``.
+
+``python -m deflow_amd.save model=icpflow dataset_path=<dir> [res_name=icpflow] [ground_source=...] [icp_*=...]`` needs no checkpoint: the
+flow comes from the training-free rigid cluster flow of ``deflow_amd.rigid`` (UNPINNED).  ``voxel_size`` and
+``point_cloud_range`` decide which rows are decoded, the ``icp_*`` keys (``rigid.COMMAND_KEYS``) are its parameters; all of them go into
+the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` then trains on the file as pseudo labels."""
 from __future__ import annotations
 
 import json
@@ -35,6 +40,10 @@ OWN_DEFAULTS: Dict[str, Any] = {"checkpoint": None, "dataset_path": None, "res_n
                                 "half": False, "overwrite": False, "inference_dtype": None}
 USAGE = ("usage: python -m deflow_amd.save checkpoint=<ckpt> dataset_path=<dir of .h5 files> [res_name=<checkpoint file stem>] [scenes=a,b] "
          "[batch_size=] [num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [inference_dtype=fp32|bf16]")
+ICP_USAGE = ("usage: python -m deflow_amd.save model=icpflow dataset_path=<dir of .h5 files> [res_name=icpflow] [scenes=a,b] [batch_size=] "
+             "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
+             "[icp_eps=] [icp_min_points=] [icp_min_cluster_size=] [icp_min_side=] [icp_max_cluster_points=] [icp_vote_cap=] [icp_vote_bin=] "
+             "[icp_max_disp=] [icp_cap=] [icp_iters=] [icp_max_dist=] [icp_min_inlier_frac=] [icp_max_yaw=]")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -46,8 +55,10 @@ def _flag(k: str, v: str) -> bool:
 def parse_args(argv: List[str]) -> Dict[str, Any]:
     """key=value arguments -> this command's own options, plus under ``_rest`` ({key: "key=value"}) the hyper-parameter overrides that
     ``eval.resolve_config`` lays over the checkpoint's configuration.  Reads no file."""
+    from .rigid import COMMAND_KEYS, params_from_command
     opt = dict(OWN_DEFAULTS)
     rest: Dict[str, str] = {}
+    icp: Dict[str, str] = {}
     for a in argv:
         if "=" not in a:
             raise SystemExit(f"expected key=value, got {a!r}")
@@ -73,6 +84,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             if v not in ("fp32", "bf16"):
                 raise SystemExit(f"bad value for inference_dtype: {v!r} (fp32, bf16)")
             opt[k] = v
+        elif k in COMMAND_KEYS:
+            icp[k] = v
         elif k in DEFAULTS or k in _TARGET_ALIASES or k == "model.target.grid_feature_size":
             if k in ("batch_size", "num_workers"):
                 try:
@@ -84,7 +97,19 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             rest[k] = f"{k}={v}"
         else:
             raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted(OWN_DEFAULTS))}, and the hyper-parameters of deflow_amd.train")
-    if not opt["checkpoint"] or not opt["dataset_path"]:
+    opt["icpflow"] = rest.get("model") == "model=icpflow" or rest.get("model.name") == "model.name=icpflow"
+    if opt["icpflow"]:
+        if opt["checkpoint"] or opt["inference_dtype"]:
+            raise SystemExit("model=icpflow has no weights: it takes neither checkpoint= nor inference_dtype=\n" + ICP_USAGE)
+        if not opt["dataset_path"]:
+            raise SystemExit(ICP_USAGE)
+        rest.pop("model", None), rest.pop("model.name", None)
+        opt["icp"] = params_from_command(icp)
+        if opt["res_name"] is None:
+            opt["res_name"] = "icpflow"
+    elif icp:
+        raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + ICP_USAGE)
+    elif not opt["checkpoint"] or not opt["dataset_path"]:
         raise SystemExit(USAGE)
     if opt["res_name"] is None:
         opt["res_name"] = os.path.splitext(os.path.basename(opt["checkpoint"]))[0]
@@ -199,23 +224,32 @@ def main(argv=None) -> int:
     assert torch.cuda.is_available(), "the save command runs on the HIP engine only"
     from .eval import resolve_config
     from .sweeps import SweepFlow
-    from .train import build_model
-    cfg = resolve_config(opt["checkpoint"], opt["_rest"])
+    from .train import build_model, parse_overrides
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
-    model = build_model(cfg).to(dev)
-    res = model.load_from_checkpoint(opt["checkpoint"])
-    if res.missing_keys or res.unexpected_keys:
-        print(f"[deflow_amd.save] WARNING: checkpoint / model mismatch (model={cfg['model']}): {len(res.missing_keys)} missing keys "
-              f"{res.missing_keys[:4]}..., {len(res.unexpected_keys)} unexpected keys {res.unexpected_keys[:4]}...", file=sys.stderr)
-    model.eval()
-    if opt["inference_dtype"]:
-        model.inference_dtype = opt["inference_dtype"]
     d, res_name, online = opt["dataset_path"], opt["res_name"], opt["ground_source"] == "online"
+    if opt["icpflow"]:
+        # no checkpoint, no weights: the configuration is the defaults under the command line
+        from .rigid import IcpFlow
+        cfg = parse_overrides(list(opt["_rest"].values()))
+        model = IcpFlow(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["icp"])
+        meta = {"res_name": res_name, "checkpoint": None, "model": "icpflow", "voxel_size": [float(v) for v in cfg["voxel_size"]],
+                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
+                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6j (UNPINNED)"}
+    else:
+        cfg = resolve_config(opt["checkpoint"], opt["_rest"])
+        model = build_model(cfg).to(dev)
+        res = model.load_from_checkpoint(opt["checkpoint"])
+        if res.missing_keys or res.unexpected_keys:
+            print(f"[deflow_amd.save] WARNING: checkpoint / model mismatch (model={cfg['model']}): {len(res.missing_keys)} missing keys "
+                  f"{res.missing_keys[:4]}..., {len(res.unexpected_keys)} unexpected keys {res.unexpected_keys[:4]}...", file=sys.stderr)
+        model.eval()
+        if opt["inference_dtype"]:
+            model.inference_dtype = opt["inference_dtype"]
+        meta = {"res_name": res_name, "checkpoint": os.path.basename(opt["checkpoint"]), "model": cfg["model"],
+                "voxel_size": [float(v) for v in cfg["voxel_size"]], "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]],
+                "ground_source": opt["ground_source"], "half": bool(opt["half"]), "definition": "DESIGN.md 6f (UNPINNED)"}
     scenes = opt["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
-    meta = {"res_name": res_name, "checkpoint": os.path.basename(opt["checkpoint"]), "model": cfg["model"],
-            "voxel_size": [float(v) for v in cfg["voxel_size"]], "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]],
-            "ground_source": opt["ground_source"], "half": bool(opt["half"]), "definition": "DESIGN.md 6f (UNPINNED)"}
     flows_for: Dict[int, SweepFlow] = {}
 
     def sweep_flow_for(B: int) -> SweepFlow:

@@ -18,7 +18,11 @@ over batches when all batches are equal-sized and carry every key.  The key is n
 
 ``augment=true`` augments every training batch on the GPU (deflow_amd/augment.py: flip, yaw, height, jitter, point dropout; one launch, a pure
 function of (seed, epoch, sample id, row), so a resumed run repeats exactly); ``aug_flip_x_p``, ``aug_flip_y_p``, ``aug_yaw_deg``,
-``aug_height``, ``aug_jitter_sigma`` and ``aug_drop_p`` are its arguments.  Validation batches are never augmented."""
+``aug_height``, ``aug_jitter_sigma`` and ``aug_drop_p`` are its arguments.  Validation batches are never augmented.
+
+``pseudo_flow=<res_name>``: training pairs whose scene files hold no ``flow`` take it from ``<scene_id>.<res_name>.flow.npz``, the file
+``python -m deflow_amd.save`` writes (``HDF5Dataset(flow_sidecar=...)``) -- with ``save model=icpflow`` the pseudo labels that
+``loss_fn=zeroflowLoss`` distils.  Like ``metrics_impl`` it is not a hyper-parameter and is never saved."""
 from __future__ import annotations
 
 import ast
@@ -71,6 +75,21 @@ def split_metrics_impl(args: List[str]):
     if impl not in METRICS_IMPLS:
         raise SystemExit(f"metrics_impl must be one of {', '.join(METRICS_IMPLS)}, got {impl!r}")
     return impl, rest
+
+
+def split_pseudo_flow(args: List[str]):
+    """-> (res_name or None, the other arguments).  ``pseudo_flow=<res_name>``: training pairs whose scene files hold no ``flow`` take it
+    from ``<scene_id>.<res_name>.flow.npz`` (``python -m deflow_amd.save``, e.g. with model=icpflow: pseudo labels for
+    loss_fn=zeroflowLoss).  Says where labels are READ: not a hyper-parameter, never saved.  The last one wins."""
+    name, rest = None, []
+    for a in args:
+        if a.lstrip("+").split("=", 1)[0] == "pseudo_flow" and "=" in a:
+            name = a.split("=", 1)[1]
+            if not name or os.sep in name:
+                raise SystemExit(f"bad value for pseudo_flow: {name!r} (the res_name of a python -m deflow_amd.save run)")
+        else:
+            rest.append(a)
+    return name, rest
 
 
 def parse_overrides(argv: List[str]) -> Dict[str, Any]:
@@ -187,7 +206,10 @@ def save_checkpoint(path: str, model, trainer, cfg, epoch: int, step: int):
 
 def main(argv=None):
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
+    pseudo_flow, args = split_pseudo_flow(args)
     cfg = parse_overrides(args)
+    if pseudo_flow and cfg["train_data"] == "synthetic":
+        raise SystemExit("pseudo_flow=<res_name> reads <scene_id>.<res_name>.flow.npz beside scene files: name them with train_data= or dataset_path=")
     rank = int(os.environ.get("RANK", "0")); local = int(os.environ.get("LOCAL_RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     assert torch.cuda.is_available(), "training runs on the HIP engine only"
     local = local % torch.cuda.device_count()      # more ranks than GPUs only in tests (dist_backend=gloo, ranks share a device)
@@ -232,7 +254,7 @@ def main(argv=None):
             if world > 1:
                 dist.barrier()
             path = dst
-        ds = HDF5Dataset(path)
+        ds = HDF5Dataset(path, flow_sidecar=pseudo_flow if shuffle else None)      # (pseudo labels are for training pairs only)
         sampler = ShardedSampler(len(ds), rank, world, shuffle=shuffle, seed=int(cfg["seed"]))
         return SceneLoader(ds, B, sampler, device=dev, num_workers=max(0, int(cfg["num_workers"])), drop_last=shuffle), sampler
 

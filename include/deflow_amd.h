@@ -876,6 +876,60 @@ int df_render_splat(const float* points, const float* vec, const uint8_t* cls, c
                     float inv_res, int W, int H, float vmax, int radius, uint64_t* image, void* stream);
 int df_render_resolve(const uint64_t* image, int B, int W, int H, int bg_rgb, int legend, uint8_t* scanlines, void* stream);
 
+/* ------------------------------------------------------------------ rigid cluster flow (model=icpflow) ----
+ * UNPINNED: the recipe follows ICP-Flow (Lin & Caesar, CVPR'24) -- ego-compensate, cluster both sweeps together, register each cluster
+ * rigidly, read the flow off the transform -- but upstream's source is absent and every choice below is this project's own (DESIGN.md
+ * section 6j).  Lengths in metres; fp32(.) is one correctly rounded operation.  Per sample: pc0s [N0,3] (first sweep, ground removed, moved
+ * into the second sweep's frame by df_ego_transform), pc1 [N1,3], count0 / count1 valid leading rows.  N = N0 + N1.
+ *   a. clusters  labels [B,N] i32 of the concatenation (pc0s rows, then pc1 rows): df_dbscan_* with eps = 0.7, min_points = 4,
+ *                min_cluster_size = 20 over the valid finite rows (0 = none, 1..K).  Slot k = label - 1 < Kcap = max(N / min_cluster_size, 1).
+ *                A slot's SOURCE rows are its rows < N0, its TARGET rows those >= N0, both in ascending row order.
+ *   b. status    exactly one per slot, tested in this order: 0 no rows; 2 fewer than min_side (8) source or target rows; 3 more than
+ *                max_cluster_points (8192) rows in all; 5 no vote in range (c); 4 / 5 / 1 from (e).
+ *   c. vote      a side of n > vote_cap (1024) rows uses entries j * n / vote_cap (integer division, j = 0 .. vote_cap - 1) of its list,
+ *                else all.  Every used pair (s, d): ix = floor(fp32(fp32(fp32(d.x - s.x) / vote_bin) + 0.5)), iy alike; R = ceil(max_disp /
+ *                vote_bin) on the host (3.4 / 0.2: 17).  |ix| <= R and |iy| <= R adds one to an i32 counter.  Winner: most votes, on equal
+ *                counts the lowest (iy + R) (2R + 1) + (ix + R).  t0 = (fp32(ix vote_bin), fp32(iy vote_bin), 0).
+ *   d. icp       yaw + translation.  Coordinates relative to the anchor a = the slot's first source row: s' = fp32(s - a), d' = fp32(d - a).
+ *                Sides over icp_cap (2048) rows are subsampled by the rule of (c).  theta = 0, t = t0; exactly icp_iters (8) iterations:
+ *                p = Rz(theta) s' + t with c = cosf(theta), s = sinf(theta): p.x = fp32(fp32(fp32(c s'.x) - fp32(s s'.y)) + t.x),
+ *                p.y = fp32(fp32(fp32(s s'.x) + fp32(c s'.y)) + t.y), p.z = fp32(s'.z + t.z); nearest used target row by
+ *                d2 = fp32(fp32(fp32(dx dx) + fp32(dy dy)) + fp32(dz dz)), dx = fp32(p.x - d'.x) ..., the lowest position on equal d2;
+ *                inlier when d2 <= fp32(icp_max_dist icp_max_dist) (0.5).  With n >= 3 inliers: ms = sum(s') / n, md = sum(d') / n,
+ *                u = s' - ms, v = d' - md, theta = atan2f(sum(u.x v.y - u.y v.x), sum(u.x v.x + u.y v.y)), t = md - Rz(theta) ms
+ *                (t.z = md.z - ms.z); with fewer the transform stays.  Sums run in a fixed order (a lane adds its rows in ascending order,
+ *                then a fixed tree): two calls are bit-identical.  One more nearest-neighbour pass with the final transform:
+ *                inlier_frac = fp32(inliers / used source rows).
+ *   e. accept    status 4 unless inlier_frac >= min_inlier_frac (0.6); else status 5 unless |theta| <= max_yaw (0.35) and the centroid c of
+ *                the used source rows moves by at most max_disp: |Rz(theta) c + t - c|^2 <= fp32(max_disp max_disp); else status 1.
+ *   f. rows      a source row of a status-1 slot: flow = (fp32(p.x - s'.x), fp32(p.y - s'.y), t.z), p as in (d) with the final transform;
+ *                rigid_id = its label.  Every other row of pc0s, padded and non-finite ones included: flow = (0, 0, 0), rigid_id = 0.
+ * df_rigid_segments: labels -> seg_off [B, 2 Kcap + 1] i32 (list 2k: sources of slot k, 2k + 1: its targets; list l is seg_rows[b][seg_off[l]
+ *   .. seg_off[l + 1])), seg_rows [B,N] i32 (rows of the concatenation, -1 behind the last list).  Integer counts, one scan, and a scatter
+ *   in which one block per sample walks the rows in order: the lists are stable.  status i32[1] (zeroed by the caller) is added to for a
+ *   label outside [0, Kcap] or a row that finds no place.  ws: df_rigid_segments_ws_bytes(B, N0, N1, Kcap) bytes.
+ * df_rigid_vote: -> vote [B,Kcap,3] i32 (ix, iy, count; zeros for slots that are not registered); hist (nullable) [B,Kcap,2R+1,2R+1] i32,
+ *   the whole histogram, [iy + R][ix + R].  0 <= R <= 64.
+ * df_rigid_icp: -> table [B,Kcap,8] f32 = (theta, tx, ty, tz, inlier_frac, n_src, n_dst, status); the first five are 0 for status 0, 2, 3
+ *   and for a slot without a vote.  ws: df_rigid_icp_ws_bytes(B, N0, N1) bytes.
+ * df_rigid_apply: -> flow [B,N0,3] f32, rigid_id [B,N0] i32, every element written exactly once.
+ * 1 <= B <= 65535, N0, N1 >= 1, B * N < 2^31, 1 <= Kcap <= N, R <= 64: violations return DF_E_SHAPE (the _ws_bytes functions return it
+ * too); NULL buffers, min_side / max_cluster_points / caps < 1, icp_iters outside [0, 1024], a non-positive or non-finite vote_bin /
+ * icp_max_dist, a negative or non-finite max_yaw / max_disp: DF_E_ARG.  ws 4-byte aligned (DF_E_ALIGN).  No launch then.  Grids come from
+ * N and Kcap, never from a device value; no float atomics; the entries never allocate or synchronise and read nothing back. */
+int64_t df_rigid_segments_ws_bytes(int B, int N0, int N1, int Kcap);
+int df_rigid_segments(const int32_t* labels, int B, int N0, int N1, int Kcap, int32_t* seg_off, int32_t* seg_rows, int32_t* status, void* ws,
+                      void* stream);
+int df_rigid_vote(const float* pc0s, const float* pc1, const int32_t* seg_off, const int32_t* seg_rows, int B, int N0, int N1, int Kcap,
+                  int min_side, int max_cluster_points, int vote_cap, float vote_bin, int R, int32_t* vote, int32_t* hist /*nullable*/,
+                  void* stream);
+int64_t df_rigid_icp_ws_bytes(int B, int N0, int N1);
+int df_rigid_icp(const float* pc0s, const float* pc1, const int32_t* seg_off, const int32_t* seg_rows, const int32_t* vote, int B, int N0,
+                 int N1, int Kcap, int min_side, int max_cluster_points, int icp_cap, int icp_iters, float vote_bin, float icp_max_dist,
+                 float min_inlier_frac, float max_yaw, float max_disp, float* table, void* ws, void* stream);
+int df_rigid_apply(const float* pc0s, const int32_t* count0, const int32_t* labels, const int32_t* seg_off, const int32_t* seg_rows,
+                   const float* table, int B, int N0, int N1, int Kcap, float* flow, int32_t* rigid_id, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
