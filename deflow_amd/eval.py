@@ -176,6 +176,24 @@ def icpflow_config(given: Dict[str, str]):
     return cfg, params_from_command(icp)
 
 
+def nsfp_config(given: Dict[str, str]):
+    """``model=nsfp``: (configuration, nsfp parameters) from the command line alone, as ``icpflow_config``; batch_size defaults to
+    nsfp.COMMAND_BATCH_SIZE.  ``icp_*`` keys are refused.  Needs no GPU and reads no file."""
+    from . import nsfp, rigid
+    for k in ("checkpoint", "inference_dtype"):
+        if k in given:
+            raise SystemExit(f"model=nsfp has no weights: it takes no {k}=")
+    wrong = sorted(k for k in given if k in rigid.COMMAND_KEYS)
+    if wrong:
+        raise SystemExit(f"{', '.join(wrong)}: the icp_* keys belong to model=icpflow")
+    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in nsfp.COMMAND_KEYS}
+    cfg = parse_overrides([a for k, a in given.items() if k not in nsfp.COMMAND_KEYS and k != "model"])
+    cfg["model"] = "nsfp"
+    if "batch_size" not in given:
+        cfg["batch_size"] = nsfp.COMMAND_BATCH_SIZE
+    return cfg, nsfp.params_from_command(own)
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
@@ -184,15 +202,27 @@ def main(argv=None):
     if icpflow and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         raise SystemExit("model=icpflow writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
                          "metrics, python -m deflow_amd.save model=icpflow writes its flow")
+    is_nsfp = given.get("model") == "model=nsfp"
+    if is_nsfp and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        raise SystemExit("model=nsfp writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
+                         "metrics, python -m deflow_amd.save model=nsfp writes its flow")
+    if not is_nsfp and not icpflow:
+        from .nsfp import COMMAND_KEYS as NSFP_KEYS
+        wrong = sorted(k for k in given if k in NSFP_KEYS)
+        if wrong:
+            raise SystemExit(f"{', '.join(wrong)}: the nsfp_* keys belong to model=nsfp")
     if given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         return main_test(args)          # the leaderboard submission: no metrics (the test split has no labels)
     if given.get("av2_mode", "av2_mode=val") != "av2_mode=val":
         raise SystemExit(f"unknown {given['av2_mode']} (val: the metrics, test: the leaderboard submission)")
     if icpflow:
         (cfg, icp_params), path = icpflow_config(given), None
+    elif is_nsfp:
+        (cfg, nsfp_params), path = nsfp_config(given), None
     elif "checkpoint" not in given:
         raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE +
-                         "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]")
+                         "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]"
+                         "\n       python -m deflow_amd.eval model=nsfp [av2_mode=val] [val_data=<dir>|synthetic] [nsfp_*=]")
     else:
         path = given["checkpoint"].split("=", 1)[1]
         cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
@@ -216,6 +246,9 @@ def main(argv=None):
     if icpflow:
         from .rigid import IcpFlow
         model = IcpFlow(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **icp_params)
+    elif is_nsfp:
+        from .nsfp import Nsfp
+        model = Nsfp(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **nsfp_params)
     else:
         model = build_model(cfg).to(dev)
         res = model.load_from_checkpoint(path)

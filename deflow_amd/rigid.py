@@ -189,23 +189,22 @@ def rigid_cluster_flow(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tens
     return flow, rigid_id, table, vote, status
 
 
-class IcpFlow:
-    """``model=icpflow``: an object with the two methods of ``DeFlow`` the commands use -- ``forward_padded`` and ``forward`` -- and no
-    weights.  ``sweeps.SweepFlow``, ``metrics.evaluate_batch`` and ``metrics_device.evaluate_batch_device`` take it as they take the model.
-    point_cloud_range / voxel_size decide which rows count as decoded, by the voxeliser's rule (floor((p - min) / voxel) inside the grid on
-    all three axes, on the ego-compensated rows); every other keyword is a parameter of ``rigid_cluster_flow``."""
+class PairFlowModel:
+    """What the weight-free estimators (``IcpFlow``, ``nsfp.Nsfp``) share: an object with the two methods of ``DeFlow`` the commands use --
+    ``forward_padded`` and ``forward`` -- and no weights.  point_cloud_range / voxel_size decide which rows count as decoded, by the
+    voxeliser's rule (floor((p - min) / voxel) inside the grid on all three axes, on the ego-compensated rows)."""
 
-    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
+    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6)):
+        name = type(self).__name__
         if len(point_cloud_range) != 6 or len(voxel_size) != 3:
-            raise ValueError("IcpFlow: point_cloud_range has 6 values and voxel_size 3")
+            raise ValueError(f"{name}: point_cloud_range has 6 values and voxel_size 3")
         self.point_cloud_range = [float(v) for v in point_cloud_range]
         self.voxel_size = [float(v) for v in voxel_size]
         if not all(v > 0 for v in self.voxel_size):
-            raise ValueError(f"IcpFlow: voxel_size must be positive, got {voxel_size}")
+            raise ValueError(f"{name}: voxel_size must be positive, got {voxel_size}")
         self.grid = [int(round((self.point_cloud_range[3 + i] - self.point_cloud_range[i]) / self.voxel_size[i])) for i in range(3)]
         if not all(g >= 1 for g in self.grid):
-            raise ValueError(f"IcpFlow: empty point_cloud_range {point_cloud_range}")
-        self.params = check_params(params)
+            raise ValueError(f"{name}: empty point_cloud_range {point_cloud_range}")
         self.training = False
         self.last_state: Optional[dict] = None
 
@@ -233,14 +232,13 @@ class IcpFlow:
         idx = torch.argsort((~valid).to(torch.uint8), dim=1, stable=True)
         return idx, valid.sum(dim=1).to(torch.int32)
 
-    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
-        """flow [B,N,3]: row i < counts0[b] is the flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind them;
-        pose_flow [B,N,3] of every input row; pc0s the ego-compensated rows.  Reads nothing back."""
+    def _pair(self, batch: Dict[str, torch.Tensor]) -> dict:
+        """the ego-compensated first sweep, the pose flow of every input row, and both sweeps' decoded rows compacted (stable)"""
         from .deflow import batch_transform
         pc0 = batch["pc0"].contiguous().float()
         pc1 = batch["pc1"].contiguous().float()
         if not pc0.is_cuda or not pc1.is_cuda:
-            raise TypeError("IcpFlow: pc0 and pc1 must be CUDA tensors (deflow_amd has no CPU fallback)")
+            raise TypeError(f"{type(self).__name__}: pc0 and pc1 must be CUDA tensors (deflow_amd has no CPU fallback)")
         B, N, _ = pc0.shape
         T = batch_transform(batch, pc0.device)
         pc0s = torch.empty_like(pc0)
@@ -251,12 +249,11 @@ class IcpFlow:
         idx1, counts1 = self._compact(v1)
         g0 = torch.gather(pc0s, 1, idx0[..., None].expand(-1, -1, 3))
         g1 = torch.gather(pc1, 1, idx1[..., None].expand(-1, -1, 3))
-        r = self.point_cloud_range
-        flow, rigid_id, table, vote, status = rigid_cluster_flow(g0, counts0, g1, counts1, grid_range=(r[0], r[1], r[3], r[4]), **self.params)
-        self.last_state = {"flow": flow, "pose_flow": pose_flow, "counts0": counts0, "counts1": counts1, "idx_c0": idx0, "idx_c1": idx1,
-                           "pc0s": pc0s, "points_c0": g0, "points_c1": g1, "rigid_id": rigid_id, "table": table, "vote": vote,
-                           "status": status}
-        return self.last_state
+        return {"pose_flow": pose_flow, "counts0": counts0, "counts1": counts1, "idx_c0": idx0, "idx_c1": idx1, "pc0s": pc0s,
+                "points_c0": g0, "points_c1": g1}
+
+    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
+        raise NotImplementedError
 
     def forward(self, batch: Dict[str, torch.Tensor]):
         """the dict of lists ``DeFlow.forward`` returns (one host read: the per-sample counts)"""
@@ -273,4 +270,27 @@ class IcpFlow:
             "pc1_points_lst": [st["points_c1"][b, :m1[b]] for b in range(B)],
         }
 
-    __call__ = forward
+    def __call__(self, batch):
+        return self.forward(batch)
+
+
+class IcpFlow(PairFlowModel):
+    """``model=icpflow``: an object with the two methods of ``DeFlow`` the commands use -- ``forward_padded`` and ``forward`` -- and no
+    weights.  ``sweeps.SweepFlow``, ``metrics.evaluate_batch`` and ``metrics_device.evaluate_batch_device`` take it as they take the model.
+    point_cloud_range / voxel_size decide which rows count as decoded, by the voxeliser's rule (floor((p - min) / voxel) inside the grid on
+    all three axes, on the ego-compensated rows); every other keyword is a parameter of ``rigid_cluster_flow``."""
+
+    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
+        super().__init__(point_cloud_range, voxel_size)
+        self.params = check_params(params)
+
+    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
+        """flow [B,N,3]: row i < counts0[b] is the flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind them;
+        pose_flow [B,N,3] of every input row; pc0s the ego-compensated rows.  Reads nothing back."""
+        st = self._pair(batch)
+        r = self.point_cloud_range
+        flow, rigid_id, table, vote, status = rigid_cluster_flow(st["points_c0"], st["counts0"], st["points_c1"], st["counts1"],
+                                                                 grid_range=(r[0], r[1], r[3], r[4]), **self.params)
+        st.update({"flow": flow, "rigid_id": rigid_id, "table": table, "vote": vote, "status": status})
+        self.last_state = st
+        return st

@@ -17,7 +17,10 @@ batch (``ground.GroundSegmenter``) and needs no mask on disk.  ``av2_mode`` is r
 ``python -m deflow_amd.save model=icpflow dataset_path=<dir> [res_name=icpflow] [ground_source=...] [icp_*=...]`` needs no checkpoint: the
 flow comes from the training-free rigid cluster flow of ``deflow_amd.rigid`` (UNPINNED).  ``voxel_size`` and
 ``point_cloud_range`` decide which rows are decoded, the ``icp_*`` keys (``rigid.COMMAND_KEYS``) are its parameters; all of them go into
-the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` then trains on the file as pseudo labels."""
+the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` then trains on the file as pseudo labels.
+
+``python -m deflow_amd.save model=nsfp dataset_path=<dir> [res_name=nsfp] [nsfp_*=...]`` is the same for the per-pair neural flow prior of
+``deflow_amd.nsfp`` (UNPINNED): no checkpoint, the ``nsfp_*`` keys (``nsfp.COMMAND_KEYS``) in the file's ``meta``."""
 from __future__ import annotations
 
 import json
@@ -44,6 +47,11 @@ ICP_USAGE = ("usage: python -m deflow_amd.save model=icpflow dataset_path=<dir o
              "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
              "[icp_eps=] [icp_min_points=] [icp_min_cluster_size=] [icp_min_side=] [icp_max_cluster_points=] [icp_vote_cap=] [icp_vote_bin=] "
              "[icp_max_disp=] [icp_cap=] [icp_iters=] [icp_max_dist=] [icp_min_inlier_frac=] [icp_max_yaw=]")
+NSFP_USAGE = ("usage: python -m deflow_amd.save model=nsfp dataset_path=<dir of .h5 files> [res_name=nsfp] [scenes=a,b] [batch_size=2] "
+              "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
+              "[nsfp_depth=7] [nsfp_iters=1000] [nsfp_lr=8e-3] [nsfp_trunc_d2=4.0] [nsfp_patience=100] [nsfp_min_delta=1e-4] "
+              "[nsfp_check_every=50] [nsfp_seed=0] [nsfp_graph=false]\n"
+              "batch_size defaults to 2: the saved activations are (nsfp_depth + 1) x N x 512 bytes per net evaluation and sample")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -55,10 +63,12 @@ def _flag(k: str, v: str) -> bool:
 def parse_args(argv: List[str]) -> Dict[str, Any]:
     """key=value arguments -> this command's own options, plus under ``_rest`` ({key: "key=value"}) the hyper-parameter overrides that
     ``eval.resolve_config`` lays over the checkpoint's configuration.  Reads no file."""
+    from . import nsfp
     from .rigid import COMMAND_KEYS, params_from_command
     opt = dict(OWN_DEFAULTS)
     rest: Dict[str, str] = {}
     icp: Dict[str, str] = {}
+    own_nsfp: Dict[str, str] = {}
     for a in argv:
         if "=" not in a:
             raise SystemExit(f"expected key=value, got {a!r}")
@@ -86,6 +96,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             opt[k] = v
         elif k in COMMAND_KEYS:
             icp[k] = v
+        elif k in nsfp.COMMAND_KEYS:
+            own_nsfp[k] = v
         elif k in DEFAULTS or k in _TARGET_ALIASES or k == "model.target.grid_feature_size":
             if k in ("batch_size", "num_workers"):
                 try:
@@ -98,7 +110,22 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         else:
             raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted(OWN_DEFAULTS))}, and the hyper-parameters of deflow_amd.train")
     opt["icpflow"] = rest.get("model") == "model=icpflow" or rest.get("model.name") == "model.name=icpflow"
-    if opt["icpflow"]:
+    opt["nsfp"] = rest.get("model") == "model=nsfp" or rest.get("model.name") == "model.name=nsfp"
+    if opt["nsfp"]:
+        if opt["checkpoint"] or opt["inference_dtype"]:
+            raise SystemExit("model=nsfp has no weights: it takes neither checkpoint= nor inference_dtype=\n" + NSFP_USAGE)
+        if icp:
+            raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + NSFP_USAGE)
+        if not opt["dataset_path"]:
+            raise SystemExit(NSFP_USAGE)
+        rest.pop("model", None), rest.pop("model.name", None)
+        rest.setdefault("batch_size", f"batch_size={nsfp.COMMAND_BATCH_SIZE}")
+        opt["nsfp_params"] = nsfp.params_from_command(own_nsfp)
+        if opt["res_name"] is None:
+            opt["res_name"] = "nsfp"
+    elif own_nsfp:
+        raise SystemExit(f"{', '.join(sorted(own_nsfp))}: the nsfp_* keys belong to model=nsfp\n" + NSFP_USAGE)
+    elif opt["icpflow"]:
         if opt["checkpoint"] or opt["inference_dtype"]:
             raise SystemExit("model=icpflow has no weights: it takes neither checkpoint= nor inference_dtype=\n" + ICP_USAGE)
         if not opt["dataset_path"]:
@@ -236,6 +263,13 @@ def main(argv=None) -> int:
         meta = {"res_name": res_name, "checkpoint": None, "model": "icpflow", "voxel_size": [float(v) for v in cfg["voxel_size"]],
                 "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
                 "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6j (UNPINNED)"}
+    elif opt["nsfp"]:
+        from .nsfp import Nsfp
+        cfg = parse_overrides(list(opt["_rest"].values()))
+        model = Nsfp(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["nsfp_params"])
+        meta = {"res_name": res_name, "checkpoint": None, "model": "nsfp", "voxel_size": [float(v) for v in cfg["voxel_size"]],
+                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
+                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6k (UNPINNED)"}
     else:
         cfg = resolve_config(opt["checkpoint"], opt["_rest"])
         model = build_model(cfg).to(dev)

@@ -930,6 +930,29 @@ int df_rigid_icp(const float* pc0s, const float* pc1, const int32_t* seg_off, co
 int df_rigid_apply(const float* pc0s, const int32_t* count0, const int32_t* labels, const int32_t* seg_off, const int32_t* seg_rows,
                    const float* table, int B, int N0, int N1, int Kcap, float* flow, int32_t* rigid_id, void* stream);
 
+/* ------------------------------------------------------------------ per-row coordinate MLP (model=nsfp) ----
+ * The hot path of the per-pair neural flow prior.  UNPINNED: upstream's NSFP source is absent; the definition is
+ * this project's own.  One net is a map R^3 -> R^3 in fp32, width H = 128 (compile time), `depth` hidden-to-hidden layers (0..15):
+ *   a_0 = relu(W_in x + b_in);  a_l = relu(W_l a_{l-1} + b_l), l = 1..depth;  y = W_out a_depth + b_out;  relu'(z) = 1 for z > 0, else 0.
+ * Its parameters are one flat fp32 vector of P = (128*3 + 128) + depth * (128*128 + 128) + (3*128 + 3) elements in the order
+ * W_in[128][3], b_in[128], then per hidden layer W_l[out][in], b_l, then W_out[3][128], b_out[3].  Nets are batched: sample b of
+ * x [B,N,3] uses params + b * param_stride (param_stride >= P, a multiple of 4, params 16-byte aligned), count [B] i32 valid leading rows.
+ * Rows >= count[b] contribute nothing; y and dx are written as 0 there (their x and dy are never used: NaN padding is legal); count 0 is legal.
+ * df_mlp_fwd: y [B,N,3]; acts (nullable: inference) [B, depth+1, N, 128] f32 = a_0 .. a_depth of every row < N, what df_mlp_bwd reads.
+ * df_mlp_bwd: dy [B,N,3] = d loss / d y -> dparams [B] blocks at param_stride floats, EVERY element of a block written (P elements, and the padding up
+ *   to the next multiple of 4 as 0; what lies between two blocks of a wider stride is not touched), not accumulated; dx (nullable) [B,N,3] = d loss / d x.  The ReLU masks are acts > 0.  ws: df_mlp_ws_bytes(B, N, depth) bytes, 16-byte
+ *   aligned: the pre-activation gradients of every layer [B, depth+1, N, 128] and one partial parameter gradient per sample and split of
+ *   1024 rows, which are added in ascending split order (rows inside a split in ascending order too): no float atomics, two calls are
+ *   bit-identical, and a sample's dparams depend on neither B nor the other samples of the launch at equal N.
+ * The 128 x 128 products (forward, data gradient, weight gradient) run on v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation.
+ * 1 <= B <= 65535, N >= 1, 3 B N < 2^31, 0 <= depth <= 15, param_stride as above: else DF_E_SHAPE (df_mlp_ws_bytes returns it too); NULL
+ * required pointers: DF_E_ARG; misaligned params / acts / ws: DF_E_ALIGN.  No launch then.  Grids come from B, N and depth only. */
+int64_t df_mlp_ws_bytes(int B, int N, int depth);
+int df_mlp_fwd(const float* x, const int32_t* count, const float* params, int64_t param_stride, int B, int N, int depth, float* y,
+               float* acts /*nullable*/, void* stream);
+int df_mlp_bwd(const float* x, const int32_t* count, const float* params, int64_t param_stride, const float* acts, const float* dy, int B,
+               int N, int depth, float* dparams, float* dx /*nullable*/, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
