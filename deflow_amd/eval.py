@@ -194,6 +194,27 @@ def nsfp_config(given: Dict[str, str]):
     return cfg, nsfp.params_from_command(own)
 
 
+def fastnsf_config(given: Dict[str, str]):
+    """``model=fastnsf``: (configuration, fastnsf parameters) from the command line alone, as ``nsfp_config``; batch_size defaults to
+    fastnsf.COMMAND_BATCH_SIZE.  ``icp_*`` and ``nsfp_*`` keys are refused.  Needs no GPU and reads no file."""
+    from . import fastnsf, nsfp, rigid
+    for k in ("checkpoint", "inference_dtype"):
+        if k in given:
+            raise SystemExit(f"model=fastnsf has no weights: it takes no {k}=")
+    wrong = sorted(k for k in given if k in rigid.COMMAND_KEYS)
+    if wrong:
+        raise SystemExit(f"{', '.join(wrong)}: the icp_* keys belong to model=icpflow")
+    wrong = sorted(k for k in given if k in nsfp.COMMAND_KEYS)
+    if wrong:
+        raise SystemExit(f"{', '.join(wrong)}: the nsfp_* keys belong to model=nsfp")
+    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in fastnsf.COMMAND_KEYS}
+    cfg = parse_overrides([a for k, a in given.items() if k not in fastnsf.COMMAND_KEYS and k != "model"])
+    cfg["model"] = "fastnsf"
+    if "batch_size" not in given:
+        cfg["batch_size"] = fastnsf.COMMAND_BATCH_SIZE
+    return cfg, fastnsf.params_from_command(own)
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
@@ -206,7 +227,16 @@ def main(argv=None):
     if is_nsfp and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         raise SystemExit("model=nsfp writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
                          "metrics, python -m deflow_amd.save model=nsfp writes its flow")
-    if not is_nsfp and not icpflow:
+    is_fastnsf = given.get("model") == "model=fastnsf"
+    if is_fastnsf and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        raise SystemExit("model=fastnsf writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
+                         "metrics, python -m deflow_amd.save model=fastnsf writes its flow")
+    if not is_fastnsf:
+        from .fastnsf import COMMAND_KEYS as FASTNSF_KEYS
+        wrong = sorted(k for k in given if k in FASTNSF_KEYS)
+        if wrong:
+            raise SystemExit(f"{', '.join(wrong)}: the fastnsf_* keys belong to model=fastnsf")
+    if not is_nsfp and not icpflow and not is_fastnsf:
         from .nsfp import COMMAND_KEYS as NSFP_KEYS
         wrong = sorted(k for k in given if k in NSFP_KEYS)
         if wrong:
@@ -219,10 +249,13 @@ def main(argv=None):
         (cfg, icp_params), path = icpflow_config(given), None
     elif is_nsfp:
         (cfg, nsfp_params), path = nsfp_config(given), None
+    elif is_fastnsf:
+        (cfg, fastnsf_params), path = fastnsf_config(given), None
     elif "checkpoint" not in given:
         raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE +
                          "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]"
-                         "\n       python -m deflow_amd.eval model=nsfp [av2_mode=val] [val_data=<dir>|synthetic] [nsfp_*=]")
+                         "\n       python -m deflow_amd.eval model=nsfp [av2_mode=val] [val_data=<dir>|synthetic] [nsfp_*=]"
+                         "\n       python -m deflow_amd.eval model=fastnsf [av2_mode=val] [val_data=<dir>|synthetic] [fastnsf_*=]")
     else:
         path = given["checkpoint"].split("=", 1)[1]
         cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
@@ -249,6 +282,9 @@ def main(argv=None):
     elif is_nsfp:
         from .nsfp import Nsfp
         model = Nsfp(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **nsfp_params)
+    elif is_fastnsf:
+        from .fastnsf import FastNsf
+        model = FastNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **fastnsf_params)
     else:
         model = build_model(cfg).to(dev)
         res = model.load_from_checkpoint(path)

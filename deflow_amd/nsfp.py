@@ -235,6 +235,52 @@ def _mean_and_weight(d2: torch.Tensor):
     return total / n, keep.to(torch.float32) / n[:, None]
 
 
+def _loop_state(B: int, iters: int, flow_like: torch.Tensor) -> dict:
+    """the device-side state of the snapshot / freeze rules (shared with deflow_amd.fastnsf)"""
+    dev = flow_like.device
+    return {"best": torch.full((B,), math.inf, dtype=torch.float32, device=dev), "best_flow": torch.zeros_like(flow_like),
+            "stalled": torch.zeros(B, dtype=torch.int32, device=dev), "frozen": torch.zeros(B, dtype=torch.bool, device=dev),
+            "last": torch.zeros(B, dtype=torch.float32, device=dev),
+            "history": torch.zeros(iters, B, dtype=torch.float32, device=dev)}
+
+
+def _snapshot_and_freeze(st: dict, loss: torch.Tensor, F: torch.Tensor, t_dev: torch.Tensor, p: Dict[str, object]) -> None:
+    """snapshot and freeze, predicated: the loss is that of the parameters before this iteration's update"""
+    active = ~st["frozen"]
+    improved = active & (loss < st["best"] - p["min_delta"])
+    st["best"].copy_(torch.where(improved, loss, st["best"]))
+    st["best_flow"].copy_(torch.where(improved[:, None, None], F, st["best_flow"]))
+    st["stalled"].copy_(torch.where(active, torch.where(improved, torch.zeros_like(st["stalled"]), st["stalled"] + 1), st["stalled"]))
+    st["last"].copy_(torch.where(active, loss, st["last"]))
+    st["history"].index_copy_(0, t_dev, st["last"][None])
+    st["frozen"].copy_(st["frozen"] | (st["stalled"] >= p["patience"]))
+    t_dev.add_(1)
+
+
+def _run(iteration, st: dict, p: Dict[str, object]) -> int:
+    """run `iteration` p["iters"] times, eagerly or as one captured iteration replayed, with the early stop -> iterations run"""
+    iters = p["iters"]
+    run = iteration
+    ran = 0
+    if p["graph"] and iters > 1:
+        iteration()                                    # the first iteration eagerly: it also warms the allocator
+        ran = 1
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):                  # one stream: the graph is a linear chain
+            iteration()
+        run = graph.replay
+        # (capturing launches nothing: the captured iteration first runs at the first replay)
+    every = p["check_every"]
+    while ran < iters:
+        run()
+        ran += 1
+        if every and ran % every == 0 and ran < iters and bool(st["frozen"].all()):
+            break
+    if ran < iters:                                    # an early stop changes nothing: the rest of the history is the last value
+        st["history"][ran:] = st["last"][None]
+    return ran
+
+
 def _cloud(name: str, t) -> int:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise TypeError(f"nsfp_optimize: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
@@ -281,10 +327,8 @@ def nsfp_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, c
         t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         search = _Search(B, GRID_RANGE if grid_range is None else grid_range, CELL, p["trunc_d2"], dev)
         grid_p1, grid_p0 = search.build(x1, n1, l1), search.build(x0, n0, l0)
-        st = {"best": torch.full((B,), math.inf, dtype=torch.float32, device=dev), "best_flow": torch.zeros_like(x0),
-              "stalled": torch.zeros(B, dtype=torch.int32, device=dev), "frozen": torch.zeros(B, dtype=torch.bool, device=dev),
-              "last": torch.zeros(B, dtype=torch.float32, device=dev),
-              "history": torch.zeros(iters, B, dtype=torch.float32, device=dev), "nn": None}
+        st = _loop_state(B, iters, x0)
+        st["nn"] = None
         fpar, gpar = arena[:, 0], arena[:, 1]
 
         def iteration():
@@ -307,39 +351,13 @@ def nsfp_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, c
             _, dxW = mlp_backward(W, n0, gpar, depth, acts_g, -dC, need_dx=True, dparams=grads[:, 1])
             dF = ((dW + dC) + dxW) * m0[..., None]
             mlp_backward(x0, n0, fpar, depth, acts_f, dF, need_dx=False, dparams=grads[:, 0])
-            # snapshot and freeze, predicated: the loss is that of the parameters before this update
-            active = ~st["frozen"]
-            improved = active & (loss < st["best"] - p["min_delta"])
-            st["best"].copy_(torch.where(improved, loss, st["best"]))
-            st["best_flow"].copy_(torch.where(improved[:, None, None], F, st["best_flow"]))
-            st["stalled"].copy_(torch.where(active, torch.where(improved, torch.zeros_like(st["stalled"]), st["stalled"] + 1), st["stalled"]))
-            st["last"].copy_(torch.where(active, loss, st["last"]))
-            st["history"].index_copy_(0, t_dev, st["last"][None])
-            st["frozen"].copy_(st["frozen"] | (st["stalled"] >= p["patience"]))
-            t_dev.add_(1)
+            _snapshot_and_freeze(st, loss, F, t_dev, p)
             step_dev.add_(1)
             call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), arena.numel(), p["lr"], BETAS[0], BETAS[1], EPS,
                  ptr(step_dev), 1.0, stream())
             st["nn"] = (i_w1, i_1w, i_c0, i_0c)
 
-        run = iteration
-        ran = 0
-        if p["graph"] and iters > 1:
-            iteration()                                    # the first iteration eagerly: it also warms the allocator
-            ran = 1
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):                  # one stream: the graph is a linear chain
-                iteration()
-            run = graph.replay
-            # (capturing launches nothing: the captured iteration first runs at the first replay)
-        every = p["check_every"]
-        while ran < iters:
-            run()
-            ran += 1
-            if every and ran % every == 0 and ran < iters and bool(st["frozen"].all()):
-                break
-        if ran < iters:                                    # an early stop changes nothing: the rest of the history is the last value
-            st["history"][ran:] = st["last"][None]
+        ran = _run(iteration, st, p)
         flow = st["best_flow"] * m0[..., None]
     info = {"best_loss": st["best"], "loss_history": st["history"], "stalled": st["stalled"], "frozen": st["frozen"], "params": arena,
             "grads": grads, "nn": st["nn"], "iters_run": ran}

@@ -20,7 +20,10 @@ flow comes from the training-free rigid cluster flow of ``deflow_amd.rigid`` (DE
 the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` then trains on the file as pseudo labels.
 
 ``python -m deflow_amd.save model=nsfp dataset_path=<dir> [res_name=nsfp] [nsfp_*=...]`` is the same for the per-pair neural flow prior of
-``deflow_amd.nsfp`` (UNPINNED): no checkpoint, the ``nsfp_*`` keys (``nsfp.COMMAND_KEYS``) in the file's ``meta``."""
+``deflow_amd.nsfp`` (UNPINNED): no checkpoint, the ``nsfp_*`` keys (``nsfp.COMMAND_KEYS``) in the file's ``meta``.
+
+``python -m deflow_amd.save model=fastnsf dataset_path=<dir> [res_name=fastnsf] [fastnsf_*=...]`` likewise for the flow optimised on a
+distance transform of ``deflow_amd.fastnsf`` (UNPINNED), with the ``fastnsf_*`` keys (``fastnsf.COMMAND_KEYS``)."""
 from __future__ import annotations
 
 import json
@@ -52,6 +55,12 @@ NSFP_USAGE = ("usage: python -m deflow_amd.save model=nsfp dataset_path=<dir of 
               "[nsfp_depth=7] [nsfp_iters=1000] [nsfp_lr=8e-3] [nsfp_trunc_d2=4.0] [nsfp_patience=100] [nsfp_min_delta=1e-4] "
               "[nsfp_check_every=50] [nsfp_seed=0] [nsfp_graph=false]\n"
               "batch_size defaults to 2: the saved activations are (nsfp_depth + 1) x N x 512 bytes per net evaluation and sample")
+FASTNSF_USAGE = ("usage: python -m deflow_amd.save model=fastnsf dataset_path=<dir of .h5 files> [res_name=fastnsf] [scenes=a,b] [batch_size=4] "
+                 "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
+                 "[fastnsf_depth=7] [fastnsf_iters=1000] [fastnsf_lr=8e-3] [fastnsf_cell=0.1] [fastnsf_trunc=2.0] [fastnsf_patience=100] "
+                 "[fastnsf_min_delta=1e-4] [fastnsf_check_every=50] [fastnsf_seed=0] [fastnsf_graph=false]\n"
+                 "batch_size defaults to 4: per sample the distance-transform grid (2 bytes per voxel of point_cloud_range / fastnsf_cell, twice "
+                 "while it is built) and the saved activations, (fastnsf_depth + 1) x N x 512 bytes, twice during the backward")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -63,12 +72,13 @@ def _flag(k: str, v: str) -> bool:
 def parse_args(argv: List[str]) -> Dict[str, Any]:
     """key=value arguments -> this command's own options, plus under ``_rest`` ({key: "key=value"}) the hyper-parameter overrides that
     ``eval.resolve_config`` lays over the checkpoint's configuration.  Reads no file."""
-    from . import nsfp
+    from . import fastnsf, nsfp
     from .rigid import COMMAND_KEYS, params_from_command
     opt = dict(OWN_DEFAULTS)
     rest: Dict[str, str] = {}
     icp: Dict[str, str] = {}
     own_nsfp: Dict[str, str] = {}
+    own_fast: Dict[str, str] = {}
     for a in argv:
         if "=" not in a:
             raise SystemExit(f"expected key=value, got {a!r}")
@@ -98,6 +108,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             icp[k] = v
         elif k in nsfp.COMMAND_KEYS:
             own_nsfp[k] = v
+        elif k in fastnsf.COMMAND_KEYS:
+            own_fast[k] = v
         elif k in DEFAULTS or k in _TARGET_ALIASES or k == "model.target.grid_feature_size":
             if k in ("batch_size", "num_workers"):
                 try:
@@ -111,7 +123,24 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted(OWN_DEFAULTS))}, and the hyper-parameters of deflow_amd.train")
     opt["icpflow"] = rest.get("model") == "model=icpflow" or rest.get("model.name") == "model.name=icpflow"
     opt["nsfp"] = rest.get("model") == "model=nsfp" or rest.get("model.name") == "model.name=nsfp"
-    if opt["nsfp"]:
+    opt["fastnsf"] = rest.get("model") == "model=fastnsf" or rest.get("model.name") == "model.name=fastnsf"
+    if opt["fastnsf"]:
+        if opt["checkpoint"] or opt["inference_dtype"]:
+            raise SystemExit("model=fastnsf has no weights: it takes neither checkpoint= nor inference_dtype=\n" + FASTNSF_USAGE)
+        if icp:
+            raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + FASTNSF_USAGE)
+        if own_nsfp:
+            raise SystemExit(f"{', '.join(sorted(own_nsfp))}: the nsfp_* keys belong to model=nsfp\n" + FASTNSF_USAGE)
+        if not opt["dataset_path"]:
+            raise SystemExit(FASTNSF_USAGE)
+        rest.pop("model", None), rest.pop("model.name", None)
+        rest.setdefault("batch_size", f"batch_size={fastnsf.COMMAND_BATCH_SIZE}")
+        opt["fastnsf_params"] = fastnsf.params_from_command(own_fast)
+        if opt["res_name"] is None:
+            opt["res_name"] = "fastnsf"
+    elif own_fast:
+        raise SystemExit(f"{', '.join(sorted(own_fast))}: the fastnsf_* keys belong to model=fastnsf\n" + FASTNSF_USAGE)
+    elif opt["nsfp"]:
         if opt["checkpoint"] or opt["inference_dtype"]:
             raise SystemExit("model=nsfp has no weights: it takes neither checkpoint= nor inference_dtype=\n" + NSFP_USAGE)
         if icp:
@@ -270,6 +299,13 @@ def main(argv=None) -> int:
         meta = {"res_name": res_name, "checkpoint": None, "model": "nsfp", "voxel_size": [float(v) for v in cfg["voxel_size"]],
                 "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
                 "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6k (UNPINNED)"}
+    elif opt["fastnsf"]:
+        from .fastnsf import FastNsf
+        cfg = parse_overrides(list(opt["_rest"].values()))
+        model = FastNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["fastnsf_params"])
+        meta = {"res_name": res_name, "checkpoint": None, "model": "fastnsf", "voxel_size": [float(v) for v in cfg["voxel_size"]],
+                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
+                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6l (UNPINNED)"}
     else:
         cfg = resolve_config(opt["checkpoint"], opt["_rest"])
         model = build_model(cfg).to(dev)

@@ -953,6 +953,33 @@ int df_mlp_fwd(const float* x, const int32_t* count, const float* params, int64_
 int df_mlp_bwd(const float* x, const int32_t* count, const float* params, int64_t param_stride, const float* acts, const float* dy, int B,
                int N, int depth, float* dparams, float* dx /*nullable*/, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ distance transform (model=fastnsf) ----
+ * The target side of the per-pair flow optimised on a distance transform.  UNPINNED: upstream's FastNSF source
+ * is absent; the definition is this project's own.  A grid of GX x GY x GZ voxels of edge `cell` (fp32) starts at the origin (ox, oy, oz)
+ * (fp32); R is the truncation radius in voxels, 1..255; every G >= 2 and GX * GY * GZ < 2^31 (offsets across the batch are 64-bit).
+ * df_dt_build: ref [B,N,3] f32 with count [B] i32 valid leading rows (clamped to [0, N]; 0 is legal).  A row occupies voxel
+ *   floor((p - o) / cell) per axis, in fp32 with an IEEE division; non-finite rows and rows outside the grid occupy nothing.
+ *   dt2 [B,GZ,GY,GX] u16 = min(R*R, min over the sample's occupied voxels v' of |v - v'|^2) in integer voxel units: the exact squared
+ *   Euclidean distance transform between voxel centres, truncated at R (R*R everywhere for a sample without an occupied voxel).  EVERY
+ *   element of dt2 is written.  Clear, mark (plain stores of one constant), then three separable windowed min-plus passes
+ *   min over |k| <= R of k*k + prev[. + k] along x, y, z, with partial sums saturated at R*R: integer arithmetic, no atomics, two calls
+ *   are bit-identical and a sample's grid depends on neither B nor the other samples.  ws: df_dt_ws_bytes(B, GX, GY, GZ, R) bytes (one
+ *   more copy of the grid), 16-byte aligned like dt2.
+ * df_dt_lookup: query [B,N,3] f32, count as above -> d [B,N] f32, g [B,N,3] f32, and optionally (nullable) cells [B,N,3] i32 and
+ *   clamped [B,N] u8.  Per axis a: u = (q - o) / cell - 0.5 (fp32), clamped to [0, G - 1]; i = min(floor(u), G - 2); t = u - i.
+ *   d = the trilinear interpolant of cell * sqrt(dt2) over the corners i .. i + 1 at t (fp32), g = its analytic gradient d d / d q with
+ *   component a = 0 where axis a was clamped; cells = (ix, iy, iz), clamped = bit a set where axis a was clamped.  A row >= count gets
+ *   d = 0, g = 0, cells = 0, clamped = 0; a counted row with a non-finite coordinate d = R * cell, g = 0, cells = 0, clamped = 0: no
+ *   index is formed from it.  All outputs are written for every row.
+ * 1 <= B <= 65535, N >= 1, 3 B N < 2^31, the grid limits above: else DF_E_SHAPE (df_dt_ws_bytes returns it too).  NULL required
+ * pointers, a cell that is not positive and finite, a NaN origin: DF_E_ARG.  dt2 / ws not 16-byte, the other buffers not 4-byte aligned:
+ * DF_E_ALIGN.  No launch then.  Grids come from B, N and the grid extents only; the entries never allocate or synchronise. */
+int64_t df_dt_ws_bytes(int B, int GX, int GY, int GZ, int R);
+int df_dt_build(const float* ref, const int32_t* count, int B, int N, float ox, float oy, float oz, float cell, int GX, int GY, int GZ, int R,
+                uint16_t* dt2, void* ws, void* stream);
+int df_dt_lookup(const float* query, const int32_t* count, const uint16_t* dt2, int B, int N, float ox, float oy, float oz, float cell,
+                 int GX, int GY, int GZ, int R, float* d, float* g, int32_t* cells /*nullable*/, uint8_t* clamped /*nullable*/, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
