@@ -95,6 +95,7 @@ _SIGS = {
     "df_weight_prep": [P, P, I, I, P, P, P, P],
     "df_conv2d_variant": [L, L, I, I],
     "df_conv2d_last_dma": [],
+    "df_conv2d_plan": [DfImg, DfImg, I, I, I, I, I, P],
     "df_conv2d_bf16": [DfImg, P, P, DfImg, I, I, I, I, P, P, I, P],
     "df_cast_bf16": [P, P, L, I, I, I, P],
     "df_upsample2x_bf16": [DfImg, DfImg, I, P],

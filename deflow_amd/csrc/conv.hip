@@ -1342,77 +1342,377 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float* __restri
   }
 }
 
+template <int BM, int BN, int WM, int WN, bool BF = false, bool H2 = false, bool BP = false, bool UPS = false>
+static int launch_conv_dma(const ConvParams& p, hipStream_t s) {
+  const size_t lds_bytes = (size_t)2 * (BM + BN) * LDT * sizeof(float);
+  DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN, BF, H2, BP, UPS>), (int)lds_bytes);
+  hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN, BF, H2, BP, UPS>), dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds_bytes, s, p);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
 // 8-wave forms (512 threads; wave tile 64 x 32 resp. 32 x 32, 32 / 16 accumulator registers): the same LDS footprint
 // and DMA traffic as the 4-wave kernels but twice the waves per SIMD to cover each other's barrier and DMA waits
 // (measured +2..4 % on the 128 x 128 tile).  DMA path only.
 template <int BM, int BN, int WM, int WN>
 static int launch_conv_w8(const ConvParams& p, hipStream_t s) {
-  const size_t lds_bytes = (size_t)2 * (BM + BN) * LDT * sizeof(float);
-  if (p.bf16) {
-    DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN, true>), (int)lds_bytes);
-    hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN, true>), dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds_bytes, s, p);
-    DF_CHECK_LAUNCH();
-    return DF_OK;
+  if (p.bf16) return launch_conv_dma<BM, BN, WM, WN, true>(p, s);
+  const bool h2 = p.amax_x && p.amax_w;         // df_conv2d_h2f: fp16x2 on the fragments
+  if (p.ups_on) {                               // ... and the bilinear half of the concatenation written by the same workgroups
+    DF_REQUIRE(h2 && p.w2p, DF_E_ARG);
+    return launch_conv_dma<BM, BN, WM, WN, false, true, true, true>(p, s);
   }
-  if (p.ups_on) {                        // ... and the bilinear half of the concatenation written by the same workgroups
-    DF_REQUIRE(p.amax_x && p.amax_w && p.w2p, DF_E_ARG);
-    DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN, false, true, true, true>), (int)lds_bytes);
-    hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN, false, true, true, true>), dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds_bytes, s, p);
-    DF_CHECK_LAUNCH();
-    return DF_OK;
+  if (h2 && p.w2p) return launch_conv_dma<BM, BN, WM, WN, false, true, true>(p, s);    // ... with the weights pre-split
+  if (h2) return launch_conv_dma<BM, BN, WM, WN, false, true>(p, s);
+  return launch_conv_dma<BM, BN, WM, WN>(p, s);
+}
+
+// the plane kernel's tiles of 64 x 64 wave tiles: 256 x 128 (SEG = 1 / 2 / 4 image rows) and 512 x 64 (SEG = 1 / 2), ring depths DB128 / DB64
+template <int DB128, int DB64, int NP, bool X16 = false, bool XP = false, bool BWS = false>
+static int launch_conv_halo_x3_big(const ConvParams& p, int bn, int seg, hipStream_t s) {
+  if (bn == 128) {
+    if (seg == 1) return launch_conv_halo_x3<256, 128, 4, 2, 1, DB128, NP, X16, XP, BWS>(p, s);
+    if (seg == 2) return launch_conv_halo_x3<256, 128, 4, 2, 2, DB128, NP, X16, XP, BWS>(p, s);
+    return launch_conv_halo_x3<256, 128, 4, 2, 4, DB128, NP, X16, XP, BWS>(p, s);
   }
-  if (p.amax_x && p.amax_w && p.w2p) {   // ... with the weights pre-split
-    DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN, false, true, true>), (int)lds_bytes);
-    hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN, false, true, true>), dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds_bytes, s, p);
-    DF_CHECK_LAUNCH();
-    return DF_OK;
-  }
-  if (p.amax_x && p.amax_w) {   // df_conv2d_h2f: fp16x2 on the fragments
-    DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN, false, true>), (int)lds_bytes);
-    hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN, false, true>), dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds_bytes, s, p);
-    DF_CHECK_LAUNCH();
-    return DF_OK;
-  }
-  DF_SET_LDS_ONCE((conv_dma_kernel<BM, BN, WM, WN>), (int)lds_bytes);
-  hipLaunchKernelGGL((conv_dma_kernel<BM, BN, WM, WN>), dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds_bytes, s, p);
-  DF_CHECK_LAUNCH();
-  return DF_OK;
+  if (seg == 1) return launch_conv_halo_x3<512, 64, 8, 1, 1, DB64, NP, X16, XP, BWS>(p, s);
+  return launch_conv_halo_x3<512, 64, 8, 1, 2, DB64, NP, X16, XP, BWS>(p, s);
+}
+
+// ... and its 128-row tiles (SEG = 2: row pairs of a W == 64 image) and the 256 x 64 row tile
+template <int NP>
+static int launch_conv_halo_x3_small(const ConvParams& p, int bm, int bn, int seg, hipStream_t s) {
+  if (seg == 2) return bn == 128 ? launch_conv_halo_x3<128, 128, 2, 4, 2, 4, NP>(p, s) : launch_conv_halo_x3<128, 64, 4, 2, 2, 8, NP>(p, s);
+  if (bn == 128) return launch_conv_halo_x3<128, 128, 2, 4, 1, 4, NP>(p, s);
+  return bm == 256 ? launch_conv_halo_x3<256, 64, 4, 2, 1, 4, NP>(p, s) : launch_conv_halo_x3<128, 64, 4, 2, 1, 8, NP>(p, s);
+}
+
+template <int BN, int WM, int WN, bool X16 = false>
+static int launch_conv_halo_w16_seg(const ConvParams& p, int seg, hipStream_t s) {
+  return seg == 1 ? launch_conv_halo_w16<BN, WM, WN, 1, X16>(p, s) : launch_conv_halo_w16<BN, WM, WN, 2, X16>(p, s);
 }
 
 }  // namespace
 
 
+// ---- host part: forward and data gradient ------------------------------------------------------------------------------------------
+// Every launch entry point is its own DF_REQUIRE line, a ConvCall with named fields, and conv_launch(): the call's argument checks,
+// conv_plan() -- the ONE place that decides tile, kernel family and buffer extents from the descriptors and the weight kind, and what the
+// _ok queries and df_conv2d_plan answer from -- ConvParams filled from the call and the plan, one ladder from the plan to a template
+// instance.  A new form is one branch of conv_plan() and one line of that ladder.
+
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+// the environment switches of this layer, each read once (A/B experiments; the defaults are what the engine runs)
+struct ConvSwitches {
+  int tile = env_int("DF_CONV_TILE", 0);              // 128064 / 256064: that tile where it applies
+  // small problems: 64-row tiles, more of them to fill 256 CUs.  Round 6: up to 4096 rows (8192 until then, measured in round 2) -- a B = 1
+  // forward's 8192-pixel 3x3 layers are bound by the 64 x 64 tile's operand traffic (split-K over its tap rows changed nothing:
+  // profiles/r06_conv_experiments.txt 5m) and run 1.5-2.5 % of the forward faster on the haloed 128-row forms (1.892 / 1.901 -> 1.868 / 1.866 ms)
+  int small_rows = env_int("DF_CONV_SMALL_ROWS", 4096);
+  int no_dma = env_int("DF_CONV_NO_DMA", 0), halo = env_int("DF_CONV_HALO", 1), wide_epi = env_int("DF_CONV_WIDE_EPI", 0);
+  int dbg = env_int("DF_CONV_DBG", 0), rot = env_int("DF_CONV_ROT", 1), cls_il = env_int("DF_CONV_CLS_IL", 1);
+  int x3 = env_int("DF_CONV_X3", 1), w16 = env_int("DF_CONV_W16", 1);      // 0: df_conv2d_x3_ok, _h2p_ok / df_conv2d_w16_ok answer 0
+  int x3_bm256 = env_int("DF_CONV_X3_BM256", 1);      // 64 output channels: 256-pixel row tiles where the image allows
+  int h2_bm256 = env_int("DF_CONV_H2_BM256", 1);      // fp16x2: the 256 x 128 / 512 x 64 tiles of 64 x 64 wave tiles
+  int pers = env_int("DF_CONV_PERS", 1);              // pre-split input: the persistent kernels of conv_x3p.hip
+  int w16_waves4 = env_int("DF_W16_WAVES4", 0);       // bit 0: 128-wide, bit 1: 64-wide bf16 tiles on 4 waves
+  // DF_W16_WIDE=1 (default off): the large tiles of the fp16x2 kernel with ONE bf16 plane (64 x 64 wave tiles: 4 fragment reads per 4
+  // MFMAs; the 128 x 128 bf16-tile forms read 3 per 2).  Measured SLOWER than those at the bench shape (bf16 step 42.8 vs 41.4 ms; 700-930
+  // vs 820-1000 TFLOP/s per layer): with one plane the kernel is not LDS-read-bound, and its register-staged halo costs more
+  int w16_wide = env_int("DF_W16_WIDE", 0);
+  int w8 = env_int("DF_CONV_W8", 3);                  // 8-wave DMA forms: bit 0 the 128 x 128, bit 1 the 128 x 64, bit 2 the 256 x 64 tile
+  int bp42 = env_int("DF_CONV_BP42", 1);
+};
+static const ConvSwitches& conv_switches() { static const ConvSwitches sw{}; return sw; }
+
 // tile variant as BM * 1000 + BN.  rows = GEMM rows one tile range covers (per parity class in class mode).
 static int pick_variant(int64_t rows, int64_t rows_per_stat_group, int cout, int epi) {
+  const ConvSwitches& sw = conv_switches();
   if (cout % 64) return 128032;
-  static const int force = getenv("DF_CONV_TILE") ? atoi(getenv("DF_CONV_TILE")) : 0;  // A/B experiments only
-  if (force == 128064 && rows > 128 * 256 && (!epi_stats(epi) || rows_per_stat_group % 128 == 0)) return 128064;
-  int bm;
-  if (epi_stats(epi)) bm = (rows_per_stat_group % 128 == 0) ? 128 : 64;
-  else {
-    // small problems: 64-row tiles, more of them to fill 256 CUs.  Round 6: up to 4096 rows (8192 until then, measured in round 2) -- a B = 1
-    // forward's 8192-pixel 3x3 layers are bound by the 64 x 64 tile's operand traffic (split-K over its tap rows changed nothing:
-    // profiles/r06_conv_experiments.txt 5m) and run 1.5-2.5 % of the forward faster on the haloed 128-row forms (1.892 / 1.901 -> 1.868 / 1.866 ms)
-    static const int small_rows = getenv("DF_CONV_SMALL_ROWS") ? atoi(getenv("DF_CONV_SMALL_ROWS")) : 4096;
-    bm = (rows <= small_rows) ? 64 : 128;
-  }
+  if (sw.tile == 128064 && rows > 128 * 256 && (!epi_stats(epi) || rows_per_stat_group % 128 == 0)) return 128064;
+  const int bm = epi_stats(epi) ? (rows_per_stat_group % 128 == 0 ? 128 : 64) : (rows <= sw.small_rows ? 64 : 128);
   if (bm == 64) return 64064;
   if (cout % 128 == 0) return 128128;
   // 64 output channels: 128x64 (48 KB LDS -> 3 workgroups/CU) measured 120 vs 115 TFLOP/s for the 256x64 tile
-  static const int use256 = getenv("DF_CONV_TILE") ? atoi(getenv("DF_CONV_TILE")) == 256064 : 0;
-  const bool ok256 = use256 && (epi_stats(epi) ? (rows_per_stat_group % 256 == 0) : (rows >= 256 * 512 && rows % 256 == 0));
+  const bool ok256 = sw.tile == 256064 && (epi_stats(epi) ? (rows_per_stat_group % 256 == 0) : (rows >= 256 * 512 && rows % 256 == 0));
   return ok256 ? 256064 : 128064;
+}
+
+// what the dispatch decides for one call (df_conv2d_plan hands the integers out)
+struct ConvPlan {
+  int family = -1;                                // DF_CONV_FAM_*
+  int bm = 0, bn = 0, wm = 0, wn = 0;             // tile and wave grid
+  int seg = 1, db = 0, planes = 0;                // haloed 16-bit forms: image rows per tile; plane forms: weight ring depth, planes per operand
+  bool xp = false, x16 = false, bws = false;      // pre-split input, bf16 input, the DF_EPI_BWD_STATS epilogue
+  int tiles_m = 0, tiles_n = 0, cls_tiles = 0, stats_mul = 1;
+  unsigned x_bytes = 0, w_bytes = 0, dshift = 0, y_bytes = 0;
+  void tile(int family_, int bm_, int bn_, int wm_, int wn_, int seg_ = 1, int db_ = 0, int planes_ = 0) {
+    family = family_; bm = bm_; bn = bn_; wm = wm_; wn = wn_; seg = seg_; db = db_; planes = planes_;
+  }
+};
+
+// h2 image: whole 32-channel chunks at 128-byte lines
+static bool h2_lines_ok(const df_img& d) {
+  return (d.ld % 32) == 0 && (d.img_stride % 32) == 0 && (d.grp_off % 32) == 0 && (((uintptr_t)d.ptr) & 127) == 0;
+}
+static int64_t img_extent(const df_img& d) {      // elements from the first to one past the last the descriptor addresses
+  return (int64_t)(d.grp_size - 1) * d.img_stride + (int64_t)(d.n / d.grp_size - 1) * d.grp_off + (int64_t)d.h * d.w * d.ld;
+}
+
+// The plan of a call, from its descriptors and the kind of its weights (DF_CONV_W_*) alone: -> DF_OK, or the code the launch refuses
+// with.  ups: the call also writes the bilinear half of a concatenation (df_conv2d_h2f_wp_up).
+static int conv_plan(ConvPlan& pl, const df_img& x, const df_img& y, int ksize, int stride, int mode, int epi, int weights, bool ups = false) {
+  const ConvSwitches& sw = conv_switches();
+  pl = ConvPlan();
+  DF_REQUIRE(weights >= DF_CONV_W_F32 && weights <= DF_CONV_W_F32_H2, DF_E_ARG);
+  const bool w16 = weights == DF_CONV_W_B16, h2 = weights == DF_CONV_W_H2, x3 = h2 || weights == DF_CONV_W_X3;
+  // bfloat16 tensors (bf16-storage training): the input only for the bf16-tile kernel (df_conv2d_w16), the output for any
+  // kernel with the branch-free epilogue; h2 input: the fp16x2 haloed form only
+  DF_REQUIRE(img_ok(x, w16 || h2) && img_ok(y, true), DF_E_ALIGN);
+  DF_REQUIRE((x.elt != 2 || h2) && (x.elt != 1 || w16), DF_E_ARG);
+  if (y.elt == 2) DF_REQUIRE(h2_lines_ok(y), DF_E_ARG);
+  if (x.elt == 2) DF_REQUIRE(h2_lines_ok(x), DF_E_ARG);
+  DF_REQUIRE(x.n == y.n, DF_E_SHAPE);
+  DF_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), DF_E_SHAPE);
+  DF_REQUIRE(mode == DF_CONV_FWD || mode == DF_CONV_DGRAD, DF_E_ARG);
+  DF_REQUIRE(epi >= 0 && epi <= 3, DF_E_ARG);
+  DF_REQUIRE(x.c % BK == 0 && y.c % 32 == 0, DF_E_SHAPE);
+  const int pad = ksize / 2;
+  const df_img &big = mode == DF_CONV_FWD ? x : y, &small = mode == DF_CONV_FWD ? y : x;      // (the conv's input-sized and output-sized grids)
+  DF_REQUIRE(small.h == (big.h + 2 * pad - ksize) / stride + 1 && small.w == (big.w + 2 * pad - ksize) / stride + 1, DF_E_SHAPE);
+  if (epi == DF_EPI_BWD_STATS)      // fused BatchNorm-backward partials: the fp16x2 data gradient of a pre-split dy with a plain fp32 output only
+    DF_REQUIRE(mode == DF_CONV_DGRAD && h2 && x.elt == 2 && y.elt == 0 && y.ld == y.c, DF_E_ARG);
+  const int64_t M = (int64_t)y.n * (y.h * y.w), rows_per_group = (int64_t)y.grp_size * (y.h * y.w);
+  DF_REQUIRE(M < (1ll << 31), DF_E_SHAPE);
+  const int K = x.c, N = y.c;
+  auto stat_rows = [&](int rows) { return !epi_stats(epi) || rows_per_group % rows == 0; };      // a tile never straddles two statistic groups
+
+  // tile; stride-2 data gradient onto an even image: row tiles per parity class where a class is whole tiles
+  const bool cls = mode == DF_CONV_DGRAD && stride == 2 && ksize == 3 && epi == DF_EPI_BIAS && (y.h % 2) == 0 && (y.w % 2) == 0;
+  int var = pick_variant(cls ? M / 4 : M, rows_per_group, N, epi);
+  DF_REQUIRE(stat_rows(var / 1000), DF_E_SHAPE);
+  if (cls && (M / 4) % (var / 1000) == 0) {
+    pl.cls_tiles = (int)(M / 4 / (var / 1000));
+    pl.tiles_m = 4 * pl.cls_tiles;
+  } else {
+    if (cls) var = pick_variant(M, rows_per_group, N, epi);
+    pl.tiles_m = (int)((M + var / 1000 - 1) / (var / 1000));
+  }
+  pl.tiles_n = N / (var % 1000);
+
+  // LDS-DMA path needs 32-bit byte offsets: extent of x (+ the shift that keeps the top-left tap offset >= 0)
+  const int xes = x.elt == 1 ? 2 : 4, yes = y.elt == 1 ? 2 : 4;
+  const int64_t ext = img_extent(x) * xes, wb = (int64_t)N * ksize * ksize * K * 4;
+  const int64_t dsh = pl.cls_tiles > 0 ? 0 : (int64_t)pad * ((int64_t)x.w + 1) * x.ld * xes;
+  const bool geom_ok = !(mode == DF_CONV_DGRAD && stride == 2 && pl.cls_tiles == 0);  // generic s2 dgrad: register path
+  if (!sw.no_dma && geom_ok && x.img_stride >= 0 && x.grp_off >= 0 && ext + dsh < (int64_t)DMA_BAD - (16 << 20) && wb < (1ll << 31) &&
+      ((int64_t)2 * x.w + 2) * x.ld * 4 + (int64_t)K * 4 < (8 << 20)) {
+    pl.x_bytes = (unsigned)(ext + dsh);
+    pl.w_bytes = (unsigned)wb;
+    pl.dshift = (unsigned)dsh;
+  }
+  const int64_t yext = img_extent(y) * yes;
+  if ((!sw.wide_epi || y.elt) && y.img_stride >= 0 && y.grp_off >= 0 && yext < (int64_t)0xFFFFFFFFll - (16 << 20)) pl.y_bytes = (unsigned)yext;
+  if (y.elt) DF_REQUIRE(pl.y_bytes != 0 && pl.x_bytes != 0, DF_E_SHAPE);   // bf16 / h2 output: only the DMA kernels' straight-line epilogue
+
+  // the haloed forms: 3x3 stride 1 (fwd / dgrad) on full 128-row tiles by DMA -- halo_ok: rows of 128 output pixels inside one image
+  // row; two: W == 64 as row pairs (the 16-bit forms only)
+  const bool same = pl.x_bytes && ksize == 3 && stride == 1 && pl.cls_tiles == 0 && x.w == y.w && x.h == y.h && (var == 128128 || var == 128064);
+  const bool halo_ok = sw.halo && same && (y.w % 128) == 0;
+  const bool two = same && y.w == 64 && (y.h % 2) == 0;
+  // tiles of 64 x 64 wave tiles (8 fragment reads per 12 MFMAs instead of 6 per 6 -- the 128 x 128 form reads LDS for as many cycles as it
+  // multiplies), where the rows allow and there are tiles for every CU twice over.  The 256 x 128 rule, 128-multiple output channels: 256
+  // pixels of one image row, two rows of a W == 128 image, four of a W == 64 one ...
+  const int seg128 = (y.w % 256) == 0 ? 1 : y.w == 128 ? 2 : y.w == 64 ? 4 : 0;
+  const bool big128 = var == 128128 && seg128 && (y.h % seg128) == 0 && (M % 256) == 0 && stat_rows(256) && M / 256 * pl.tiles_n >= 512;
+  // ... and the 512 x 64 rule, 64 output channels (8 x 1 waves): 512 pixels of one row, or two rows of a W == 256 image
+  const int seg64 = (y.w % 512) == 0 ? 1 : y.w == 256 ? 2 : 0;
+  const bool big64 = var == 128064 && seg64 && (y.h % seg64) == 0 && (M % 512) == 0 && stat_rows(512) && M / 512 >= 512;
+
+  if (x3) {   // fp32-accurate product from three bf16 / two fp16 planes per operand (W % 128 == 0, or W == 64 as row pairs)
+    DF_REQUIRE((halo_ok || two) && (y.elt == 0 || (y.elt == 2 && h2)), DF_E_SHAPE);
+    pl.xp = x.elt == 2;                  // pre-split input (h2 image): the 256 x 128 / 512 x 64 tile forms only
+    pl.bws = epi == DF_EPI_BWD_STATS;
+    const int np = h2 ? 2 : 3;
+    pl.w_bytes = (unsigned)((int64_t)N * 9 * K * 2 * np);
+    // 64 output channels: 256-pixel row tiles where the image allows (wave tile 64 x 32 instead of 32 x 32)
+    const bool wide = !two && var == 128064 && sw.x3_bm256 && (y.w % 256) == 0 && (M % 256) == 0 && stat_rows(256);
+    if (h2 && sw.h2_bm256 && big128) pl.tile(pl.xp && sw.pers ? DF_CONV_FAM_HALO_X3P : DF_CONV_FAM_HALO_X3, 256, 128, 4, 2, seg128, 4, np);
+    else if (h2 && sw.h2_bm256 && big64) pl.tile(pl.xp && sw.pers ? DF_CONV_FAM_HALO_X3P : DF_CONV_FAM_HALO_X3, 512, 64, 8, 1, seg64, 3, np);
+    else if (pl.xp) return DF_E_SHAPE;
+    else if (two) var == 128128 ? pl.tile(DF_CONV_FAM_HALO_X3, 128, 128, 2, 4, 2, 4, np) : pl.tile(DF_CONV_FAM_HALO_X3, 128, 64, 4, 2, 2, 8, np);
+    else if (var == 128128) pl.tile(DF_CONV_FAM_HALO_X3, 128, 128, 2, 4, 1, 4, np);
+    else if (wide) pl.tile(DF_CONV_FAM_HALO_X3, 256, 64, 4, 2, 1, 4, np);
+    else pl.tile(DF_CONV_FAM_HALO_X3, 128, 64, 4, 2, 1, 8, np);
+  } else if (w16) {   // bf16 tiles in LDS, only the haloed forms exist
+    DF_REQUIRE(halo_ok || two, DF_E_SHAPE);
+    pl.x16 = x.elt != 0;
+    pl.w_bytes /= 2;
+    const int w4 = pl.x16 ? 0 : sw.w16_waves4;        // (bf16 activations in memory: 8-wave forms only)
+    if (sw.w16_wide && big128) pl.tile(DF_CONV_FAM_HALO_X3, 256, 128, 4, 2, seg128, 8, 1);
+    else if (sw.w16_wide && big64) pl.tile(DF_CONV_FAM_HALO_X3, 512, 64, 8, 1, seg64, 8, 1);
+    else if (var == 128128) pl.tile(DF_CONV_FAM_HALO_W16, 128, 128, 2, (w4 & 1) ? 2 : 4, halo_ok ? 1 : 2);
+    else pl.tile(DF_CONV_FAM_HALO_W16, 128, 64, (w4 & 2) ? 2 : 4, 2, halo_ok ? 1 : 2);
+  } else {            // fp32 tiles in LDS; with a bound on x and w (df_conv2d_h2f) the DMA-tile kernel splits them on the fragments
+    const bool bp = weights == DF_CONV_W_WP;
+    if (ups) DF_REQUIRE(pl.x_bytes && bp, DF_E_SHAPE);      // only the 8-wave DMA kernels with pre-split weights carry the UPS form
+    const int fam = pl.x_bytes ? DF_CONV_FAM_DMA : DF_CONV_FAM_REG;
+    const auto w8 = [&](int bit) { return pl.x_bytes && ((sw.w8 & bit) || ups); };
+    switch (var) {
+      case 128032: pl.tile(fam, 128, 32, 4, 1); break;
+      case 64064: pl.tile(fam, 64, 64, 2, 2); break;
+      case 128128:
+        // pre-split weights (BP): B fragments cost no VALU, so the wave grid that shares an A fragment among FEWER waves wins -- 4 x 2
+        // (each wave splits one 32-row A fragment per 6 MFMAs) instead of 2 x 4 (two per 6, each redone by four waves)
+        if (halo_ok) pl.tile(DF_CONV_FAM_HALO, 128, 128, 2, 4);
+        else if (w8(1) && bp && (sw.bp42 || ups)) pl.tile(fam, 128, 128, 4, 2);
+        else if (w8(1)) pl.tile(fam, 128, 128, 2, 4);
+        else pl.tile(fam, 128, 128, 2, 2);
+        break;
+      case 256064: w8(4) ? pl.tile(fam, 256, 64, 4, 2) : pl.tile(fam, 256, 64, 4, 1); break;
+      default:
+        // (with pre-split weights a 4 x 1 grid -- 32 x 64 wave tiles, one A split per 6 MFMAs, but 4 waves per workgroup -- measured
+        // 9-33 % SLOWER than 4 x 2 on the four 64-wide layers: occupancy beats the split count here)
+        if (halo_ok) pl.tile(DF_CONV_FAM_HALO, 128, 64, 4, 2);
+        else w8(2) ? pl.tile(fam, 128, 64, 4, 2) : pl.tile(fam, 128, 64, 2, 2);
+    }
+  }
+  if (pl.family >= DF_CONV_FAM_HALO_W16) {     // the 16-bit forms' row tiles are whole; the statistics table stays sized for 128-row tiles
+    pl.tiles_m = (int)(M / pl.bm);
+    pl.stats_mul = pl.bm / 128;         // (table rows per tile: the first takes the sums, the others zeros)
+  }
+  return DF_OK;
 }
 
 extern "C" int df_conv2d_variant(int64_t rows, int64_t rows_per_stat_group, int cout, int epi) {
   return pick_variant(rows, rows_per_stat_group, cout, epi);
 }
 
+extern "C" int df_conv2d_tile_m(int64_t rows_per_stat_group, int cout) {
+  return pick_variant(rows_per_stat_group, rows_per_stat_group, cout, DF_EPI_STATS) / 1000;
+}
+
+extern "C" int df_conv2d_plan(df_img x, df_img y, int ksize, int stride, int mode, int epi, int weights, int32_t* out) {
+  DF_REQUIRE(out, DF_E_ARG);
+  ConvPlan pl;
+  const int rc = conv_plan(pl, x, y, ksize, stride, mode, epi, weights);
+  if (rc != DF_OK) pl = ConvPlan();
+  const int flags = (pl.xp ? DF_CONV_PLAN_XP : 0) | (pl.x16 ? DF_CONV_PLAN_X16 : 0) | (pl.bws ? DF_CONV_PLAN_BWS : 0) |
+                    (pl.x_bytes ? DF_CONV_PLAN_DMA : 0) | (pl.cls_tiles ? DF_CONV_PLAN_CLS : 0);
+  const int32_t v[DF_CONV_PLAN_LEN] = {pl.family, pl.bm, pl.bn, pl.wm, pl.wn, pl.seg, pl.db, pl.planes, flags, pl.stats_mul};
+  for (int i = 0; i < DF_CONV_PLAN_LEN; ++i) out[i] = v[i];
+  return rc;
+}
+
+// the form queries: 1 if the form exists for a call of these descriptors
+static int conv_form_ok(const df_img& x, const df_img& y, int ksize, int stride, int mode, int epi, int weights) {
+  ConvPlan pl;
+  return conv_plan(pl, x, y, ksize, stride, mode, epi, weights) == DF_OK ? 1 : 0;
+}
+extern "C" int df_conv2d_x3_ok(df_img x, df_img y, int ksize, int stride, int mode, int epi) {
+  return conv_switches().x3 && conv_form_ok(x, y, ksize, stride, mode, epi, DF_CONV_W_X3);
+}
+extern "C" int df_conv2d_h2p_ok(df_img x, df_img y, int ksize, int stride, int mode, int epi) {
+  return conv_switches().x3 && conv_form_ok(x, y, ksize, stride, mode, epi, DF_CONV_W_H2);
+}
+extern "C" int df_conv2d_w16_ok(df_img x, df_img y, int ksize, int stride, int mode, int epi) {
+  return conv_switches().w16 && conv_form_ok(x, y, ksize, stride, mode, epi, DF_CONV_W_B16);
+}
+
 static thread_local int g_last_dma = 0;   // per host thread: the query below refers to the CALLING thread's previous df_conv2d
 extern "C" int df_conv2d_last_dma(void) { return g_last_dma; }  // 1 if the previous df_conv2d used the LDS-DMA kernel
 
-extern "C" int df_conv2d_tile_m(int64_t rows_per_stat_group, int cout) {
-  return pick_variant(rows_per_stat_group, rows_per_stat_group, cout, DF_EPI_STATS) / 1000;
+// what an entry point passes on (value-initialised: an entry point names the fields it has)
+struct ConvCall {
+  df_img x = {}, y = {};
+  const void *w = nullptr, *w2p = nullptr;                          // the weights as `weights` says; DF_CONV_W_WP: the fp32 ones, the planes in w2p
+  int weights = DF_CONV_W_F32;
+  const float *x_amax = nullptr, *w_amax = nullptr;                 // fp16x2 forms: bounds of max |x| and max |w| (device scalars)
+  int ksize = 0, stride = 0, pad = 0, mode = DF_CONV_FWD, epi = DF_EPI_BIAS, accumulate = 0, mfma_bf16 = 0;
+  const float *bias = nullptr, *scale = nullptr, *shift = nullptr;
+  float* stats = nullptr;                                           // DF_EPI_STATS / DF_EPI_BWD_STATS: the partial table
+  float* y_amax = nullptr;                                          // optional: receives max |y|
+  const float* y_bound = nullptr;                                   // y.elt == 2: the bound that defines the output planes' scale
+  const float *bwd_y = nullptr, *bwd_ss = nullptr;                  // DF_EPI_BWD_STATS: the BatchNorm layer's conv output and its statistics
+  const df_img* ups = nullptr;                                      // df_conv2d_h2f_wp_up: the tensor whose bilinear x2 the call also writes
+  int ups_ac = 0;
+  void* stream = nullptr;
+};
+
+static int conv_launch(const ConvCall& c) {
+  const ConvSwitches& sw = conv_switches();
+  const df_img &x = c.x, &y = c.y;
+  DF_REQUIRE(c.w && df_aligned16(c.w), DF_E_ALIGN);
+  // h2 output: a bound, no accumulation (the planes of two scales do not add)
+  if (y.elt == 2) DF_REQUIRE(c.y_bound && !c.accumulate, DF_E_ARG);
+  DF_REQUIRE(c.pad == c.ksize / 2, DF_E_SHAPE);
+  if (c.epi == DF_EPI_BN_GELU) DF_REQUIRE(c.scale && c.shift, DF_E_ARG);
+  if (epi_stats(c.epi)) DF_REQUIRE(c.stats, DF_E_ARG);
+  if (c.epi == DF_EPI_BWD_STATS) DF_REQUIRE(c.bwd_y && c.bwd_ss && !c.accumulate && !c.bias, DF_E_ARG);
+  ConvPlan pl;
+  const int rc = conv_plan(pl, x, y, c.ksize, c.stride, c.mode, c.epi, c.weights, c.ups != nullptr);
+  if (rc != DF_OK) return rc;
+  if (c.ups) {     // (the entry point fixes the rest: a 1x1 forward conv with bias into the second half of a pre-split concatenation)
+    const df_img& t = *c.ups;
+    DF_REQUIRE(t.ptr && df_aligned16(t.ptr) && t.elt == 0 && t.n == y.n && t.c == y.c && 2 * t.h == y.h && 2 * t.w == y.w && (t.c % 8) == 0 &&
+                   (t.ld % 4) == 0 && (t.img_stride % 4) == 0 && (t.grp_off % 4) == 0 && t.grp_size > 0 && (y.ld % 32) == 0 && y.ld >= 2 * y.c,
+               DF_E_SHAPE);
+  }
+  g_last_dma = pl.x_bytes != 0;
+
+  ConvParams p;     // every field: from the call ...
+  p.x = x; p.y = y; p.w = reinterpret_cast<const float*>(c.w); p.w2p = c.w2p; p.amax_x = c.x_amax; p.amax_w = c.w_amax;
+  p.bias = c.bias; p.scale = c.scale; p.shift = c.shift; p.stats = c.stats; p.bwd_y = c.bwd_y; p.bwd_ss = c.bwd_ss;
+  p.ks = c.ksize; p.stride = c.stride; p.pad = c.pad; p.mode = c.mode; p.epi = c.epi; p.accumulate = c.accumulate; p.bf16 = c.mfma_bf16 != 0;
+  p.amax_y = reinterpret_cast<unsigned*>(c.y_amax); p.bound_y = c.y_bound;
+  p.ups_t = c.ups ? *c.ups : df_img{}; p.ups_on = c.ups != nullptr; p.ups_ac = c.ups_ac;
+  p.hw_y = y.h * y.w; p.M = y.n * p.hw_y; p.K = x.c; p.N = y.c;
+  // ... from the plan, from the switches
+  p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.cls_tiles = pl.cls_tiles; p.stats_mul = pl.stats_mul;
+  p.x_bytes = pl.x_bytes; p.w_bytes = pl.w_bytes; p.dshift = pl.dshift; p.y_bytes = pl.y_bytes;
+  p.dbg = sw.dbg; p.rot = sw.rot; p.cls_il = sw.cls_il;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
+  const auto is = [&](int bm, int bn, int wm, int wn) { return pl.bm == bm && pl.bn == bn && pl.wm == wm && pl.wn == wn; };
+  switch (pl.family) {
+    case DF_CONV_FAM_HALO_X3P: return df_launch_conv_halo_x3p(p, pl.bn, pl.seg, pl.bws, s);
+    case DF_CONV_FAM_HALO_X3:
+      if (pl.bm / pl.wm == 64 && pl.bn / pl.wn == 64) {      // 64 x 64 wave tiles
+        if (pl.planes == 1) return pl.x16 ? launch_conv_halo_x3_big<8, 8, 1, true>(p, pl.bn, pl.seg, s) : launch_conv_halo_x3_big<8, 8, 1, false>(p, pl.bn, pl.seg, s);
+        if (pl.bws) return launch_conv_halo_x3_big<4, 3, 2, false, true, true>(p, pl.bn, pl.seg, s);
+        return pl.xp ? launch_conv_halo_x3_big<4, 3, 2, false, true>(p, pl.bn, pl.seg, s) : launch_conv_halo_x3_big<4, 3, 2>(p, pl.bn, pl.seg, s);
+      }
+      return pl.planes == 2 ? launch_conv_halo_x3_small<2>(p, pl.bm, pl.bn, pl.seg, s) : launch_conv_halo_x3_small<3>(p, pl.bm, pl.bn, pl.seg, s);
+    case DF_CONV_FAM_HALO_W16:
+      if (pl.x16) return pl.bn == 128 ? launch_conv_halo_w16_seg<128, 2, 4, true>(p, pl.seg, s) : launch_conv_halo_w16_seg<64, 4, 2, true>(p, pl.seg, s);
+      if (pl.bn == 128) return pl.wn == 2 ? launch_conv_halo_w16_seg<128, 2, 2>(p, pl.seg, s) : launch_conv_halo_w16_seg<128, 2, 4>(p, pl.seg, s);
+      return pl.wm == 2 ? launch_conv_halo_w16_seg<64, 2, 2>(p, pl.seg, s) : launch_conv_halo_w16_seg<64, 4, 2>(p, pl.seg, s);
+    case DF_CONV_FAM_HALO: return pl.bn == 128 ? launch_conv_halo<128, 2, 4>(p, s) : launch_conv_halo<64, 4, 2>(p, s);
+    case DF_CONV_FAM_DMA:
+      // (round 5: the small tiles chosen for layers with few pixels -- a B = 1 forward -- take the DMA-tile kernel's H2 forms like the large ones)
+      if (is(128, 32, 4, 1)) return launch_conv_w8<128, 32, 4, 1>(p, s);
+      if (is(64, 64, 2, 2)) return launch_conv_w8<64, 64, 2, 2>(p, s);
+      if (is(128, 128, 4, 2)) return launch_conv_w8<128, 128, 4, 2>(p, s);
+      if (is(128, 128, 2, 4)) return launch_conv_w8<128, 128, 2, 4>(p, s);
+      if (is(256, 64, 4, 2)) return launch_conv_w8<256, 64, 4, 2>(p, s);
+      if (is(128, 64, 4, 2)) return launch_conv_w8<128, 64, 4, 2>(p, s);
+      [[fallthrough]];      // DF_CONV_W8 bits off: the 4-wave DMA forms of the large tiles
+    default:                // DF_CONV_FAM_REG: launch_conv takes conv_kernel where the plan has no DMA extents
+      if (is(128, 32, 4, 1)) return launch_conv<128, 32, 4, 1>(p, s);
+      if (is(64, 64, 2, 2)) return launch_conv<64, 64, 2, 2>(p, s);
+      if (is(128, 128, 2, 2)) return launch_conv<128, 128, 2, 2>(p, s);
+      if (is(256, 64, 4, 1)) return launch_conv<256, 64, 4, 1>(p, s);
+      return launch_conv<128, 64, 2, 2>(p, s);
+  }
+}
+
+extern "C" int df_conv2d_mp(df_img x, const float* w, const float* bias, df_img y, int ksize, int stride, int pad,
+                            int mode, int epi, const float* scale, const float* shift, float* stats_partial,
+                            int accumulate, int mfma_bf16, void* stream) {
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad; c.mode = mode; c.epi = epi; c.scale = scale; c.shift = shift;
+  c.stats = stats_partial; c.accumulate = accumulate; c.mfma_bf16 = mfma_bf16; c.stream = stream;
+  return conv_launch(c);
 }
 
 extern "C" int df_conv2d(df_img x, const float* w, const float* bias, df_img y, int ksize, int stride, int pad,
@@ -1421,28 +1721,26 @@ extern "C" int df_conv2d(df_img x, const float* w, const float* bias, df_img y, 
   return df_conv2d_mp(x, w, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, stream);
 }
 
-// w16 != nullptr: the pre-cast bf16 weights of df_conv2d_w16 (w is then unused); query: return 1 / 0 = "the w16 form
-// exists for this call" without launching anything
-static int conv2d_impl(df_img x, const float* w, const void* w16, const float* bias, df_img y, int ksize, int stride, int pad,
-                       int mode, int epi, const float* scale, const float* shift, float* stats_partial,
-                       int accumulate, int mfma_bf16, bool query, void* stream, const void* w3 = nullptr,
-                       const float* h2_amax_x = nullptr, const float* h2_amax_w = nullptr, float* y_amax = nullptr,
-                       const float* y_bound = nullptr, const float* bwd_y = nullptr, const float* bwd_ss = nullptr,
-                       const void* w2p = nullptr, const df_img* ups_t = nullptr, int ups_ac = 0);
-
-extern "C" int df_conv2d_mp(df_img x, const float* w, const float* bias, df_img y, int ksize, int stride, int pad,
-                            int mode, int epi, const float* scale, const float* shift, float* stats_partial,
-                            int accumulate, int mfma_bf16, void* stream) {
-  return conv2d_impl(x, w, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, mfma_bf16,
-                     false, stream);
+// df_conv2d (fp32 MFMA kernels, any supported shape) that also leaves max |y| in *y_amax (zero-initialised by the caller; see
+// df_absmax): the 1x1 and stride-2 convolutions whose output an fp16x2 convolution reads next
+extern "C" int df_conv2d_amax(df_img x, const float* w, const float* bias, df_img y, int ksize, int stride, int pad, int mode, int epi,
+                              const float* scale, const float* shift, float* stats_partial, int accumulate, float* y_amax,
+                              void* stream) {
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad; c.mode = mode; c.epi = epi; c.scale = scale; c.shift = shift;
+  c.stats = stats_partial; c.accumulate = accumulate; c.y_amax = y_amax; c.stream = stream;
+  return conv_launch(c);
 }
 
+// the bf16-tile form (conv_halo_w16_kernel): w16 = the pre-cast bf16 weights
 extern "C" int df_conv2d_w16(df_img x, const void* w16, const float* bias, df_img y, int ksize, int stride, int pad,
                              int mode, int epi, const float* scale, const float* shift, float* stats_partial,
                              int accumulate, void* stream) {
   DF_REQUIRE(w16 && df_aligned16(w16), DF_E_ALIGN);
-  return conv2d_impl(x, nullptr, w16, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 1, false,
-                     stream);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w16; c.weights = DF_CONV_W_B16; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad; c.mode = mode; c.epi = epi; c.scale = scale;
+  c.shift = shift; c.stats = stats_partial; c.accumulate = accumulate; c.mfma_bf16 = 1; c.stream = stream;
+  return conv_launch(c);
 }
 
 // fp32-accurate convolution through three bf16 planes per operand (conv_halo_x3_kernel): w3 = df_split_bf16x3 of the
@@ -1451,17 +1749,10 @@ extern "C" int df_conv2d_x3(df_img x, const void* w3, const float* bias, df_img 
                             int mode, int epi, const float* scale, const float* shift, float* stats_partial,
                             int accumulate, void* stream) {
   DF_REQUIRE(w3 && df_aligned16(w3), DF_E_ALIGN);
-  return conv2d_impl(x, nullptr, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false,
-                     stream, w3);
-}
-
-extern "C" int df_conv2d_x3_ok(df_img x, df_img y, int ksize, int stride, int mode, int epi) {
-  static const int on = getenv("DF_CONV_X3") ? atoi(getenv("DF_CONV_X3")) : 1;
-  if (!on || ksize != 3 || stride != 1) return 0;
-  const float* any = reinterpret_cast<const float*>(x.ptr);
-  const int r = conv2d_impl(x, nullptr, nullptr, nullptr, y, ksize, stride, 1, mode, epi, any, any, const_cast<float*>(any), 0, 0, true,
-                            nullptr, x.ptr);
-  return r == 1 ? 1 : 0;
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w3; c.weights = DF_CONV_W_X3; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad; c.mode = mode; c.epi = epi; c.scale = scale;
+  c.shift = shift; c.stats = stats_partial; c.accumulate = accumulate; c.stream = stream;
+  return conv_launch(c);
 }
 
 // fp32-accurate convolution through TWO fp16 planes per operand (conv_halo_x3_kernel<.., NP = 2>): w2 = df_split_h2 of the
@@ -1471,8 +1762,10 @@ extern "C" int df_conv2d_h2(df_img x, const void* w2, const float* x_amax, const
                             int ksize, int stride, int pad, int mode, int epi, const float* scale, const float* shift,
                             float* stats_partial, int accumulate, float* y_amax, void* stream) {
   DF_REQUIRE(w2 && df_aligned16(w2) && x_amax && w_amax, DF_E_ALIGN);
-  return conv2d_impl(x, nullptr, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false,
-                     stream, w2, x_amax, w_amax, y_amax);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w2; c.weights = DF_CONV_W_H2; c.x_amax = x_amax; c.w_amax = w_amax; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad;
+  c.mode = mode; c.epi = epi; c.scale = scale; c.shift = shift; c.stats = stats_partial; c.accumulate = accumulate; c.y_amax = y_amax; c.stream = stream;
+  return conv_launch(c);
 }
 
 // ... with PRE-SPLIT tensors (round 4): x may be an h2 image (x.elt = 2, scale = df_h2_scale(*x_amax): x_amax is then the bound
@@ -1483,11 +1776,14 @@ extern "C" int df_conv2d_h2p(df_img x, const void* w2, const float* x_amax, cons
                              const float* y_bound, int ksize, int stride, int pad, int mode, int epi, const float* scale,
                              const float* shift, float* stats_partial, int accumulate, float* y_amax, void* stream) {
   DF_REQUIRE(w2 && df_aligned16(w2) && x_amax && w_amax && epi != DF_EPI_BWD_STATS, DF_E_ALIGN);
-  return conv2d_impl(x, nullptr, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false,
-                     stream, w2, x_amax, w_amax, y_amax, y_bound);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w2; c.weights = DF_CONV_W_H2; c.x_amax = x_amax; c.w_amax = w_amax; c.bias = bias; c.y_bound = y_bound; c.ksize = ksize; c.stride = stride;
+  c.pad = pad; c.mode = mode; c.epi = epi; c.scale = scale; c.shift = shift; c.stats = stats_partial;
+  c.accumulate = accumulate; c.y_amax = y_amax; c.stream = stream;
+  return conv_launch(c);
 }
 
-// the 3x3 stride-1 fp16x2 DATA GRADIENT (x = dy: fp32 or pre-split; dz = fp32, contiguous) whose epilogue also leaves the partial
+// the 3x3 stride-1 fp16x2 DATA GRADIENT (x = dy: pre-split; dz = fp32, contiguous) whose epilogue also leaves the partial
 // sums of the BatchNorm + GELU backward of the layer in front -- per tile and channel (sum g, sum g xhat), g = dz gelu'(bn(y)) --
 // in bwd_partial ([rows / df_conv2d_tile_m][C][2], the layout df_bn_bwd_finalize reads): bn_y = that layer's conv output (the
 // geometry of dz), bn_ss = its statistics per group of dz.grp_size images.  Replaces one full pass over dz and y per layer
@@ -1495,21 +1791,39 @@ extern "C" int df_conv2d_h2p(df_img x, const void* w2, const float* x_amax, cons
 extern "C" int df_conv2d_h2p_dgrad_bn(df_img x, const void* w2, const float* x_amax, const float* w_amax, df_img dz, const float* bn_y,
                                       const float* bn_ss, float* bwd_partial, float* dz_amax, void* stream) {
   DF_REQUIRE(w2 && df_aligned16(w2) && x_amax && w_amax && bn_y && bn_ss && bwd_partial, DF_E_ALIGN);
-  return conv2d_impl(x, nullptr, nullptr, nullptr, dz, 3, 1, 1, DF_CONV_DGRAD, DF_EPI_BWD_STATS, nullptr, nullptr, bwd_partial, 0, 0, false,
-                     stream, w2, x_amax, w_amax, dz_amax, nullptr, bn_y, bn_ss);
+  ConvCall c;
+  c.x = x; c.y = dz; c.w = w2; c.weights = DF_CONV_W_H2; c.x_amax = x_amax; c.w_amax = w_amax; c.ksize = 3; c.stride = 1; c.pad = 1; c.mode = DF_CONV_DGRAD;
+  c.epi = DF_EPI_BWD_STATS; c.stats = bwd_partial; c.bwd_y = bn_y; c.bwd_ss = bn_ss; c.y_amax = dz_amax; c.stream = stream;
+  return conv_launch(c);
 }
 
-extern "C" int df_conv2d_h2p_ok(df_img x, df_img y, int ksize, int stride, int mode, int epi) {
-  static const int on = getenv("DF_CONV_X3") ? atoi(getenv("DF_CONV_X3")) : 1;
-  if (!on || ksize != 3 || stride != 1) return 0;
-  const float* any = reinterpret_cast<const float*>(x.ptr);
-  const int r = conv2d_impl(x, nullptr, nullptr, nullptr, y, ksize, stride, 1, mode, epi, any, any, const_cast<float*>(any), 0, 0, true,
-                            nullptr, x.ptr, any, any, nullptr, any);
-  return r == 1 ? 1 : 0;
+// fp16x2 for the convolutions WITHOUT a haloed form (1x1, stride 2; conv_dma_kernel<.., H2>): fp32 weights as they are (the
+// fragments are split in registers), x_amax / w_amax as for df_conv2d_h2.  Shapes the 8-wave DMA kernels do not cover run the fp32
+// kernels of df_conv2d (same result class, no error).
+extern "C" int df_conv2d_h2f(df_img x, const float* w, const float* x_amax, const float* w_amax, const float* bias, df_img y,
+                             int ksize, int stride, int pad, int mode, int epi, const float* scale, const float* shift,
+                             float* stats_partial, int accumulate, float* y_amax, void* stream) {
+  DF_REQUIRE(x_amax && w_amax, DF_E_ARG);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w; c.weights = DF_CONV_W_F32_H2; c.x_amax = x_amax; c.w_amax = w_amax; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad;
+  c.mode = mode; c.epi = epi; c.scale = scale; c.shift = shift; c.stats = stats_partial; c.accumulate = accumulate; c.y_amax = y_amax; c.stream = stream;
+  return conv_launch(c);
 }
 
-// the fp32-input kernels of df_conv2d_mp / df_conv2d_h2f / df_conv2d_amax with an h2 OUTPUT (y.elt = 2, scale from *y_bound): the
-// 1x1 convolutions that write a half of a pre-split concatenation, the 1x1 data gradients that feed a pre-split 3x3 layer
+// the fp32-input kernels of df_conv2d_mp / df_conv2d_h2f with an h2 OUTPUT (y.elt = 2, scale from *y_bound; no y_amax): the 1x1
+// convolutions that write a half of a pre-split concatenation, the 1x1 data gradients that feed a pre-split 3x3 layer.  x_amax and
+// w_amax both given: fp16x2 on the fragments as df_conv2d_h2f
+extern "C" int df_conv2d_yh2(df_img x, const float* w, const float* x_amax, const float* w_amax, const float* bias, df_img y,
+                             const float* y_bound, int ksize, int stride, int pad, int mode, int epi, const float* scale,
+                             const float* shift, float* stats_partial, int accumulate, void* stream) {
+  DF_REQUIRE(y.elt == 2 && y_bound, DF_E_ARG);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w; c.weights = (x_amax && w_amax) ? DF_CONV_W_F32_H2 : DF_CONV_W_F32; c.x_amax = x_amax; c.w_amax = w_amax; c.bias = bias; c.y_bound = y_bound;
+  c.ksize = ksize; c.stride = stride; c.pad = pad; c.mode = mode; c.epi = epi;
+  c.scale = scale; c.shift = shift; c.stats = stats_partial; c.accumulate = accumulate; c.stream = stream;
+  return conv_launch(c);
+}
+
 // df_conv2d_h2f / df_conv2d_yh2 (y.elt = 2: y_bound required, no y_amax) with the weights ALSO given pre-split: w2 = the [hi | lo]
 // fp16 planes of w scaled by df_h2_scale(*w_amax) (df_split_h2, or the layer's planes from df_weight_prep) -- conv_dma_kernel<.., H2,
 // BP> fetches them by DMA instead of splitting the fp32 weight fragments in every wave; w (fp32) is still what the tile forms
@@ -1518,8 +1832,11 @@ extern "C" int df_conv2d_h2f_wp(df_img x, const float* w, const void* w2, const 
                                 df_img y, const float* y_bound, int ksize, int stride, int pad, int mode, int epi, const float* scale,
                                 const float* shift, float* stats_partial, int accumulate, float* y_amax, void* stream) {
   DF_REQUIRE(x_amax && w_amax && w2 && df_aligned16(w2) && (y.elt != 2 || y_bound), DF_E_ARG);
-  return conv2d_impl(x, w, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false, stream,
-                     nullptr, x_amax, w_amax, y.elt == 2 ? nullptr : y_amax, y.elt == 2 ? y_bound : nullptr, nullptr, nullptr, w2);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w; c.weights = DF_CONV_W_WP; c.w2p = w2; c.x_amax = x_amax; c.w_amax = w_amax; c.bias = bias; c.ksize = ksize; c.stride = stride; c.pad = pad;
+  c.mode = mode; c.epi = epi; c.scale = scale; c.shift = shift; c.stats = stats_partial; c.accumulate = accumulate; c.stream = stream;
+  if (y.elt == 2) c.y_bound = y_bound; else c.y_amax = y_amax;
+  return conv_launch(c);
 }
 
 // df_conv2d_h2f_wp for the 1x1 skip convolution of an UpsampleSkip block (forward, bias epilogue, y = the SECOND half of the pre-split
@@ -1530,36 +1847,10 @@ extern "C" int df_conv2d_h2f_wp(df_img x, const float* w, const void* w2, const 
 extern "C" int df_conv2d_h2f_wp_up(df_img x, const float* w, const void* w2, const float* x_amax, const float* w_amax, const float* bias,
                                    df_img y, const float* y_bound, df_img t, int align_corners, void* stream) {
   DF_REQUIRE(x_amax && w_amax && w2 && df_aligned16(w2) && y.elt == 2 && y_bound, DF_E_ARG);
-  return conv2d_impl(x, w, nullptr, bias, y, 1, 1, 0, DF_CONV_FWD, DF_EPI_BIAS, nullptr, nullptr, nullptr, 0, 0, false, stream, nullptr, x_amax,
-                     w_amax, nullptr, y_bound, nullptr, nullptr, w2, &t, align_corners);
-}
-
-extern "C" int df_conv2d_yh2(df_img x, const float* w, const float* x_amax, const float* w_amax, const float* bias, df_img y,
-                             const float* y_bound, int ksize, int stride, int pad, int mode, int epi, const float* scale,
-                             const float* shift, float* stats_partial, int accumulate, void* stream) {
-  DF_REQUIRE(y.elt == 2 && y_bound, DF_E_ARG);
-  return conv2d_impl(x, w, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false, stream,
-                     nullptr, x_amax, w_amax, nullptr, y_bound);
-}
-
-// fp16x2 for the convolutions WITHOUT a haloed form (1x1, stride 2; conv_dma_kernel<.., H2>): fp32 weights as they are (the
-// fragments are split in registers), x_amax / w_amax as for df_conv2d_h2.  Shapes the 8-wave DMA kernels do not cover run the fp32
-// kernels of df_conv2d (same result class, no error).
-extern "C" int df_conv2d_h2f(df_img x, const float* w, const float* x_amax, const float* w_amax, const float* bias, df_img y,
-                             int ksize, int stride, int pad, int mode, int epi, const float* scale, const float* shift,
-                             float* stats_partial, int accumulate, float* y_amax, void* stream) {
-  DF_REQUIRE(x_amax && w_amax, DF_E_ARG);
-  return conv2d_impl(x, w, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false, stream,
-                     nullptr, x_amax, w_amax, y_amax);
-}
-
-// df_conv2d (fp32 MFMA kernels, any supported shape) that also leaves max |y| in *y_amax (zero-initialised by the caller; see
-// df_absmax): the 1x1 and stride-2 convolutions whose output an fp16x2 convolution reads next
-extern "C" int df_conv2d_amax(df_img x, const float* w, const float* bias, df_img y, int ksize, int stride, int pad, int mode, int epi,
-                              const float* scale, const float* shift, float* stats_partial, int accumulate, float* y_amax,
-                              void* stream) {
-  return conv2d_impl(x, w, nullptr, bias, y, ksize, stride, pad, mode, epi, scale, shift, stats_partial, accumulate, 0, false, stream,
-                     nullptr, nullptr, nullptr, y_amax);
+  ConvCall c;
+  c.x = x; c.y = y; c.w = w; c.weights = DF_CONV_W_WP; c.w2p = w2; c.x_amax = x_amax; c.w_amax = w_amax; c.bias = bias; c.y_bound = y_bound; c.ksize = 1; c.stride = 1;
+  c.pad = 0; c.mode = DF_CONV_FWD; c.epi = DF_EPI_BIAS; c.ups = &t; c.ups_ac = align_corners; c.stream = stream;
+  return conv_launch(c);
 }
 
 extern "C" int df_absmax(df_img x, float* amax, void* stream) {
@@ -1592,305 +1883,4 @@ extern "C" int df_split_bf16x3(const float* w, void* out3, int64_t n, void* stre
   DF_CHECK_LAUNCH();
   return DF_OK;
 }
-
-extern "C" int df_conv2d_w16_ok(df_img x, df_img y, int ksize, int stride, int mode, int epi) {
-  static const int on = getenv("DF_CONV_W16") ? atoi(getenv("DF_CONV_W16")) : 1;
-  if (!on || (ksize != 1 && ksize != 3)) return 0;
-  const float* any = reinterpret_cast<const float*>(x.ptr);   // argument checks only: nothing is dereferenced in query mode
-  const int r = conv2d_impl(x, nullptr, x.ptr, nullptr, y, ksize, stride, ksize / 2, mode, epi, any, any, const_cast<float*>(any), 0,
-                            1, true, nullptr);
-  return r == 1 ? 1 : 0;
-}
-
-static int conv2d_impl(df_img x, const float* w, const void* w16, const float* bias, df_img y, int ksize, int stride, int pad,
-                       int mode, int epi, const float* scale, const float* shift, float* stats_partial,
-                       int accumulate, int mfma_bf16, bool query, void* stream, const void* w3, const float* h2_amax_x,
-                       const float* h2_amax_w, float* y_amax, const float* y_bound, const float* bwd_y, const float* bwd_ss,
-                       const void* w2p, const df_img* ups_t, int ups_ac) {
-  if (w3) w = reinterpret_cast<const float*>(w3);   // (argument checks below want a non-null, aligned weight pointer)
-  // bfloat16 tensors (bf16-storage training): the input only for the bf16-tile kernel (df_conv2d_w16), the output for any
-  // kernel with the branch-free epilogue
-  DF_REQUIRE(img_ok(x, w16 != nullptr || (w3 && h2_amax_x)) && img_ok(y, true) && (w16 || (w && df_aligned16(w))), DF_E_ALIGN);
-  DF_REQUIRE((x.elt != 2 || (w3 && h2_amax_x)) && (x.elt != 1 || w16), DF_E_ARG);      // h2 input: the fp16x2 haloed form only
-  // h2 output: a bound, no accumulation (the planes of two scales do not add), whole 32-channel chunks at 128-byte lines
-  if (y.elt == 2)
-    DF_REQUIRE((query || y_bound) && !accumulate && (y.ld % 32) == 0 && (y.img_stride % 32) == 0 && (y.grp_off % 32) == 0 &&
-               (((uintptr_t)y.ptr) & 127) == 0, DF_E_ARG);
-  if (x.elt == 2)
-    DF_REQUIRE((x.ld % 32) == 0 && (x.img_stride % 32) == 0 && (x.grp_off % 32) == 0 && (((uintptr_t)x.ptr) & 127) == 0, DF_E_ARG);
-  const int xes = x.elt == 1 ? 2 : 4, yes = y.elt == 1 ? 2 : 4;
-  DF_REQUIRE(x.n == y.n, DF_E_SHAPE);
-  DF_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && pad == ksize / 2, DF_E_SHAPE);
-  DF_REQUIRE(mode == DF_CONV_FWD || mode == DF_CONV_DGRAD, DF_E_ARG);
-  DF_REQUIRE(epi >= 0 && epi <= 3, DF_E_ARG);
-  DF_REQUIRE(x.c % BK == 0 && y.c % 32 == 0, DF_E_SHAPE);
-  if (mode == DF_CONV_FWD) {
-    DF_REQUIRE(y.h == (x.h + 2 * pad - ksize) / stride + 1 && y.w == (x.w + 2 * pad - ksize) / stride + 1, DF_E_SHAPE);
-  } else {
-    DF_REQUIRE(x.h == (y.h + 2 * pad - ksize) / stride + 1 && x.w == (y.w + 2 * pad - ksize) / stride + 1, DF_E_SHAPE);
-  }
-  if (epi == DF_EPI_BN_GELU) DF_REQUIRE(scale && shift, DF_E_ARG);
-  if (epi_stats(epi)) DF_REQUIRE(stats_partial, DF_E_ARG);
-  if (epi == DF_EPI_BWD_STATS)      // fused BatchNorm-backward partials: the fp16x2 data gradient with a plain fp32 output only
-    DF_REQUIRE(mode == DF_CONV_DGRAD && w3 && h2_amax_x && x.elt == 2 && (query || (bwd_y && bwd_ss)) && y.elt == 0 && !accumulate && y.ld == y.c &&
-                   !bias, DF_E_ARG);
-  ConvParams p;
-  p.x = x; p.y = y; p.w = w; p.bias = bias; p.scale = scale; p.shift = shift; p.stats = stats_partial;
-  p.ks = ksize; p.stride = stride; p.pad = pad; p.mode = mode; p.epi = epi; p.accumulate = accumulate;
-  p.bf16 = mfma_bf16 != 0;
-  p.stats_mul = 1;
-  p.amax_x = h2_amax_x;      // (used by the fp16x2 forms only: conv_halo_x3_kernel<NP = 2> below, conv_dma_kernel<.., H2>)
-  p.amax_w = h2_amax_w;
-  p.w2p = w2p;
-  p.amax_y = reinterpret_cast<unsigned*>(y_amax);
-  p.bound_y = y_bound;
-  p.bwd_y = bwd_y;
-  p.bwd_ss = bwd_ss;
-  static const int conv_rot = getenv("DF_CONV_ROT") ? atoi(getenv("DF_CONV_ROT")) : 1;
-  p.rot = conv_rot;
-  static const int cls_il = getenv("DF_CONV_CLS_IL") ? atoi(getenv("DF_CONV_CLS_IL")) : 1;
-  p.cls_il = cls_il;
-  p.ups_on = 0; p.ups_ac = ups_ac;
-  if (ups_t) {   // df_conv2d_h2f_wp_up: a 1x1 forward conv into the second half of a pre-split concatenation, fp32 t of half the resolution
-    const df_img& t = *ups_t;
-    DF_REQUIRE(!w3 && !w16 && ksize == 1 && stride == 1 && mode == DF_CONV_FWD && epi == DF_EPI_BIAS && !accumulate && y.elt == 2 && x.elt == 0 &&
-                   w2p && h2_amax_x && h2_amax_w && !mfma_bf16, DF_E_ARG);
-    DF_REQUIRE(t.ptr && df_aligned16(t.ptr) && t.elt == 0 && t.n == y.n && t.c == y.c && 2 * t.h == y.h && 2 * t.w == y.w && (t.c % 8) == 0 &&
-                   (t.ld % 4) == 0 && (t.img_stride % 4) == 0 && (t.grp_off % 4) == 0 && t.grp_size > 0 && (y.ld % 32) == 0 && y.ld >= 2 * y.c,
-               DF_E_SHAPE);
-    p.ups_t = t;
-    p.ups_on = 1;
-  }
-  p.hw_y = y.h * y.w;
-  const int64_t M = (int64_t)y.n * p.hw_y;
-  DF_REQUIRE(M < (1ll << 31), DF_E_SHAPE);
-  p.M = (int)M; p.K = x.c; p.N = y.c;
-  p.cls_tiles = 0;
-  static const int dbg_env = getenv("DF_CONV_DBG") ? atoi(getenv("DF_CONV_DBG")) : 0;
-  p.dbg = dbg_env;
-  const int64_t rows_per_group = (int64_t)y.grp_size * p.hw_y;
-  int64_t rows = M;
-  const bool cls = mode == DF_CONV_DGRAD && stride == 2 && ksize == 3 && epi == DF_EPI_BIAS && (y.h % 2) == 0 && (y.w % 2) == 0;
-  if (cls) rows = M / 4;
-  int var = pick_variant(rows, rows_per_group, p.N, epi);
-  int bm = var / 1000;
-  if (epi_stats(epi)) DF_REQUIRE(rows_per_group % bm == 0, DF_E_SHAPE);
-  if (cls && rows % bm == 0) {
-    p.cls_tiles = (int)(rows / bm);
-    p.tiles_m = 4 * p.cls_tiles;
-  } else {
-    if (cls) { var = pick_variant(M, rows_per_group, p.N, epi); bm = var / 1000; }
-    p.tiles_m = (int)((M + bm - 1) / bm);
-  }
-  p.tiles_n = p.N / (var % 1000);
-  // LDS-DMA path needs 32-bit byte offsets: extent of x (+ the shift that keeps the top-left tap offset >= 0)
-  p.x_bytes = p.w_bytes = p.dshift = 0;
-  {
-    static const int no_dma = getenv("DF_CONV_NO_DMA") ? atoi(getenv("DF_CONV_NO_DMA")) : 0;
-    const int64_t groups = x.n / x.grp_size;
-    const int64_t ext = ((int64_t)(x.grp_size - 1) * x.img_stride + (groups - 1) * x.grp_off + (int64_t)x.h * x.w * x.ld) * xes;
-    const int64_t dsh = (p.cls_tiles > 0) ? 0 : (int64_t)pad * ((int64_t)x.w + 1) * x.ld * xes;
-    const int64_t wb = (int64_t)p.N * ksize * ksize * p.K * 4;
-    const bool geom_ok = !(mode == DF_CONV_DGRAD && stride == 2 && p.cls_tiles == 0);  // generic s2 dgrad: register path
-    if (!no_dma && geom_ok && x.img_stride >= 0 && x.grp_off >= 0 && ext + dsh < (int64_t)DMA_BAD - (16 << 20) && wb < (1ll << 31) &&
-        ((int64_t)2 * x.w + 2) * x.ld * 4 + (int64_t)p.K * 4 < (8 << 20)) {
-      p.x_bytes = (unsigned)(ext + dsh);
-      p.w_bytes = (unsigned)wb;
-      p.dshift = (unsigned)dsh;
-    }
-  }
-  {
-    static const int wide_epi = getenv("DF_CONV_WIDE_EPI") ? atoi(getenv("DF_CONV_WIDE_EPI")) : 0;
-    const int64_t ygroups = y.n / y.grp_size;
-    const int64_t yext = ((int64_t)(y.grp_size - 1) * y.img_stride + (ygroups - 1) * y.grp_off + (int64_t)y.h * y.w * y.ld) * yes;
-    p.y_bytes = ((!wide_epi || y.elt) && y.img_stride >= 0 && y.grp_off >= 0 && yext < (int64_t)0xFFFFFFFFll - (16 << 20)) ? (unsigned)yext : 0u;
-    if (y.elt) DF_REQUIRE(p.y_bytes != 0 && p.x_bytes != 0, DF_E_SHAPE);   // bf16 output: only the DMA kernels' straight-line epilogue
-  }
-  if (!query) g_last_dma = p.x_bytes != 0;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // haloed-A kernel: 3x3 stride 1 (fwd / dgrad), rows of 128 output pixels inside one image row, full tiles only
-  static const int use_halo = getenv("DF_CONV_HALO") ? atoi(getenv("DF_CONV_HALO")) : 1;
-  const bool halo_ok = use_halo && p.x_bytes && ksize == 3 && stride == 1 && p.cls_tiles == 0 && (y.w % 128) == 0 &&
-                       x.w == y.w && x.h == y.h && (var == 128128 || var == 128064);
-  if (w3) {    // df_conv2d_x3: fp32-accurate product from three bf16 planes per operand (W % 128 == 0, or W == 64 as row pairs)
-    const bool two = p.x_bytes && ksize == 3 && stride == 1 && p.cls_tiles == 0 && y.w == 64 && (y.h % 2) == 0 && x.w == y.w &&
-                     x.h == y.h && (var == 128128 || var == 128064);
-    const bool h2 = h2_amax_x != nullptr;        // two fp16 planes (df_conv2d_h2) instead of three bf16 ones
-    const bool xp = x.elt == 2;                  // pre-split input (h2 image): the 256 x 128 / 512 x 64 tile forms below only
-    bool ok = (halo_ok || two) && (p.K % BK) == 0 && (x.elt == 0 || (xp && h2)) && (y.elt == 0 || (y.elt == 2 && h2));
-    if (ok && xp) {
-      const int seg_ = (y.w % 256) == 0 ? 1 : y.w == 128 ? 2 : y.w == 64 ? 4 : 0;
-      const int seg64_ = (y.w % 512) == 0 ? 1 : y.w == 256 ? 2 : 0;
-      const bool big128 = var == 128128 && seg_ && (y.h % seg_) == 0 && (M % 256) == 0 && (!epi_stats(epi) || rows_per_group % 256 == 0) &&
-                          M / 256 * p.tiles_n >= 512;
-      const bool big64 = var != 128128 && !two && seg64_ && (y.h % seg64_) == 0 && (M % 512) == 0 &&
-                         (!epi_stats(epi) || rows_per_group % 512 == 0) && M / 512 >= 512;
-      ok = big128 || big64;
-    }
-    if (query) return ok ? 1 : 0;
-    DF_REQUIRE(ok, DF_E_SHAPE);
-    p.w = reinterpret_cast<const float*>(w3);
-    p.w_bytes = (unsigned)((int64_t)p.N * 9 * p.K * 2 * (h2 ? 2 : 3));
-    p.bf16 = 0;
-    p.amax_x = h2_amax_x;
-    p.amax_w = h2_amax_w;
-    static const int bm256 = getenv("DF_CONV_X3_BM256") ? atoi(getenv("DF_CONV_X3_BM256")) : 1;
-    // 64 output channels: 256-pixel row tiles where the image allows (wave tile 64 x 32 instead of 32 x 32)
-    const bool wide = !two && var != 128128 && bm256 && (y.w % 256) == 0 && (M % 256) == 0 && (!epi_stats(epi) || rows_per_group % 256 == 0);
-    if (wide) {
-      p.tiles_m = (int)(M / 256);
-      p.stats_mul = 2;
-    }
-    if (h2) {
-      // 128-multiple output channels: 256 x 128 tiles whose waves own 64 x 64 (8 fragment reads per 12 MFMAs instead of 6 per 6 --
-      // the 128 x 128 form reads LDS for as many cycles as it multiplies) where the rows allow: 256 pixels of one image row, two
-      // rows of a W == 128 image, four of a W == 64 one
-      static const int big = getenv("DF_CONV_H2_BM256") ? atoi(getenv("DF_CONV_H2_BM256")) : 1;
-      const int seg = (y.w % 256) == 0 ? 1 : y.w == 128 ? 2 : y.w == 64 ? 4 : 0;
-      if (big && var == 128128 && seg && (y.h % seg) == 0 && (M % 256) == 0 && (!epi_stats(epi) || rows_per_group % 256 == 0) &&
-          M / 256 * p.tiles_n >= 512) {
-        p.tiles_m = (int)(M / 256);
-        p.stats_mul = 2;
-        static const int pers = getenv("DF_CONV_PERS") ? atoi(getenv("DF_CONV_PERS")) : 1;
-        if (xp && pers && epi == DF_EPI_BWD_STATS) {
-          return df_launch_conv_halo_x3p(p, 128, seg, true, s);
-        }
-        if (xp && pers) {
-          return df_launch_conv_halo_x3p(p, 128, seg, false, s);
-        }
-        if (xp && epi == DF_EPI_BWD_STATS) {
-          if (seg == 1) return launch_conv_halo_x3<256, 128, 4, 2, 1, 4, 2, false, true, true>(p, s);
-          if (seg == 2) return launch_conv_halo_x3<256, 128, 4, 2, 2, 4, 2, false, true, true>(p, s);
-          return launch_conv_halo_x3<256, 128, 4, 2, 4, 4, 2, false, true, true>(p, s);
-        }
-        if (xp) {
-          if (seg == 1) return launch_conv_halo_x3<256, 128, 4, 2, 1, 4, 2, false, true>(p, s);
-          if (seg == 2) return launch_conv_halo_x3<256, 128, 4, 2, 2, 4, 2, false, true>(p, s);
-          return launch_conv_halo_x3<256, 128, 4, 2, 4, 4, 2, false, true>(p, s);
-        }
-        if (seg == 1) return launch_conv_halo_x3<256, 128, 4, 2, 1, 4, 2>(p, s);
-        if (seg == 2) return launch_conv_halo_x3<256, 128, 4, 2, 2, 4, 2>(p, s);
-        return launch_conv_halo_x3<256, 128, 4, 2, 4, 4, 2>(p, s);
-      }
-      // 64 output channels: 512 x 64 tiles (8 x 1 waves of 64 x 64): 512 pixels of one row, or two rows of a W == 256 image
-      const int seg64 = (y.w % 512) == 0 ? 1 : y.w == 256 ? 2 : 0;
-      if (big && var != 128128 && !two && seg64 && (y.h % seg64) == 0 && (M % 512) == 0 && (!epi_stats(epi) || rows_per_group % 512 == 0) &&
-          M / 512 >= 512) {
-        p.tiles_m = (int)(M / 512);
-        p.stats_mul = 4;
-        static const int pers64 = getenv("DF_CONV_PERS") ? atoi(getenv("DF_CONV_PERS")) : 1;
-        if (xp && pers64 && epi == DF_EPI_BWD_STATS)
-          return df_launch_conv_halo_x3p(p, 64, seg64, true, s);
-        if (xp && pers64) return df_launch_conv_halo_x3p(p, 64, seg64, false, s);
-        if (xp && epi == DF_EPI_BWD_STATS)
-          return seg64 == 1 ? launch_conv_halo_x3<512, 64, 8, 1, 1, 3, 2, false, true, true>(p, s) : launch_conv_halo_x3<512, 64, 8, 1, 2, 3, 2, false, true, true>(p, s);
-        if (xp) return seg64 == 1 ? launch_conv_halo_x3<512, 64, 8, 1, 1, 3, 2, false, true>(p, s) : launch_conv_halo_x3<512, 64, 8, 1, 2, 3, 2, false, true>(p, s);
-        return seg64 == 1 ? launch_conv_halo_x3<512, 64, 8, 1, 1, 3, 2>(p, s) : launch_conv_halo_x3<512, 64, 8, 1, 2, 3, 2>(p, s);
-      }
-      DF_REQUIRE(!xp, DF_E_SHAPE);
-      if (two) return var == 128128 ? launch_conv_halo_x3<128, 128, 2, 4, 2, 4, 2>(p, s) : launch_conv_halo_x3<128, 64, 4, 2, 2, 8, 2>(p, s);
-      if (var == 128128) return launch_conv_halo_x3<128, 128, 2, 4, 1, 4, 2>(p, s);
-      if (wide) return launch_conv_halo_x3<256, 64, 4, 2, 1, 4, 2>(p, s);
-      return launch_conv_halo_x3<128, 64, 4, 2, 1, 8, 2>(p, s);
-    }
-    if (two) return var == 128128 ? launch_conv_halo_x3<128, 128, 2, 4, 2, 4>(p, s) : launch_conv_halo_x3<128, 64, 4, 2, 2, 8>(p, s);
-    if (var == 128128) return launch_conv_halo_x3<128, 128, 2, 4, 1, 4>(p, s);
-    if (wide) return launch_conv_halo_x3<256, 64, 4, 2, 1, 4>(p, s);
-    return launch_conv_halo_x3<128, 64, 4, 2, 1, 8>(p, s);
-  }
-  if (w16) {   // df_conv2d_w16: bf16 tiles in LDS, only the haloed forms exist (W % 128 == 0, or W == 64 as row pairs)
-    const bool two = p.x_bytes && ksize == 3 && stride == 1 && p.cls_tiles == 0 && y.w == 64 && (y.h % 2) == 0 && x.w == y.w &&
-                     x.h == y.h && (var == 128128 || var == 128064);
-    const bool ok = (halo_ok || two) && (p.K % BK) == 0;
-    if (query) return ok ? 1 : 0;
-    DF_REQUIRE(ok, DF_E_SHAPE);
-    p.w = reinterpret_cast<const float*>(w16);
-    p.w_bytes = p.w_bytes / 2;
-    p.bf16 = 1;
-    static const int w4 = getenv("DF_W16_WAVES4") ? atoi(getenv("DF_W16_WAVES4")) : 0;   // bit 0: 128-wide, bit 1: 64-wide tiles on 4 waves
-    {   // DF_W16_WIDE=1 (A/B; default off): the large tiles of the fp16x2 kernel with ONE bf16 plane (64 x 64 wave tiles: 4 fragment
-        // reads per 4 MFMAs; the 128 x 128 forms below read 3 per 2).  Measured SLOWER than the forms below at the bench shape
-        // (bf16 step 42.8 vs 41.4 ms; 700-930 vs 820-1000 TFLOP/s per layer): with one plane the kernel is not LDS-read-bound, and
-        // this kernel's register-staged halo costs more than conv_halo_w16_kernel's
-      static const int wide = getenv("DF_W16_WIDE") ? atoi(getenv("DF_W16_WIDE")) : 0;
-      const int seg = (y.w % 256) == 0 ? 1 : y.w == 128 ? 2 : y.w == 64 ? 4 : 0;
-      if (wide && var == 128128 && seg && (y.h % seg) == 0 && (M % 256) == 0 && (!epi_stats(epi) || rows_per_group % 256 == 0) &&
-          M / 256 * p.tiles_n >= 512) {
-        p.tiles_m = (int)(M / 256);
-        p.stats_mul = 2;
-        if (x.elt) {
-          if (seg == 1) return launch_conv_halo_x3<256, 128, 4, 2, 1, 8, 1, true>(p, s);
-          if (seg == 2) return launch_conv_halo_x3<256, 128, 4, 2, 2, 8, 1, true>(p, s);
-          return launch_conv_halo_x3<256, 128, 4, 2, 4, 8, 1, true>(p, s);
-        }
-        if (seg == 1) return launch_conv_halo_x3<256, 128, 4, 2, 1, 8, 1, false>(p, s);
-        if (seg == 2) return launch_conv_halo_x3<256, 128, 4, 2, 2, 8, 1, false>(p, s);
-        return launch_conv_halo_x3<256, 128, 4, 2, 4, 8, 1, false>(p, s);
-      }
-      const int seg64 = (y.w % 512) == 0 ? 1 : y.w == 256 ? 2 : 0;    // 64 output channels: 512 x 64 tiles, 8 x 1 waves
-      if (wide && var == 128064 && seg64 && (y.h % seg64) == 0 && (M % 512) == 0 && (!epi_stats(epi) || rows_per_group % 512 == 0) &&
-          M / 512 >= 512) {
-        p.tiles_m = (int)(M / 512);
-        p.stats_mul = 4;
-        if (x.elt) return seg64 == 1 ? launch_conv_halo_x3<512, 64, 8, 1, 1, 8, 1, true>(p, s) : launch_conv_halo_x3<512, 64, 8, 1, 2, 8, 1, true>(p, s);
-        return seg64 == 1 ? launch_conv_halo_x3<512, 64, 8, 1, 1, 8, 1, false>(p, s) : launch_conv_halo_x3<512, 64, 8, 1, 2, 8, 1, false>(p, s);
-      }
-    }
-    if (x.elt) {   // bf16 activations in memory: 8-wave forms only
-      if (halo_ok) return var == 128128 ? launch_conv_halo_w16<128, 2, 4, 1, true>(p, s) : launch_conv_halo_w16<64, 4, 2, 1, true>(p, s);
-      return var == 128128 ? launch_conv_halo_w16<128, 2, 4, 2, true>(p, s) : launch_conv_halo_w16<64, 4, 2, 2, true>(p, s);
-    }
-    if (halo_ok) {
-      if (var == 128128) return (w4 & 1) ? launch_conv_halo_w16<128, 2, 2>(p, s) : launch_conv_halo_w16<128, 2, 4>(p, s);
-      return (w4 & 2) ? launch_conv_halo_w16<64, 2, 2>(p, s) : launch_conv_halo_w16<64, 4, 2>(p, s);
-    }
-    if (var == 128128) return (w4 & 1) ? launch_conv_halo_w16<128, 2, 2, 2>(p, s) : launch_conv_halo_w16<128, 2, 4, 2>(p, s);
-    return (w4 & 2) ? launch_conv_halo_w16<64, 2, 2, 2>(p, s) : launch_conv_halo_w16<64, 4, 2, 2>(p, s);
-  }
-  DF_REQUIRE(x.elt == 0, DF_E_ARG);
-  if (p.ups_on) {      // only the 8-wave DMA kernels with pre-split weights carry the UPS form
-    DF_REQUIRE(p.x_bytes && p.w2p && p.amax_x && p.amax_w && !p.bf16, DF_E_SHAPE);
-    switch (var) {
-      case 128032: return launch_conv_w8<128, 32, 4, 1>(p, s);
-      case 64064: return launch_conv_w8<64, 64, 2, 2>(p, s);
-      case 128128: return launch_conv_w8<128, 128, 4, 2>(p, s);
-      case 256064: return launch_conv_w8<256, 64, 4, 2>(p, s);
-      default: return launch_conv_w8<128, 64, 4, 2>(p, s);
-    }
-  }
-  switch (var) {
-    // (round 5: the small tiles chosen for layers with few pixels -- a B = 1 forward -- ran on the fp32 MFMA whatever the caller asked
-    // for: launch_conv has no fp16x2 form.  With a bound on x and w they take the DMA-tile kernel's H2 forms like the large tiles.)
-    case 128032:
-      if (p.x_bytes && p.amax_x && p.amax_w) return launch_conv_w8<128, 32, 4, 1>(p, s);
-      return launch_conv<128, 32, 4, 1>(p, s);
-    case 64064:
-      if (p.x_bytes && p.amax_x && p.amax_w) return launch_conv_w8<64, 64, 2, 2>(p, s);
-      return launch_conv<64, 64, 2, 2>(p, s);
-    case 128128: {
-      static const int w8 = getenv("DF_CONV_W8") ? atoi(getenv("DF_CONV_W8")) : 3;
-      if (halo_ok) return launch_conv_halo<128, 2, 4>(p, s);
-      // pre-split weights (BP): B fragments cost no VALU, so the wave grid that shares an A fragment among FEWER waves wins -- 4 x 2
-      // (each wave splits one 32-row A fragment per 6 MFMAs) instead of 2 x 4 (two per 6, each redone by four waves)
-      static const int bp42 = getenv("DF_CONV_BP42") ? atoi(getenv("DF_CONV_BP42")) : 1;
-      if ((w8 & 1) && p.x_bytes && p.w2p && p.amax_x && p.amax_w && bp42) return launch_conv_w8<128, 128, 4, 2>(p, s);
-      if ((w8 & 1) && p.x_bytes) return launch_conv_w8<128, 128, 2, 4>(p, s);
-      return launch_conv<128, 128, 2, 2>(p, s);
-    }
-    case 256064: {
-      static const int w8 = getenv("DF_CONV_W8") ? atoi(getenv("DF_CONV_W8")) : 3;
-      if ((w8 & 4) && p.x_bytes) return launch_conv_w8<256, 64, 4, 2>(p, s);
-      return launch_conv<256, 64, 4, 1>(p, s);
-    }
-    default: {
-      static const int w8 = getenv("DF_CONV_W8") ? atoi(getenv("DF_CONV_W8")) : 3;
-      if (halo_ok) return launch_conv_halo<64, 4, 2>(p, s);
-      // (with pre-split weights a 4 x 1 grid -- 32 x 64 wave tiles, one A split per 6 MFMAs, but 4 waves per workgroup -- measured
-      // 9-33 % SLOWER than 4 x 2 on the four 64-wide layers: occupancy beats the split count here)
-      if ((w8 & 2) && p.x_bytes) return launch_conv_w8<128, 64, 4, 2>(p, s);
-      return launch_conv<128, 64, 2, 2>(p, s);
-    }
-  }
-}
-
 

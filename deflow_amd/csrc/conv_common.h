@@ -357,5 +357,5 @@ using namespace dfconv;
 
 // conv_x3p.hip (its own translation unit since round 6: the persistent pre-split 3x3 kernels -- 28 of the step's 70 ms -- compile in
 // under a minute there instead of behind conv.hip's 3.5): tile form bm x bn = 256 x 128 (seg 1 / 2 / 4) or 512 x 64 (seg 1 / 2),
-// bws = the DF_EPI_BWD_STATS epilogue.  p as prepared by conv2d_impl (conv.hip).
+// bws = the DF_EPI_BWD_STATS epilogue.  p as filled by conv_launch (conv.hip) from the call and its conv_plan().
 int df_launch_conv_halo_x3p(const dfconv::ConvParams& p, int bn, int seg, bool bws, hipStream_t s);

@@ -2,6 +2,7 @@
 torch's current stream with raw device pointers; nothing here computes with torch ops."""
 from __future__ import annotations
 
+import ctypes
 import os
 
 from typing import Optional, Tuple
@@ -211,27 +212,35 @@ class side_stream:
         return False
 
 
-def _conv_variant(x: DfImg, y: DfImg, ks: int, stride: int, mode: int, epi: int) -> str:
-    """kernel template instance df_conv2d will launch (asks the library, so it cannot drift from the C dispatch)"""
-    rows = y.n * y.h * y.w
-    cls = mode == CONV_DGRAD and stride == 2 and ks == 3 and epi == EPI_BIAS and y.h % 2 == 0 and y.w % 2 == 0
-    v = call("df_conv2d_variant", rows // 4 if cls else rows, y.grp_size * y.h * y.w, y.c, epi)
-    if cls and (rows // 4) % (v // 1000):
-        v = call("df_conv2d_variant", rows, y.grp_size * y.h * y.w, y.c, epi)
-    bm, bn = v // 1000, v % 1000
-    wm, wn = {(128, 32): (4, 1), (256, 64): (4, 1)}.get((bm, bn), (2, 2))
-    kern = "conv_dma_kernel" if call("df_conv2d_last_dma") else "conv_kernel"
-    halo = (kern == "conv_dma_kernel" and os.environ.get("DF_CONV_HALO", "1") != "0" and ks == 3 and stride == 1 and not cls
-            and y.w % 128 == 0 and x.w == y.w and x.h == y.h and (bm, bn) in ((128, 128), (128, 64)))
-    if halo:  # haloed-A kernel (mirrors df_conv2d's dispatch)
-        return f"conv_halo_kernel<{bn},{2 if bn == 128 else 4},{4 if bn == 128 else 2}>"
-    if kern == "conv_dma_kernel":  # 8-wave forms of the two big tiles (DF_CONV_W8 bit 0 / bit 1, default both)
-        w8 = int(os.environ.get("DF_CONV_W8", "3"))
-        if (bm, bn) == (128, 128) and (w8 & 1):
-            wm, wn = 2, 4
-        elif (bm, bn) == (128, 64) and (w8 & 2):
-            wm, wn = 4, 2
-    return f"{kern}<{bm},{bn},{wm},{wn}>"
+W_F32, W_B16, W_X3, W_H2, W_WP, W_F32_H2 = range(6)                               # DF_CONV_W_*: the kind of weights a conv entry point takes
+FAM_REG, FAM_DMA, FAM_HALO, FAM_HALO_W16, FAM_HALO_X3, FAM_HALO_X3P = range(6)      # DF_CONV_FAM_*
+PLAN_XP, PLAN_X16, PLAN_BWS, PLAN_DMA, PLAN_CLS = 1, 2, 4, 8, 16                    # DF_CONV_PLAN_*: bits of the plan's flags word
+
+
+def conv_plan(x: DfImg, y: DfImg, ks: int, stride: int, mode: int, epi: int, weights: int) -> tuple:
+    """what the library's dispatch decides for the call (df_conv2d_plan; host side, nothing is launched): -> (family, BM, BN, WM, WN, SEG,
+    DB, planes, flags, stats_mul); raises where the launch would be refused"""
+    out = (ctypes.c_int32 * 10)()
+    call("df_conv2d_plan", x, y, ks, stride, mode, epi, weights, ctypes.addressof(out))
+    return tuple(out)
+
+
+def _conv_label(x: DfImg, y: DfImg, ks: int, stride: int, mode: int, epi: int, form: str, h2f: bool) -> str:
+    """profiler label of the launch conv2d made in `form`, formatted from the library's plan -- bench.py's roofline and the layer census
+    match on these strings.  The DMA-tile forms carry the fp32 instance's name, `/h2` marking fp16x2 products on the 128-row tiles; the
+    persistent plane kernels carry conv_halo_x3_kernel's"""
+    weights = {"w16": W_B16, "x3": W_X3, "h2": W_H2, "h2p": W_H2, "dgrad_bn": W_H2}.get(form, W_F32)
+    fam, bm, bn, wm, wn, seg, db, planes, flags, _ = conv_plan(x, y, ks, stride, mode, 3 if form == "dgrad_bn" else epi, weights)
+    if fam in (FAM_HALO_X3, FAM_HALO_X3P):
+        np = {3: "", 2: ",2", 1: f",1,{'true' if flags & PLAN_X16 else 'false'}"}[planes]
+        return f"conv_halo_x3_kernel<{bm},{bn},{wm},{wn},{seg},{db}{np}{',xp' if flags & PLAN_XP else ''}>"
+    if fam == FAM_HALO_W16:
+        return f"conv_halo_w16_kernel<{bn},{wm},{wn},{seg}>"
+    if fam == FAM_HALO:
+        return f"conv_halo_kernel<{bn},{wm},{wn}>"
+    if fam == FAM_DMA:
+        return f"conv_dma_kernel<{bm},{bn},{wm},{wn}>" + ("/h2" if h2f and bm == 128 else "")
+    return f"conv_kernel<{bm},{bn},{wm},{wn}>"
 
 
 # ---- max |x| bookkeeping of the fp16x2 convolution kernels (df_conv2d_h2 / df_conv2d_wgrad_h2) -------------------------------
@@ -603,6 +612,53 @@ def _wprep_planes(w_ohwi: torch.Tensor):
     return _split_h2(w_ohwi)     # (W_AMAX is None here: _split_h2 keeps the planes in _PLANE_CACHE)
 
 
+def _w_amax(w_ohwi: torch.Tensor) -> torch.Tensor:
+    """bound of the weights for the in-kernel split (DF_CONV_H2F_WP=0: no prepared planes): the trainer's, else one df_absmax pass"""
+    if W_AMAX is not None:
+        return W_AMAX
+    wa = amax_slot(w_ohwi.device)
+    call("df_absmax", img(w_ohwi.reshape(1, 1, -1, w_ohwi.shape[-1])), ptr(wa), stream())
+    return wa
+
+
+def _conv_form(x: DfImg, y: DfImg, ks: int, stride: int, mode: int, epi: int, bias, accumulate: bool, bwd_bn) -> Tuple[str, bool]:
+    """The form that takes the call, decided in ONE place (queries only: nothing is allocated or launched) -> (form, h2f):
+      dgrad_bn  the fp16x2 3x3 data gradient whose epilogue leaves the BatchNorm-backward partials (df_conv2d_h2p_dgrad_bn)
+      h2p / h2  fp32-accurate 3x3 stride-1 products from TWO fp16 planes per operand with per-tensor power-of-two scales (conv_halo_x3_kernel
+                <NP = 2>: three MFMAs per operand pair instead of six), with / without a pre-split input or output
+      x3        ... from three bf16 planes (DF_CONV_H2=0)
+      yh2       a 1x1 / stride-2 convolution with a pre-split OUTPUT: the fp32-input kernels
+      h2f       a convolution without a haloed fp16x2 form whose input carries a bound: fp16x2 on the fragments of the DMA-tile kernel
+      w16       bf16 mode: bf16 tiles in LDS (conv_halo_w16_kernel)
+      mp        the fp32 / bf16-operand MFMA kernels (conv2d makes it `amax` where the output's max |y| is wanted)
+    h2f: the fragments of a `yh2` / `h2f` call are split (x has a bound); conv2d then looks for the layer's prepared weight planes."""
+    s1 = ks == 3 and stride == 1
+    geom = (x, y, ks, stride, mode)
+    if MFMA_BF16:
+        assert x.elt != 2 and y.elt != 2
+        w16 = s1 and os.environ.get("DF_CONV_W16", "1") != "0" and call("df_conv2d_w16_ok", *geom, epi) == 1
+        return ("w16" if w16 else "mp"), False
+    pre = x.elt == 2 or y.elt == 2     # pre-split input and / or output (h2 images; their bounds ride on the descriptors)
+    if pre:
+        assert _h2_on() and not accumulate
+        assert s1 or x.elt == 0, "1x1 / stride-2 convolutions read fp32"
+    if s1 and (pre or (x.elt == 0 and y.elt == 0 and call("df_conv2d_x3_ok", *geom, epi) == 1)):
+        if not _h2_on():
+            return "x3", False
+        if (bwd_bn is not None and mode == CONV_DGRAD and y.elt == 0 and not accumulate and bias is None and y.ld == y.c
+                and os.environ.get("DF_FUSE_BN_BWD", "1") != "0" and call("df_conv2d_h2p_ok", *geom, 3) == 1):
+            return "dgrad_bn", False
+        if pre:
+            assert call("df_conv2d_h2p_ok", *geom, epi) == 1, "no pre-split tile form for this shape (ask df_conv2d_h2p_ok first)"
+        return ("h2p" if pre else "h2"), False
+    # (round 5: also the 3x3 stride-1 layers that have NO haloed fp16x2 tile form -- too few pixels: the 64 x 64 layers of a B = 1
+    # forward ran on the fp32 MFMA, 5 x 94 us of a 2.2 ms forward)
+    h2f = (h2_active() and x.elt == 0 and y.elt in (0, 2)
+           and x.c % (64 if os.environ.get("DF_CONV_H2F_C32", "1") == "0" else 32) == 0     # (32: the first encoder conv on the canvas: its bound comes from the pillar feature net's statistics)
+           and getattr(x, "_amax", None) is not None and os.environ.get("DF_CONV_H2F", "1") != "0")
+    return ("yh2" if pre else "h2f" if h2f else "mp"), h2f
+
+
 def conv2d(x: DfImg, w_ohwi: torch.Tensor, bias: Optional[torch.Tensor], y: DfImg, ks: int, stride: int = 1,
            mode: int = CONV_FWD, epi: int = EPI_BIAS, scale=None, shift=None, stats=None, accumulate: bool = False,
            amax_out: Optional[torch.Tensor] = None, bwd_bn=None):
@@ -615,24 +671,13 @@ def conv2d(x: DfImg, w_ohwi: torch.Tensor, bias: Optional[torch.Tensor], y: DfIm
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    w16 = (MFMA_BF16 and ks == 3 and stride == 1 and os.environ.get("DF_CONV_W16", "1") != "0"
-           and call("df_conv2d_w16_ok", x, y, ks, stride, mode, epi) == 1)
-    pre = x.elt == 2 or y.elt == 2     # pre-split input and / or output (h2 images; their bounds ride on the descriptors)
-    if pre:
-        assert not MFMA_BF16 and _h2_on() and not accumulate
-        if ks == 3 and stride == 1:
-            assert call("df_conv2d_h2p_ok", x, y, ks, stride, mode, epi) == 1, "no pre-split tile form for this shape (ask df_conv2d_h2p_ok first)"
-        else:
-            assert x.elt == 0, "1x1 / stride-2 convolutions read fp32"
-    x3 = (not MFMA_BF16 and not w16 and ks == 3 and stride == 1 and ((x.elt == 0 and y.elt == 0) or pre)
-          and (pre or call("df_conv2d_x3_ok", x, y, ks, stride, mode, epi) == 1))
-    h2 = x3 and _h2_on()
+    form, h2f = _conv_form(x, y, ks, stride, mode, epi, bias, accumulate, bwd_bn)
     # fp32 mode with the fp16x2 kernels on: every fp32 conv output carries its max |y| for a possible fp16x2 consumer (measured by
     # the epilogue; outputs that go through BatchNorm + GELU first get theirs from that pass instead)
     ya = None
-    if h2_active() and y.elt == 0 and epi == EPI_STATS and amax_out is not None and not w16:
+    if h2_active() and y.elt == 0 and epi == EPI_STATS and amax_out is not None:
         ya = amax_out          # max |y| of a conv output that BatchNorm + GELU follow: the bounds of the pre-split z / dy come from it
-    elif h2_active() and y.elt == 0 and epi != EPI_STATS and not w16:
+    elif h2_active() and y.elt == 0 and epi != EPI_STATS:
         ya = amax_out if amax_out is not None else amax_slot(w_ohwi.device)
         y._amax = ya
         src = getattr(y, "_src", None)      # the descriptor covers a whole tensor: descriptors made of it later inherit the bound
@@ -640,116 +685,55 @@ def conv2d(x: DfImg, w_ohwi: torch.Tensor, bias: Optional[torch.Tensor], y: DfIm
             src._df_amax = (ya, ver(src))
     if ya is None and getattr(y, "_src", None) is not None:
         wrote(y._src)          # (an unmeasured write into a tensor that carried a bound)
-    # (round 5: also the 3x3 stride-1 layers that have NO haloed fp16x2 tile form -- too few pixels: the 64 x 64 layers of a B = 1
-    # forward ran on the fp32 MFMA, 5 x 94 us of a 2.2 ms forward)
-    h2f = (h2_active() and not x3 and not w16 and x.elt == 0 and y.elt in (0, 2) and (ks == 1 or stride == 2 or (ks == 3 and stride == 1))
-           and x.c % (64 if os.environ.get("DF_CONV_H2F_C32", "1") == "0" else 32) == 0     # (32: the first encoder conv on the canvas: its bound comes from the pillar feature net's statistics)
-           and getattr(x, "_amax", None) is not None and os.environ.get("DF_CONV_H2F", "1") != "0")
-    fused_bn = False
-    if (h2 and bwd_bn is not None and mode == CONV_DGRAD and y.elt == 0 and not accumulate and bias is None and y.ld == y.c
-            and os.environ.get("DF_FUSE_BN_BWD", "1") != "0" and call("df_conv2d_h2p_ok", x, y, ks, stride, mode, 3) == 1):
+    if form == "mp" and ya is not None:
+        form = "amax"          # the same kernels, measuring
+    # what the form reads besides x and y: the weights in its layout (they change every optimizer step: split / cast once per call unless
+    # the step's WeightPrep holds them), bounds
+    dev, acc = w_ohwi.device, int(accumulate)
+    tail = (ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift), ptr(stats))
+    if form in ("dgrad_bn", "h2p", "h2"):
         w2, wa = _split_h2(w_ohwi)
-        yp, ssp, part = bwd_bn
-        call("df_conv2d_h2p_dgrad_bn", x, ptr(w2), ptr(amax_of(x, w_ohwi.device)), ptr(wa), y, ptr(yp), ptr(ssp), ptr(part), ptr(ya), stream())
-        fused_bn = True
-    elif h2 and pre:
-        w2, wa = _split_h2(w_ohwi)
-        call("df_conv2d_h2p", x, ptr(w2), ptr(amax_of(x, w_ohwi.device)), ptr(wa), ptr(bias), y, ptr(y._amax) if y.elt == 2 else None,
-             ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift), ptr(stats), 0, ptr(ya), stream())
-    elif pre:      # 1x1 (or stride-2) convolution with a pre-split OUTPUT: the fp32-input kernels, fp16x2 on the fragments when x has a bound
-        wa = None
+    elif form in ("yh2", "h2f"):
         wp = _wprep_planes(w_ohwi) if h2f else None
-        if h2f and wp is None:      # (the in-kernel weight split, DF_CONV_H2F_WP=0: needs the weights' bound)
-            wa = W_AMAX
-            if wa is None:
-                wa = amax_slot(w_ohwi.device)
-                call("df_absmax", img(w_ohwi.reshape(1, 1, -1, w_ohwi.shape[-1])), ptr(wa), stream())
-        if wp is not None:      # the step's WeightPrep holds this layer's planes: no weight split in the kernel (conv_dma_kernel<.., H2, BP>)
-            call("df_conv2d_h2f_wp", x, ptr(w_ohwi), ptr(wp[0]), ptr(x._amax), ptr(wp[1]), ptr(bias), y, ptr(y._amax), ks, stride, ks // 2, mode,
-                 epi, ptr(scale), ptr(shift), ptr(stats), 0, None, stream())
-        else:
-            call("df_conv2d_yh2", x, ptr(w_ohwi), ptr(x._amax) if h2f else None, ptr(wa), ptr(bias), y, ptr(y._amax), ks, stride, ks // 2, mode, epi,
-                 ptr(scale), ptr(shift), ptr(stats), 0, stream())
-    elif h2:
-        # fp32-accurate product from TWO fp16 planes per operand with per-tensor power-of-two scales (conv_halo_x3_kernel<NP = 2>:
-        # three MFMAs per operand pair instead of six)
-        w2, wa = _split_h2(w_ohwi)
-        call("df_conv2d_h2", x, ptr(w2), ptr(amax_of(x, w_ohwi.device)), ptr(wa), ptr(bias), y, ks, stride, ks // 2, mode, epi,
-             ptr(scale), ptr(shift), ptr(stats), int(accumulate), ptr(ya), stream())
-    elif h2f:
-        # 1x1 / stride-2 convolutions whose input already carries a bound: fp16x2 on the fragments of the DMA-tile kernel
-        wp = _wprep_planes(w_ohwi)
-        wa = W_AMAX
-        if wp is None and wa is None:      # (the in-kernel weight split, DF_CONV_H2F_WP=0: needs the weights' bound)
-            wa = amax_slot(w_ohwi.device)
-            call("df_absmax", img(w_ohwi.reshape(1, 1, -1, w_ohwi.shape[-1])), ptr(wa), stream())
-        if wp is not None:
-            call("df_conv2d_h2f_wp", x, ptr(w_ohwi), ptr(wp[0]), ptr(x._amax), ptr(wp[1]), ptr(bias), y, None, ks, stride, ks // 2, mode, epi,
-                 ptr(scale), ptr(shift), ptr(stats), int(accumulate), ptr(ya), stream())
-        else:
-            call("df_conv2d_h2f", x, ptr(w_ohwi), ptr(x._amax), ptr(wa), ptr(bias), y, ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift),
-                 ptr(stats), int(accumulate), ptr(ya), stream())
-    elif ya is not None and not x3:
-        call("df_conv2d_amax", x, ptr(w_ohwi), ptr(bias), y, ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift), ptr(stats),
-             int(accumulate), ptr(ya), stream())
-    elif x3:
-        # fp32-accurate product from three bf16 planes per operand (conv_halo_x3_kernel): the weights are split once per call
-        # (they change every optimizer step), the activations in the kernel's staging
-        w3 = torch.empty(3 * w_ohwi.numel(), dtype=torch.bfloat16, device=w_ohwi.device)
-        call("df_split_bf16x3", ptr(w_ohwi), ptr(w3), w_ohwi.numel(), stream())
-        call("df_conv2d_x3", x, ptr(w3), ptr(bias), y, ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift), ptr(stats),
-             int(accumulate), stream())
-    elif w16:
-        # bf16 tiles in LDS (conv_halo_w16_kernel): the weights are cast once per call (they change every optimizer step and
-        # each conv uses them once per direction), the activations stay fp32 in memory
-        wb = torch.empty(w_ohwi.numel(), dtype=torch.bfloat16, device=w_ohwi.device)
-        call("df_cast_bf16", ptr(w_ohwi), ptr(wb), w_ohwi.numel() // x.c, x.c, x.c, x.c, stream())
-        call("df_conv2d_w16", x, ptr(wb), ptr(bias), y, ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift), ptr(stats),
-             int(accumulate), stream())
+        if wp is not None:      # this layer's planes: no weight split in the kernel (conv_dma_kernel<.., H2, BP>)
+            form = "h2f_wp"
+        wa = _w_amax(w_ohwi) if (h2f and wp is None) else None
+    elif form == "x3":
+        wx = torch.empty(3 * w_ohwi.numel(), dtype=torch.bfloat16, device=dev)
+        call("df_split_bf16x3", ptr(w_ohwi), ptr(wx), w_ohwi.numel(), stream())
+    elif form == "w16":         # (the activations stay fp32 in memory unless the descriptors say bf16)
+        wx = torch.empty(w_ohwi.numel(), dtype=torch.bfloat16, device=dev)
+        call("df_cast_bf16", ptr(w_ohwi), ptr(wx), w_ohwi.numel() // x.c, x.c, x.c, x.c, stream())
+    if form == "dgrad_bn":
+        call("df_conv2d_h2p_dgrad_bn", x, ptr(w2), ptr(amax_of(x, dev)), ptr(wa), y, *map(ptr, bwd_bn), ptr(ya), stream())
+    elif form == "h2p":
+        call("df_conv2d_h2p", x, ptr(w2), ptr(amax_of(x, dev)), ptr(wa), ptr(bias), y, ptr(y._amax) if y.elt == 2 else None, *tail, 0, ptr(ya), stream())
+    elif form == "h2":
+        call("df_conv2d_h2", x, ptr(w2), ptr(amax_of(x, dev)), ptr(wa), ptr(bias), y, *tail, acc, ptr(ya), stream())
+    elif form == "h2f_wp":      # (y pre-split: its bound, no measurement -- ya is None then)
+        call("df_conv2d_h2f_wp", x, ptr(w_ohwi), ptr(wp[0]), ptr(x._amax), ptr(wp[1]), ptr(bias), y, ptr(y._amax) if y.elt == 2 else None, *tail, acc, ptr(ya), stream())
+    elif form == "yh2":
+        call("df_conv2d_yh2", x, ptr(w_ohwi), ptr(x._amax) if h2f else None, ptr(wa), ptr(bias), y, ptr(y._amax), *tail, 0, stream())
+    elif form == "h2f":
+        call("df_conv2d_h2f", x, ptr(w_ohwi), ptr(x._amax), ptr(wa), ptr(bias), y, *tail, acc, ptr(ya), stream())
+    elif form == "amax":
+        call("df_conv2d_amax", x, ptr(w_ohwi), ptr(bias), y, *tail, acc, ptr(ya), stream())
+    elif form == "x3":
+        call("df_conv2d_x3", x, ptr(wx), ptr(bias), y, *tail, acc, stream())
+    elif form == "w16":
+        call("df_conv2d_w16", x, ptr(wx), ptr(bias), y, *tail, acc, stream())
     else:
-        call("df_conv2d_mp", x, ptr(w_ohwi), ptr(bias), y, ks, stride, ks // 2, mode, epi, ptr(scale), ptr(shift), ptr(stats),
-             int(accumulate), int(MFMA_BF16), stream())
+        call("df_conv2d_mp", x, ptr(w_ohwi), ptr(bias), y, *tail, acc, int(MFMA_BF16), stream())
     if prof is not None:
         e1.record()
         small = y if mode == CONV_FWD else x  # the conv-output-sized grid
         flops = 2.0 * small.n * small.h * small.w * ks * ks * x.c * y.c
         tag = f"{'fwd' if mode == CONV_FWD else 'dgrad'} {ks}x{ks} s{stride} {x.c}->{y.c} @{small.h}x{small.w} x{small.n} {'fbh'[x.elt]}{'fbh'[y.elt]}"
-        name = _conv_variant(x, y, ks, stride, mode, epi) + ("/h2" if (h2f and "conv_dma_kernel<128," in _conv_variant(x, y, ks, stride, mode, epi)) else "")
-        if x3:   # mirrors conv2d_impl's dispatch of the bf16x3 forms (BM, BN, WM, WN, SEG, DB)
-            bn = 128 if y.c % 128 == 0 else 64
-            seg = 1 if y.w % 128 == 0 else 2
-            m_rows, rpg = y.n * y.h * y.w, y.grp_size * y.h * y.w
-            bm = 256 if (bn == 64 and seg == 1 and y.w % 256 == 0 and m_rows % 256 == 0 and (epi != EPI_STATS or rpg % 256 == 0)
-                         and os.environ.get("DF_CONV_X3_BM256", "1") != "0") else 128
-            name = f"conv_halo_x3_kernel<{bm},{bn},{2 if bn == 128 else 4},{4 if bn == 128 else 2},{seg},{4 if (bn == 128 or bm == 256) else 8}{',2' if h2 else ''}>"
-            seg2 = 1 if y.w % 256 == 0 else 2 if y.w == 128 else 4 if y.w == 64 else 0
-            if (h2 and bn == 128 and seg2 and y.h % seg2 == 0 and m_rows % 256 == 0 and (epi != EPI_STATS or rpg % 256 == 0)
-                    and m_rows // 256 * (y.c // 128) >= 512 and os.environ.get("DF_CONV_H2_BM256", "1") != "0"):
-                name = f"conv_halo_x3_kernel<256,128,4,2,{seg2},4,2>"     # 64 x 64 wave tiles
-            seg64 = 1 if y.w % 512 == 0 else 2 if y.w == 256 else 0
-            if (h2 and bn == 64 and seg64 and y.h % seg64 == 0 and m_rows % 512 == 0 and (epi != EPI_STATS or rpg % 512 == 0)
-                    and m_rows // 512 >= 512 and os.environ.get("DF_CONV_H2_BM256", "1") != "0"):
-                name = f"conv_halo_x3_kernel<512,64,8,1,{seg64},3,2>"
-            if x.elt == 2:
-                name = name[:-1] + ",xp>"        # pre-split input: halo by LDS-DMA (template argument XP)
-        if w16:
-            bn = 128 if y.c % 128 == 0 else 64
-            name = f"conv_halo_w16_kernel<{bn},{2 if bn == 128 else 4},{4 if bn == 128 else 2},{1 if y.w % 128 == 0 else 2}>"
-            m_rows, rpg = y.n * y.h * y.w, y.grp_size * y.h * y.w
-            wide = os.environ.get("DF_W16_WIDE", "0") == "1" and m_rows > 8192
-            seg2 = 1 if y.w % 256 == 0 else 2 if y.w == 128 else 4 if y.w == 64 else 0
-            seg64 = 1 if y.w % 512 == 0 else 2 if y.w == 256 else 0
-            if (wide and bn == 128 and seg2 and y.h % seg2 == 0 and m_rows % 256 == 0 and (epi != EPI_STATS or rpg % 256 == 0)
-                    and m_rows // 256 * (y.c // 128) >= 512):
-                name = f"conv_halo_x3_kernel<256,128,4,2,{seg2},8,1,{'true' if x.elt else 'false'}>"     # one bf16 plane, 64 x 64 wave tiles
-            elif (wide and bn == 64 and seg64 and y.h % seg64 == 0 and m_rows % 512 == 0 and (epi != EPI_STATS or rpg % 512 == 0)
-                    and m_rows // 512 >= 512):
-                name = f"conv_halo_x3_kernel<512,64,8,1,{seg64},8,1,{'true' if x.elt else 'false'}>"
         # operand bytes of the call (input + output images once, the weights once): what an HBM-bound small-K layer is priced against
         esz = lambda d: (4, 2, 4)[d.elt]
         obytes = float(x.n * x.h * x.w * x.c * esz(x) + y.n * y.h * y.w * y.c * esz(y) * (2 if accumulate else 1) + w_ohwi.numel() * 4)
-        prof.records.append((name + ("/bf16" if MFMA_BF16 else ""), flops, e0, e1, tag, obytes))
-    return fused_bn
+        prof.records.append((_conv_label(x, y, ks, stride, mode, epi, form, h2f) + ("/bf16" if MFMA_BF16 else ""), flops, e0, e1, tag, obytes))
+    return form == "dgrad_bn"
 
 
 def conv_tile_m(rows_per_group: int, cout: int) -> int:

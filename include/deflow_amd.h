@@ -261,6 +261,32 @@ int df_conv2d_w16_ok(df_img x, df_img y, int ksize, int stride, int mode, int ep
 /* tile variant the launcher picks, as BM * 1000 + BN (for profiling tools) */
 int df_conv2d_variant(int64_t rows, int64_t rows_per_stat_group, int cout, int epi);
 int df_conv2d_last_dma(void); /* 1 if the previous df_conv2d call launched the LDS-DMA kernel (profiling tools) */
+/* What the forward / data-gradient dispatch decides for a call, from its descriptors and the kind of its weights alone (no data
+ * pointer is read, nothing is launched; the _ok queries above answer from the same plan).  weights: what the entry point hands over --
+ * F32 df_conv2d / _mp / _amax / _yh2 without bounds, B16 df_conv2d_w16, X3 df_conv2d_x3, H2 df_conv2d_h2 / _h2p / _h2p_dgrad_bn, WP
+ * df_conv2d_h2f_wp, F32_H2 df_conv2d_h2f / _yh2 with both bounds.  out [DF_CONV_PLAN_LEN]: kernel family (DF_CONV_FAM_*), BM, BN, WM, WN
+ * (tile and wave grid), SEG (image rows per tile of the haloed 16-bit forms), DB (weight ring depth of the plane forms), planes per
+ * operand (0: fp32 tiles), flags (DF_CONV_PLAN_*), statistics-table rows per tile.  Returns DF_OK, or the code the launch would refuse
+ * with (out: family -1). */
+#define DF_CONV_W_F32 0     /* fp32 [Cout, k*k, Cin] */
+#define DF_CONV_W_B16 1     /* bf16 tiles (df_cast_bf16) */
+#define DF_CONV_W_X3 2      /* three bf16 planes (df_split_bf16x3) */
+#define DF_CONV_W_H2 3      /* two fp16 planes (df_split_h2) */
+#define DF_CONV_W_WP 4      /* fp32 + pre-split planes for the DMA-tile kernel */
+#define DF_CONV_W_F32_H2 5  /* fp32, split on the fragments (bounds of max |x| and max |w| given) */
+#define DF_CONV_FAM_REG 0       /* conv_kernel: register-staged tiles */
+#define DF_CONV_FAM_DMA 1       /* conv_dma_kernel */
+#define DF_CONV_FAM_HALO 2      /* conv_halo_kernel: haloed fp32 tiles */
+#define DF_CONV_FAM_HALO_W16 3  /* conv_halo_w16_kernel: haloed bf16 tiles */
+#define DF_CONV_FAM_HALO_X3 4   /* conv_halo_x3_kernel: haloed planes */
+#define DF_CONV_FAM_HALO_X3P 5  /* conv_halo_x3p_kernel: haloed pre-split planes, persistent */
+#define DF_CONV_PLAN_XP 1    /* pre-split input */
+#define DF_CONV_PLAN_X16 2   /* bf16 input */
+#define DF_CONV_PLAN_BWS 4   /* DF_EPI_BWD_STATS epilogue */
+#define DF_CONV_PLAN_DMA 8   /* operands by LDS-DMA (32-bit buffer offsets) */
+#define DF_CONV_PLAN_CLS 16  /* stride-2 data gradient tiled per output-parity class */
+#define DF_CONV_PLAN_LEN 10
+int df_conv2d_plan(df_img x, df_img y, int ksize, int stride, int mode, int epi, int weights, int32_t* out);
 /* BatchNorm2d training statistics from the partials. groups = stat groups (the shared encoder is
  * applied to pc0 then pc1: two calls => two groups, running stats updated in call order).
  * bn_ss [groups,4,C] = scale, shift, mean, invstd.  Optional two-stage reduction for layers with many tiles:

@@ -281,12 +281,12 @@ def _variant(rows, rpg, cout, epi):
 
 
 def class_mode_asked(p: Prob) -> bool:
-    """conv2d_impl's `cls`: a 3x3 stride-2 data gradient with the bias epilogue onto an image with even sides"""
+    """conv_plan's `cls` (csrc/conv.hip): a 3x3 stride-2 data gradient with the bias epilogue onto an image with even sides"""
     return p.mode == "dgrad" and p.stride == 2 and p.k == 3 and p.epi == "bias" and p.h % 2 == 0 and p.w % 2 == 0
 
 
 def tiling(p: Prob) -> dict:
-    """conv2d_impl's tile choice restated (the variant itself is asked from the library): -> var, bm, bn, cls (class mode taken),
+    """conv_plan's tile choice restated (the variant itself is asked from the library): -> var, bm, bn, cls (class mode taken),
     tiles [(class or None, m0, m_end)] in launch order of the row tiles"""
     _, oh, ow, C = p.out_shape
     M = p.M

@@ -2,9 +2,12 @@
 nothing).
 
   * tile selection: df_conv2d_variant / df_conv2d_tile_m give every problem of tests/helpers/conv_cases.py the tile its case was built for,
-    with the stated tile count and last-tile size; the class-mode condition of conv2d_impl, restated, holds for `s2_class` only;
+    with the stated tile count and last-tile size; the class-mode condition of conv_plan(), restated, holds for `s2_class` only;
   * form queries: df_conv2d_x3_ok / df_conv2d_w16_ok say 1 for the halo_* cases and 0 for tail*; the weight-gradient _ok functions answer as
     the forms table says; the *_splits functions return the recorded counts;
+  * the forward / data-gradient host layer: every launch entry point's refusal code for one fault in a complete call; the _ok queries
+    against the case tables; df_conv2d_plan (family, tile, flags, statistics rows) pinned on the case tables and the benchmark's layer
+    shapes, an _ok query saying 1 exactly where the plan is no refusal; the profiler labels ops._conv_label formats from the plan;
   * chunks and splits: the restated wg_chunk / chunks_per_split / c_begin / c_end show which split starts mid-row, which crosses an image,
     which has fewer chunks than the ring is deep and which is empty;
   * the restatements (rows -> tiles; chunks -> splits -> reduce) equal ref64 with no fault, and every fault injected into them (never into
@@ -149,6 +152,228 @@ def test_forward_form_queries():
             assert ok == (0, 0), (p.pid, ok)
         assert ("x3" in CC.forms(p.case)) <= (ok == (1, 1)), p.pid
     assert CC.refused(_by("tail64", acc=True)[0], "yh2") == CC.E_ARG and CC.refused(_by("tail64", acc=False)[0], "yh2") is None
+
+
+# ---- the forward / data-gradient host layer: refusals, queries, the plan, the profiler labels ------------------------------------------
+E_OK = 0
+W_F32, W_B16, W_X3, W_H2, W_WP, W_F32_H2 = range(6)                                 # DF_CONV_W_*
+FAM_REG, FAM_DMA, FAM_HALO, FAM_HALO_W16, FAM_HALO_X3, FAM_HALO_X3P = range(6)        # DF_CONV_FAM_*
+XP, X16, BWS, DMA, CLS = 1, 2, 4, 8, 16                                              # DF_CONV_PLAN_*
+
+
+def _with(d, **kw):
+    """a copy of descriptor d with fields replaced"""
+    from deflow_amd._lib import DfImg
+    f = {k: getattr(d, k) for k, _ in DfImg._fields_}
+    f.update(kw)
+    return DfImg(*(f[k] for k, _ in DfImg._fields_))
+
+
+def _stage(name, k, elt=0):
+    """a 3x3 stride-1 layer's tensor at encoder stage k of a tests/helpers/rect_cases.py grid, as rect_cases.selection builds it (2B images, one
+    group, no data)"""
+    import rect_cases as RC
+    c = RC.case(name)
+    n, (h, w), C = 2 * c.B, c.stage_hw(k), RC.STAGE_C[k - 1]
+    return _with(_desc((n, h, w, C), CC.layout((n, h, w, C), 0, False, "x")), ptr=_pair(1)[0].ptr, elt=elt)
+
+
+def _plan(x, y, k, stride, mode, epi, weights):
+    """-> (code, the plan's ten integers)"""
+    import ctypes
+    from deflow_amd._lib import load
+    out = (ctypes.c_int32 * 10)()
+    rc = load().df_conv2d_plan(x, y, k, stride, mode, epi, weights, ctypes.addressof(out))
+    return rc, tuple(out)
+
+
+def _forward_entries(lib, a):
+    """name -> call(f) of the twelve forward / data-gradient launch entry points; f: x, y, t descriptors, w (the weights the entry point
+    reads), w2 (df_conv2d_h2f_wp's planes), yb (y_bound), geometry, epilogue; every other pointer is the aligned address a"""
+    import ctypes
+    P = ctypes.c_void_p
+    geo = lambda f: (f["ks"], f["stride"], f["pad"], f["mode"], f["epi"], P(a), P(a), P(f["stats"]), f["acc"])
+    return {
+        "df_conv2d": lambda f: lib.df_conv2d(f["x"], P(f["w"]), P(a), f["y"], *geo(f), P(0)),
+        "df_conv2d_mp": lambda f: lib.df_conv2d_mp(f["x"], P(f["w"]), P(a), f["y"], *geo(f), 0, P(0)),
+        "df_conv2d_amax": lambda f: lib.df_conv2d_amax(f["x"], P(f["w"]), P(a), f["y"], *geo(f), P(a), P(0)),
+        "df_conv2d_w16": lambda f: lib.df_conv2d_w16(f["x"], P(f["w"]), P(a), f["y"], *geo(f), P(0)),
+        "df_conv2d_x3": lambda f: lib.df_conv2d_x3(f["x"], P(f["w"]), P(a), f["y"], *geo(f), P(0)),
+        "df_conv2d_h2": lambda f: lib.df_conv2d_h2(f["x"], P(f["w"]), P(a), P(a), P(a), f["y"], *geo(f), P(a), P(0)),
+        "df_conv2d_h2p": lambda f: lib.df_conv2d_h2p(f["x"], P(f["w"]), P(a), P(a), P(a), f["y"], P(f["yb"]), *geo(f), P(a), P(0)),
+        "df_conv2d_h2p_dgrad_bn": lambda f: lib.df_conv2d_h2p_dgrad_bn(f["x"], P(f["w"]), P(a), P(a), f["y"], P(a), P(a), P(a), P(a), P(0)),
+        "df_conv2d_h2f": lambda f: lib.df_conv2d_h2f(f["x"], P(f["w"]), P(a), P(a), P(a), f["y"], *geo(f), P(a), P(0)),
+        "df_conv2d_h2f_wp": lambda f: lib.df_conv2d_h2f_wp(f["x"], P(f["w"]), P(f["w2"]), P(a), P(a), P(a), f["y"], P(f["yb"]), *geo(f), P(a), P(0)),
+        "df_conv2d_h2f_wp_up": lambda f: lib.df_conv2d_h2f_wp_up(f["x"], P(f["w"]), P(f["w2"]), P(a), P(a), P(a), f["y"], P(f["yb"]), f["t"], 0, P(0)),
+        "df_conv2d_yh2": lambda f: lib.df_conv2d_yh2(f["x"], P(f["w"]), P(a), P(a), P(a), f["y"], P(f["yb"]), *geo(f), P(0)),
+    }
+
+
+FIXED_GEOMETRY = ("df_conv2d_h2p_dgrad_bn", "df_conv2d_h2f_wp_up")         # no ksize / stride / pad / mode / epi / accumulate arguments
+NEEDS_H2_OUTPUT = ("df_conv2d_yh2", "df_conv2d_h2f_wp_up")                 # refuse y.elt != 2 themselves
+READS_H2 = ("df_conv2d_h2", "df_conv2d_h2p", "df_conv2d_h2p_dgrad_bn")      # accept an h2 input
+
+
+@pytest.mark.parametrize("case", ["tail64", "halo_thin"])
+def test_forward_entry_points_refuse_before_launching(case):
+    """per launch entry point and ONE fault in an otherwise complete call, the status the entry point documents; every call returns before
+    a launch.  The faults: a null / misaligned weight pointer, an h2 image where fp32 is read, an h2 output with accumulate or without its
+    bound, x.n != y.n, a bad ksize / stride / pad, DF_EPI_STATS without its buffer or with rows per group that are no tile multiple,
+    DF_EPI_BWD_STATS on a forward call, an upsample source of the wrong size"""
+    from deflow_amd._lib import load
+    p = CC.PROBS[case][0]
+    x, y = _descs(p)
+    a = x.ptr
+    entries = _forward_entries(load(), a)
+    for name, fn in entries.items():
+        base = dict(x=x, y=_with(y, elt=2) if name in NEEDS_H2_OUTPUT else y, t=_with(y, h=2, w=4), w=a, w2=a, yb=a, ks=p.k, stride=p.stride,
+                    pad=p.k // 2, mode=CC.FWD, epi=CC.EPI[p.epi], stats=a, acc=0)
+        if name == "df_conv2d_h2f_wp_up":
+            base.update(ks=1, pad=0)
+        faults = [("w NULL", dict(w=0), E_ALIGN), ("w misaligned", dict(w=a + 4), E_ALIGN),
+                  ("y h2 without its bound", dict(y=_with(y, elt=2), yb=0), CC.E_ARG),
+                  ("x.n != y.n", dict(y=_with(base["y"], n=2 * y.n)), CC.E_SHAPE)]
+        if name not in READS_H2:
+            faults.append(("x h2", dict(x=_with(x, elt=2)), CC.E_ARG if name == "df_conv2d_w16" else E_ALIGN))
+        if name in ("df_conv2d_h2f_wp", "df_conv2d_h2f_wp_up"):
+            faults += [("w2 NULL", dict(w2=0), CC.E_ARG), ("w2 misaligned", dict(w2=a + 4), CC.E_ARG)]
+        if name == "df_conv2d_h2f_wp_up":
+            faults.append(("t of the wrong size", {}, CC.E_SHAPE))             # (2 t.h != y.h: the only fault of the base call)
+        if name not in FIXED_GEOMETRY:
+            bwd_code = E_ALIGN if name == "df_conv2d_h2p" else CC.E_ARG      # (df_conv2d_h2p refuses the epilogue in its own first check)
+            faults += [("y h2 with accumulate", dict(y=_with(y, elt=2), acc=1), CC.E_ARG),
+                       ("ksize 5", dict(ks=5, pad=2), CC.E_SHAPE), ("stride 3", dict(stride=3), CC.E_SHAPE), ("pad 0", dict(pad=0), CC.E_SHAPE),
+                       ("stats without a buffer", dict(epi=CC.EPI["stats"], stats=0), CC.E_ARG),
+                       ("bwd_stats on a forward call", dict(epi=3), bwd_code)]
+            if case == "tail64":
+                assert ((p.grp or p.n) * p.ho * p.wo) % 64 != 0
+                faults.append(("stats rows per group no tile multiple", dict(epi=CC.EPI["stats"]), CC.E_SHAPE))
+        for what, kw, code in faults:
+            got = fn({**base, **kw})
+            print(f"[conv refusals] {case} {name}: {what} -> {got}")
+            assert got == code, (case, name, what, got)
+
+
+def test_forward_query_consistency():
+    """df_conv2d_variant and df_conv2d_tile_m agree; the three _ok queries answer as the case tables say -- on every problem of conv_cases.py
+    and every row of rect_cases.py"""
+    import rect_cases as RC
+    from deflow_amd._lib import call
+    for p in ALL:
+        x, y = _descs(p)
+        mode, epi = CC.FWD if p.mode == "fwd" else CC.DGRAD, CC.EPI[p.epi]
+        rpg = (p.grp or p.n) * p.out_shape[1] * p.out_shape[2]
+        assert call("df_conv2d_tile_m", rpg, p.out_shape[3]) == call("df_conv2d_variant", rpg, rpg, p.out_shape[3], CC.EPI["stats"]) // 1000, p.pid
+        ok = tuple(call(q, x, y, p.k, p.stride, mode, epi) for q in ("df_conv2d_x3_ok", "df_conv2d_h2p_ok", "df_conv2d_w16_ok"))
+        assert ok == ((1, 1, 1) if p.case.startswith("halo") else (0, 0, 0)), (p.pid, ok)
+        assert ("x3" in CC.forms(p.case)) == ("h2" in CC.forms(p.case)) == ("w16" in CC.forms(p.case)) == (ok == (1, 1, 1)), p.pid
+        assert call("df_conv2d_h2p_ok", _with(x, elt=2), y, p.k, p.stride, mode, epi) == 0, p.pid     # (too few tiles for the pre-split forms)
+    for (name, k), want in RC.SELECTION.items():
+        c = RC.case(name)
+        assert RC.selection(c, k) == want, (name, k)
+        assert want[0] == call("df_conv2d_variant", c.rows_pg(k), c.rows_pg(k), RC.STAGE_C[k - 1], CC.EPI["stats"]) // 1000
+
+
+def test_forward_plan():
+    """df_conv2d_plan, the one dispatch behind the launches, the queries and the profiler labels, pinned on the case tables"""
+    import rect_cases as RC
+    from deflow_amd._lib import call
+    queries = (("df_conv2d_x3_ok", W_X3), ("df_conv2d_h2p_ok", W_H2), ("df_conv2d_w16_ok", W_B16))
+
+    def check_queries(x, y, k, stride, mode, epi, tag):
+        for q, kind in queries:
+            rc, pl = _plan(x, y, k, stride, mode, epi, kind)
+            assert (call(q, x, y, k, stride, mode, epi) == 1) == (rc == E_OK) == (pl[0] >= 0), (tag, q)
+            assert rc in (E_OK, CC.E_SHAPE, CC.E_ARG, E_ALIGN)
+
+    for p in ALL:
+        x, y = _descs(p)
+        mode, epi = CC.FWD if p.mode == "fwd" else CC.DGRAD, CC.EPI[p.epi]
+        rc, pl = _plan(x, y, p.k, p.stride, mode, epi, W_F32)
+        tl = CC.tiling(p)
+        halo = p.case.startswith("halo") and p.w % 128 == 0                 # (the fp32 tiles have no row-pair form for W == 64)
+        assert rc == E_OK and (pl[0] == FAM_HALO) == halo and bool(pl[8] & CLS) == tl["cls"], (p.pid, rc, pl)
+        if pl[0] != FAM_HALO:
+            assert pl[0] == (FAM_DMA if pl[8] & DMA else FAM_REG) and pl[1] * 1000 + pl[2] == tl["var"] and pl[9] == 1, (p.pid, pl)
+        assert bool(pl[8] & DMA) == (not (p.mode == "dgrad" and p.stride == 2 and not tl["cls"])), p.pid       # the generic stride-2 data gradient: registers
+        check_queries(x, y, p.k, p.stride, mode, epi, p.pid)
+        for xe, ye in ((2, 0), (0, 2), (1, 1)):
+            check_queries(_with(x, elt=xe), _with(y, elt=ye), p.k, p.stride, mode, epi, p.pid)
+    assert all(_plan(*_descs(p), p.k, p.stride, CC.DGRAD, 0, W_F32)[1][8] & CLS for p in CC.PROBS["s2_class"])
+    assert not any(_plan(*_descs(p), p.k, p.stride, CC.DGRAD, 0, W_F32)[1][8] & CLS for p in _by("s2_odd", mode="dgrad"))
+    # the benchmark's layer shapes: [320,512] at B = 16 reaches the persistent plane form at 512 x 64 (stage 1: two rows of W = 256), 256 x 128
+    # (stage 2: two rows of W = 128; stage 3: four of W = 64), the statistics table still in 128-row tiles
+    want = {1: (FAM_HALO_X3P, 512, 64, 8, 1, 2, 3, 2, XP | DMA, 4), 2: (FAM_HALO_X3P, 256, 128, 4, 2, 2, 4, 2, XP | DMA, 2),
+            3: (FAM_HALO_X3P, 256, 128, 4, 2, 4, 4, 2, XP | DMA, 2)}
+    for k in (1, 2, 3):
+        xh, y = _stage("320x512", k, 2), _stage("320x512", k)
+        for mode, epi in ((CC.FWD, 0), (CC.FWD, 1), (CC.DGRAD, 0)):
+            assert _plan(xh, y, 3, 1, mode, epi, W_H2) == (E_OK, want[k]), (k, mode, epi)
+            assert _plan(xh, _with(y, elt=2), 3, 1, mode, epi, W_H2) == (E_OK, want[k]), (k, mode, epi)
+            check_queries(xh, y, 3, 1, mode, epi, k)
+        assert _plan(xh, y, 3, 1, CC.DGRAD, 3, W_H2) == (E_OK, want[k][:8] + (XP | DMA | BWS,) + want[k][9:])
+        rc, pl = _plan(y, y, 3, 1, CC.FWD, 1, W_H2)                      # fp32 input: the same tile on the register-staged halo
+        assert rc == E_OK and pl == (FAM_HALO_X3,) + want[k][1:8] + (DMA,) + want[k][9:]
+        assert _plan(xh, y, 3, 1, CC.FWD, 0, W_X3)[0] == _plan(xh, y, 3, 1, CC.FWD, 0, W_F32)[0] == E_ALIGN        # (only the fp16x2 planes read an h2 image)
+    for (name, k) in RC.SELECTION:
+        for mode, epi in ((CC.FWD, 1), (CC.DGRAD, 0)):
+            for xe, ye in ((0, 0), (2, 0), (1, 1)):
+                check_queries(_stage(name, k, xe), _stage(name, k, ye), 3, 1, mode, epi, (name, k))
+    for k in (1, 2, 3):                                                 # [64,96]: W = 48 / 24 / 12 reaches none of the haloed forms
+        x = _stage("64x96", k)
+        assert _plan(x, x, 3, 1, CC.FWD, 1, W_F32)[1][0] == FAM_DMA
+        assert [_plan(x, x, 3, 1, CC.FWD, 1, kind)[0] for kind in (W_X3, W_H2, W_B16)] == [CC.E_SHAPE] * 3
+    # a tensor past what a buffer descriptor reaches falls to the register-staged family; a bf16 output needs the DMA kernels' epilogue
+    x, y = _pair(1)
+    far = _with(x, img_stride=_edge_stride(128, 4, 4))
+    assert _plan(x, y, 3, 1, CC.FWD, 0, W_F32)[1][0] == FAM_DMA
+    assert _plan(far, y, 3, 1, CC.FWD, 0, W_F32) == (E_OK, (FAM_REG, 64, 64, 2, 2, 1, 0, 0, 0, 1))
+    assert _plan(far, _with(y, elt=1), 3, 1, CC.FWD, 0, W_F32)[0] == CC.E_SHAPE and _plan(x, _with(y, elt=1), 3, 1, CC.FWD, 0, W_F32)[0] == E_OK
+    assert _plan(x, y, 3, 1, CC.FWD, 0, 6)[0] == CC.E_ARG
+
+
+# (descriptors, form, h2f) -> the label; the strings are the parent's ops.conv2d, derived by hand
+LABELS = [
+    (("stage", "320x512", 2, 0, 0), CC.FWD, 1, "h2", False, "conv_halo_x3_kernel<256,128,4,2,2,4,2>"),
+    (("stage", "320x512", 2, 2, 0), CC.FWD, 1, "h2p", False, "conv_halo_x3_kernel<256,128,4,2,2,4,2,xp>"),
+    (("stage", "320x512", 3, 2, 2), CC.DGRAD, 0, "h2p", False, "conv_halo_x3_kernel<256,128,4,2,4,4,2,xp>"),
+    (("stage", "320x512", 1, 2, 0), CC.DGRAD, 0, "dgrad_bn", False, "conv_halo_x3_kernel<512,64,8,1,2,3,2,xp>"),
+    (("stage", "320x512", 1, 0, 0), CC.FWD, 1, "x3", False, "conv_halo_x3_kernel<256,64,4,2,1,4>"),
+    (("stage", "320x512_b8", 3, 0, 0), CC.FWD, 1, "h2", False, "conv_halo_x3_kernel<128,128,2,4,2,4,2>"),
+    (("stage", "192x256", 1, 1, 1), CC.FWD, 1, "w16", False, "conv_halo_w16_kernel<64,4,2,1>"),
+    (("stage", "192x256", 2, 0, 0), CC.DGRAD, 0, "w16", False, "conv_halo_w16_kernel<128,2,4,2>"),
+    (("stage", "320x512", 2, 0, 0), CC.FWD, 0, "mp", False, "conv_halo_kernel<128,2,4>"),
+    (("stage", "320x512", 1, 0, 0), CC.FWD, 0, "amax", False, "conv_halo_kernel<64,4,2>"),
+    (("1x1", "320x512", 2, 0, 0), CC.FWD, 0, "h2f_wp", True, "conv_dma_kernel<128,128,2,4>/h2"),
+    (("1x1", "320x512", 2, 0, 2), CC.FWD, 0, "yh2", True, "conv_dma_kernel<128,128,2,4>/h2"),
+    (("1x1", "320x512", 1, 0, 0), CC.DGRAD, 0, "h2f", True, "conv_dma_kernel<128,64,4,2>/h2"),
+    (("1x1", "320x512", 1, 0, 0), CC.FWD, 0, "amax", False, "conv_dma_kernel<128,64,4,2>"),
+    (("1x1", "64x96", 3, 0, 0), CC.FWD, 0, "h2f", True, "conv_dma_kernel<64,64,2,2>"),
+    (("prob", "tail64", 0), None, None, "mp", False, "conv_dma_kernel<64,64,2,2>"),
+    (("prob", "n32", 3), None, None, "mp", False, "conv_dma_kernel<128,32,4,1>"),
+    (("prob", "s2_odd", 2), None, None, "mp", False, "conv_kernel<128,32,4,1>"),
+    (("prob", "s2_class", 0), None, None, "amax", False, "conv_dma_kernel<64,64,2,2>"),
+    (("prob", "halo_thin", 2), None, None, "x3", False, "conv_halo_x3_kernel<256,64,4,2,1,4>"),
+    (("prob", "halo_thin", 1), None, None, "h2", False, "conv_halo_x3_kernel<128,64,4,2,2,8,2>"),
+    (("prob", "halo_thin", 3), None, None, "x3", False, "conv_halo_x3_kernel<128,128,2,4,1,4>"),
+]
+
+
+def test_profiler_labels():
+    """ops._conv_label formats the label from the plan; bench.py keys its roofline block on `conv_halo_x3_kernel<...,2>`, a trailing `,xp>`,
+    `conv_dma_kernel<128,...>/h2`, `conv_halo_w16_kernel` and `conv_kernel`"""
+    from deflow_amd import ops
+    for src, mode, epi, form, h2f, want in LABELS:
+        if src[0] == "prob":
+            p = CC.PROBS[src[1]][src[2]]
+            x, y = _descs(p)
+            k, stride, mode, epi = p.k, p.stride, CC.FWD if p.mode == "fwd" else CC.DGRAD, CC.EPI[p.epi]
+        else:
+            x, y = _stage(src[1], src[2], src[3]), _stage(src[1], src[2], src[4])
+            k, stride = (3, 1) if src[0] == "stage" else (1, 1)
+        assert ops._conv_label(x, y, k, stride, mode, epi, form, h2f) == want, (src, form)
+    for shape in ("conv_halo_x3_kernel<", ",2>", ",xp>", "conv_dma_kernel<128,", "/h2", "conv_halo_w16_kernel<", "conv_kernel<"):
+        assert any(shape in row[-1] for row in LABELS), shape
 
 
 # the library's own split counts (wgrad, wgrad1_h2, wgrad_s2_h2) per weight-gradient problem, in table order
