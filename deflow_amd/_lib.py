@@ -201,6 +201,8 @@ _SIGS = {
     "df_dt_ws_bytes": [I, I, I, I, I],
     "df_dt_build": [P, P, I, I, F, F, F, F, I, I, I, I, P, P, P],
     "df_dt_lookup": [P, P, P, I, I, F, F, F, F, I, I, I, I, P, P, P, P, P],
+    "df_iso_plan": [P, P, P, P, P, I, I, I, I, I, P, P, P, P],
+    "df_iso_pairs": [P, P, P, I, I, I, F, P, P, P],
     "df_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
     "df_adam_step_dev": [P, P, P, P, L, F, F, F, F, P, F, P],
 }

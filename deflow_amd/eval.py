@@ -215,10 +215,38 @@ def fastnsf_config(given: Dict[str, str]):
     return cfg, fastnsf.params_from_command(own)
 
 
+def mbnsf_config(given: Dict[str, str]):
+    """``model=mbnsf``: (configuration, mbnsf parameters) from the command line alone, as ``fastnsf_config``; batch_size defaults to
+    mbnsf.COMMAND_BATCH_SIZE.  ``icp_*``, ``nsfp_*`` and ``fastnsf_*`` keys are refused.  Needs no GPU and reads no file."""
+    from . import fastnsf, mbnsf, nsfp, rigid
+    for k in ("checkpoint", "inference_dtype"):
+        if k in given:
+            raise SystemExit(f"model=mbnsf has no weights: it takes no {k}=")
+    for keys, owner in ((rigid.COMMAND_KEYS, "icpflow"), (nsfp.COMMAND_KEYS, "nsfp"), (fastnsf.COMMAND_KEYS, "fastnsf")):
+        wrong = sorted(k for k in given if k in keys)
+        if wrong:
+            raise SystemExit(f"{', '.join(wrong)}: the {'icp' if owner == 'icpflow' else owner}_* keys belong to model={owner}")
+    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in mbnsf.COMMAND_KEYS}
+    cfg = parse_overrides([a for k, a in given.items() if k not in mbnsf.COMMAND_KEYS and k != "model"])
+    cfg["model"] = "mbnsf"
+    if "batch_size" not in given:
+        cfg["batch_size"] = mbnsf.COMMAND_BATCH_SIZE
+    return cfg, mbnsf.params_from_command(own)
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
+    is_mbnsf = given.get("model") == "model=mbnsf"
+    if is_mbnsf and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        raise SystemExit("model=mbnsf writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
+                         "metrics, python -m deflow_amd.save model=mbnsf writes its flow")
+    if not is_mbnsf:
+        from .mbnsf import COMMAND_KEYS as MBNSF_KEYS
+        wrong = sorted(k for k in given if k in MBNSF_KEYS)
+        if wrong:
+            raise SystemExit(f"{', '.join(wrong)}: the mbnsf_* keys belong to model=mbnsf")
     icpflow = given.get("model") == "model=icpflow"
     if icpflow and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         raise SystemExit("model=icpflow writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
@@ -251,11 +279,14 @@ def main(argv=None):
         (cfg, nsfp_params), path = nsfp_config(given), None
     elif is_fastnsf:
         (cfg, fastnsf_params), path = fastnsf_config(given), None
+    elif is_mbnsf:
+        (cfg, mbnsf_params), path = mbnsf_config(given), None
     elif "checkpoint" not in given:
         raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE +
                          "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]"
                          "\n       python -m deflow_amd.eval model=nsfp [av2_mode=val] [val_data=<dir>|synthetic] [nsfp_*=]"
-                         "\n       python -m deflow_amd.eval model=fastnsf [av2_mode=val] [val_data=<dir>|synthetic] [fastnsf_*=]")
+                         "\n       python -m deflow_amd.eval model=fastnsf [av2_mode=val] [val_data=<dir>|synthetic] [fastnsf_*=]"
+                         "\n       python -m deflow_amd.eval model=mbnsf [av2_mode=val] [val_data=<dir>|synthetic] [mbnsf_*=]")
     else:
         path = given["checkpoint"].split("=", 1)[1]
         cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
@@ -285,6 +316,9 @@ def main(argv=None):
     elif is_fastnsf:
         from .fastnsf import FastNsf
         model = FastNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **fastnsf_params)
+    elif is_mbnsf:
+        from .mbnsf import MbNsf
+        model = MbNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **mbnsf_params)
     else:
         model = build_model(cfg).to(dev)
         res = model.load_from_checkpoint(path)

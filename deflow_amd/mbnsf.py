@@ -1,0 +1,267 @@
+"""Per-pair flow optimised on a GPU distance transform with a per-cluster rigidity term (``model=mbnsf``): ``fastnsf``'s loop -- one small
+coordinate MLP per pair of sweeps against a lookup in the distance transform of the second sweep -- plus a penalty on every change of the
+distances between rows of one cluster of the first sweep, so that the rows of one body move together.  No weights and no checkpoint.
+
+UNPINNED: the idea is MBNSF's multi-body regulariser (Vidanapathirana et al., 3DV'24), but upstream's source is absent and was not read;
+every choice here is this project's own.  The definition is in DESIGN.md section 6m and include/deflow_amd.h; tests/helpers/iso_ref.py
+restates it in torch.  The clusters come from ``cluster.dbscan`` once per pair, their ordered row lists from df_rigid_segments, the
+neighbour table and the term from csrc/iso.hip; everything else is ``fastnsf``'s and ``nsfp``'s, unchanged.
+
+CUDA tensors only, like the rest of the library: there is no CPU fallback.  The loop makes no host decision, so one iteration can be
+captured as a HIP graph (``graph=True``): a linear chain on one stream."""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from . import fastnsf
+from ._lib import call, ptr, stream
+from .fastnsf import _rows, _tensor, dt_build, dt_grid, dt_lookup, start_params
+from .nsfp import BETAS, EPS, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze, mlp_backward, mlp_forward, param_stride
+from .rigid import PairFlowModel
+
+P_MAX = 16               # pairs per row (csrc/iso.hip: ISO_PMAX)
+
+# every default of section 6m: fastnsf's ten, then the term's and the clustering's; all of them are arguments of mbnsf_optimize and MbNsf,
+# and `mbnsf_<name>=` keys of the commands
+DEFAULTS: Dict[str, object] = {**fastnsf.DEFAULTS, "rigid_weight": 10.0, "rigid_pairs": 4, "rigid_delta": 0.2, "eps": 0.7, "min_points": 4,
+                               "min_cluster_size": 20, "max_cluster_points": 8192}
+COMMAND_KEYS: Dict[str, str] = {"mbnsf_" + k: k for k in DEFAULTS}
+# default batch_size of the commands: fastnsf's peak per sample (about 0.9 GB at the defaults and 80 000 rows) plus the neighbour table,
+# N x 2 rigid_pairs x 8 bytes (5 MB)
+COMMAND_BATCH_SIZE = 4
+
+
+def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
+    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
+    import ast
+    p: Dict[str, object] = {}
+    for k, v in given.items():
+        try:
+            p[COMMAND_KEYS[k]] = ast.literal_eval(v.capitalize() if v.lower() in ("true", "false") else v)
+        except (ValueError, SyntaxError):
+            raise SystemExit(f"bad value for {k}: {v!r}")
+    try:
+        return check_params(p)
+    except (ValueError, TypeError) as e:
+        raise SystemExit(f"bad value among the mbnsf_* keys: {e}")
+
+
+def check_params(p: Dict[str, object]) -> Dict[str, object]:
+    """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
+    out = dict(DEFAULTS)
+    for k, v in p.items():
+        if k not in DEFAULTS:
+            raise ValueError(f"mbnsf_optimize: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
+        out[k] = v
+    try:
+        out.update(fastnsf.check_params({k: out[k] for k in fastnsf.DEFAULTS}))
+    except ValueError as e:
+        raise ValueError(str(e).replace("fastnsf_optimize:", "mbnsf_optimize:")) from None
+
+    def number(k):
+        v = out[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"mbnsf_optimize: {k} must be a finite number, got {v!r}")
+        return v
+
+    def integer(k, lo, hi):
+        v = number(k)
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"mbnsf_optimize: {k} must be an integer in [{lo}, {hi}], got {v!r}")
+        out[k] = int(v)
+
+    if number("rigid_weight") < 0:
+        raise ValueError(f"mbnsf_optimize: rigid_weight must be finite and >= 0, got {out['rigid_weight']!r}")
+    out["rigid_weight"] = float(out["rigid_weight"])
+    for k in ("rigid_delta", "eps"):
+        if number(k) <= 0:
+            raise ValueError(f"mbnsf_optimize: {k} must be positive and finite, got {out[k]!r}")
+        out[k] = float(out[k])
+    integer("rigid_pairs", 1, P_MAX)
+    integer("min_points", 1, 1 << 30)
+    integer("min_cluster_size", 1, 1 << 30)
+    integer("max_cluster_points", 1, 1 << 30)
+    return out
+
+
+def kcap(N0: int, min_cluster_size: int) -> int:
+    """cluster slots per sample: every cluster has at least min_cluster_size rows, so no more than this many exist"""
+    return max(int(N0) // int(min_cluster_size), 1)
+
+
+def _table(fn: str, name: str, t, dtype, B: int, N: int, device):
+    _tensor(fn, name, t, dtype, None, device)
+    if t.dim() != 3 or t.shape[0] != B or t.shape[1] != N or t.shape[2] < 2 or t.shape[2] % 2 or t.shape[2] > 2 * P_MAX:
+        raise ValueError(f"{fn}: {name} must be {dtype} of shape ({B}, {N}, 2 P) with 1 <= P <= {P_MAX}, got {tuple(t.shape)}")
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{fn}: {name} must be contiguous and 16-byte aligned")
+
+
+def iso_plan(x: torch.Tensor, count: torch.Tensor, labels: torch.Tensor, *, pairs: int, max_cluster_points: int,
+             kcap: Optional[int] = None, status: Optional[torch.Tensor] = None):
+    """x [B,N,3] f32 with count [B] i32 valid leading rows, labels [B,N] i32 (0: no cluster; 1..kcap, default kcap = N)
+    -> nbr [B,N,2 pairs] i32 (the rows of every row's forward, then backward partners inside its cluster, -1 without partners),
+    r0 [B,N,2 pairs] f32 (their rest distances, 0 at -1), n_pairs [B] i32 (the pair instances M_b).  Labels of rows behind the count are
+    ignored.  status: optional i32[1] that is added to for a label outside [0, kcap].  Exact integers; two calls are bit-identical;
+    workspaces come from torch's allocator; no host synchronisation."""
+    B, N = _rows("iso_plan", "x", x)
+    dev = x.device
+    _tensor("iso_plan", "count", count, torch.int32, (B,), dev)
+    _tensor("iso_plan", "labels", labels, torch.int32, (B, N), dev)
+    for name, v, hi in (("pairs", pairs, P_MAX), ("max_cluster_points", max_cluster_points, 1 << 30)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f"iso_plan: {name} must be an integer in [1, {hi}], got {v!r}")
+    K = N if kcap is None else kcap
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= N + 1:
+        raise ValueError(f"iso_plan: kcap must be an integer in [1, {N + 1}], got {kcap!r}")
+    if B * N * 2 * pairs >= 2 ** 31 or B * (N + 1) >= 2 ** 31 or B * (2 * K + 1) >= 2 ** 31:
+        raise ValueError(f"iso_plan: x: B * N * 2 * pairs < 2^31 expected, got B = {B}, N = {N}, pairs = {pairs}")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        _tensor("iso_plan", "status", status, torch.int32, (1,), dev)
+    x, count = x.detach().contiguous(), count.contiguous()
+    counted = torch.arange(N, device=dev)[None] < count.clamp(0, N)[:, None]
+    ext = torch.zeros(B, N + 1, dtype=torch.int32, device=dev)          # the labels, then one column of zeros: df_rigid_segments' N1 = 1
+    lab = torch.where(counted, labels, torch.zeros_like(labels)).contiguous()
+    ext[:, :N] = lab
+    need = int(call("df_rigid_segments_ws_bytes", B, N, 1, K))
+    if need < 0:
+        raise ValueError(f"iso_plan: x: df_rigid_segments_ws_bytes refused B = {B}, N = {N}, kcap = {K}")
+    ws = torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
+    seg_off = torch.empty(B, 2 * K + 1, dtype=torch.int32, device=dev)
+    seg_rows = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
+    nbr = torch.empty(B, N, 2 * pairs, dtype=torch.int32, device=dev)
+    r0 = torch.empty(B, N, 2 * pairs, dtype=torch.float32, device=dev)
+    n_pairs = torch.empty(B, dtype=torch.int32, device=dev)
+    s = stream()
+    call("df_rigid_segments", ptr(ext), B, N, 1, K, ptr(seg_off), ptr(seg_rows), ptr(status), ptr(ws), s)
+    call("df_iso_plan", ptr(x), ptr(count), ptr(lab), ptr(seg_off), ptr(seg_rows), B, N, K, pairs, max_cluster_points, ptr(nbr), ptr(r0),
+         ptr(n_pairs), s)
+    return nbr, r0, n_pairs
+
+
+def iso_pairs(w: torch.Tensor, nbr: torch.Tensor, r0: torch.Tensor, *, delta: float):
+    """w [B,N,3] f32 (the warped rows), nbr / r0 [B,N,2P] (iso_plan's) -> v [B,N] f32 (the penalty summed over each row's P forward
+    instances) and g [B,N,3] f32 (d (sum of the penalties) / d w, not normalised).  Every element is written, 0 at a row without
+    partners; no atomics: two calls are bit-identical.  No host synchronisation."""
+    B, N = _rows("iso_pairs", "w", w)
+    _table("iso_pairs", "nbr", nbr, torch.int32, B, N, w.device)
+    _table("iso_pairs", "r0", r0, torch.float32, B, N, w.device)
+    if r0.shape != nbr.shape:
+        raise ValueError(f"iso_pairs: r0 must have the shape of nbr {tuple(nbr.shape)}, got {tuple(r0.shape)}")
+    if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not (math.isfinite(delta) and delta > 0):
+        raise ValueError(f"iso_pairs: delta must be positive and finite, got {delta!r}")
+    P = int(nbr.shape[2]) // 2
+    if B * N * 2 * P >= 2 ** 31:
+        raise ValueError(f"iso_pairs: w: B * N * 2 P < 2^31 expected, got B = {B}, N = {N}, P = {P}")
+    v = torch.empty(B, N, dtype=torch.float32, device=w.device)
+    g = torch.empty(B, N, 3, dtype=torch.float32, device=w.device)
+    call("df_iso_pairs", ptr(w.detach().contiguous()), ptr(nbr), ptr(r0), B, N, P, float(delta), ptr(v), ptr(g), stream())
+    return v, g
+
+
+def mbnsf_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *, grid_range: Sequence[float],
+                   init: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, **params):
+    """The arguments and the result of ``fastnsf.fastnsf_optimize``, with loss = data + rigid_weight x iso (section 6m).
+    labels: the cluster labels [B,N0] i32 of the first sweep when the caller has them (else ``cluster.dbscan`` over the participating
+    rows, xy cells over grid_range).  info holds fastnsf's keys and labels [B,N0] i32, n_pairs [B] i32 (the pair instances M_b),
+    cluster_status i32[1] (dbscan's and the lists' status word, 0 on a sane input), last_terms [B,2] (data, iso of the last iteration).
+    Keywords: DEFAULTS.  Uses no torch autograd.  No host synchronisation unless check_every > 0."""
+    B, N0 = _rows("mbnsf_optimize", "pc0s", pc0s)
+    B1, N1 = _rows("mbnsf_optimize", "pc1", pc1)
+    dev = pc0s.device
+    if B1 != B or pc1.device != dev:
+        raise ValueError(f"mbnsf_optimize: pc1 must have the batch size ({B}) and device of pc0s, got {tuple(pc1.shape)} on {pc1.device}")
+    for name, c in (("count0", count0), ("count1", count1)):
+        _tensor("mbnsf_optimize", name, c, torch.int32, (B,), dev)
+    if labels is not None:
+        _tensor("mbnsf_optimize", "labels", labels, torch.int32, (B, N0), dev)
+    p = check_params(params)
+    depth, iters, cell = p["depth"], p["iters"], p["cell"]
+    try:
+        origin, dims, R = dt_grid(grid_range, cell, p["trunc"])
+    except ValueError as e:
+        raise ValueError(str(e).replace("dt_grid:", "mbnsf_optimize:")) from None
+    S = param_stride(depth)
+    start = start_params(depth, p["seed"]) if init is None else init
+    if not isinstance(start, torch.Tensor) or tuple(start.shape) != (1, S) or start.dtype != torch.float32:
+        raise ValueError(f"mbnsf_optimize: init must be a float32 tensor of shape (1, {S})")
+    rw, P = p["rigid_weight"], p["rigid_pairs"]
+    with torch.no_grad():
+        pc0s, pc1 = pc0s.detach().contiguous(), pc1.detach().contiguous()
+        n0, n1 = count0.contiguous().clamp(0, N0), count1.contiguous().clamp(0, N1)
+        m0 = (torch.arange(N0, device=dev)[None] < n0[:, None]) & torch.isfinite(pc0s).all(dim=2)
+        x0 = torch.where(m0[..., None], pc0s, torch.zeros_like(pc0s))
+        # the clusters, their neighbour table and the number of pair instances: once per pair
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if labels is None:
+            from .cluster import dbscan
+            labels, _ = dbscan(x0, n0, mask=m0, eps=p["eps"], min_points=p["min_points"], min_cluster_size=p["min_cluster_size"],
+                               grid_range=(grid_range[0], grid_range[1], grid_range[3], grid_range[4]), status=status)
+        labels = torch.where(m0, labels, torch.zeros_like(labels)).contiguous()
+        nbr, r0, n_pairs = iso_plan(x0, n0, labels, pairs=P, max_cluster_points=p["max_cluster_points"],
+                                    kcap=kcap(N0, p["min_cluster_size"]), status=status)
+        inv_m = 1.0 / n_pairs.clamp_min(1).to(torch.float32)               # 1 / max(M_b, 1)
+        g_scale = (rw * inv_m)[:, None, None]
+        dt2 = dt_build(pc1, n1, origin=origin, cell=cell, dims=dims, radius=R)
+        arena = start.to(dev)[None].repeat(B, 1, 1).contiguous()       # [B][1][S]
+        grads = torch.zeros_like(arena)
+        exp_avg, exp_avg_sq = torch.zeros_like(arena), torch.zeros_like(arena)
+        step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        st = _loop_state(B, iters, x0)
+        st["cells"] = None
+        last_terms = torch.zeros(B, 2, dtype=torch.float32, device=dev)
+        fpar = arena[:, 0]
+        inf = torch.full((B, N0), math.inf, dtype=torch.float32, device=dev)
+
+        def iteration():
+            F, acts = mlp_forward(x0, n0, fpar, depth)
+            F = F * m0[..., None]
+            W = x0 + F
+            d, g, cells, _ = dt_lookup(W, n0, dt2, origin=origin, cell=cell, radius=R, return_cells=True)
+            data, weight = _mean_and_weight(torch.where(m0, d, inf))
+            v, gi = iso_pairs(W, nbr, r0, delta=p["rigid_delta"])
+            iso = torch.stack([row.clone().sum() for row in v.unbind(0)]) * inv_m      # _mean_and_weight's rule: sample by sample
+            loss = data + rw * iso
+            dF = g * weight[..., None] + g_scale * gi                       # (gi is 0 outside m0: those rows have no partners)
+            mlp_backward(x0, n0, fpar, depth, acts, dF, need_dx=False, dparams=grads[:, 0])
+            _snapshot_and_freeze(st, loss, F, t_dev, p)
+            step_dev.add_(1)
+            call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), arena.numel(), p["lr"], BETAS[0], BETAS[1], EPS,
+                 ptr(step_dev), 1.0, stream())
+            last_terms.copy_(torch.stack([data, iso], dim=1))
+            st["cells"] = cells
+
+        ran = _run(iteration, st, p)
+        flow = st["best_flow"] * m0[..., None]
+    info = {"best_loss": st["best"], "loss_history": st["history"], "stalled": st["stalled"], "frozen": st["frozen"], "params": arena,
+            "grads": grads, "cells": st["cells"], "iters_run": ran, "labels": labels, "n_pairs": n_pairs, "cluster_status": status,
+            "last_terms": last_terms}
+    return flow, info
+
+
+class MbNsf(PairFlowModel):
+    """``model=mbnsf``: ``fastnsf.FastNsf``'s interface -- ``forward_padded`` and ``forward`` with ``DeFlow``'s keys, no weights -- around
+    ``mbnsf_optimize``.  Every keyword besides point_cloud_range / voxel_size is one of DEFAULTS; the transform's grid covers
+    point_cloud_range."""
+
+    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
+        super().__init__(point_cloud_range, voxel_size)
+        self.params = check_params(params)
+        dt_grid(self.point_cloud_range, self.params["cell"], self.params["trunc"])        # refuse a grid that does not fit here
+
+    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
+        """flow [B,N,3]: row i < counts0[b] is the residual flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind
+        them; pose_flow [B,N,3] of every input row.  Reads nothing back when check_every = 0."""
+        st = self._pair(batch)
+        flow, info = mbnsf_optimize(st["points_c0"], st["counts0"], st["points_c1"], st["counts1"], grid_range=self.point_cloud_range,
+                                    **self.params)
+        st.update({"flow": flow, "best_loss": info["best_loss"], "loss_history": info["loss_history"], "stalled": info["stalled"],
+                   "frozen": info["frozen"], "labels": info["labels"], "n_pairs": info["n_pairs"], "last_terms": info["last_terms"]})
+        self.last_state = st
+        return st

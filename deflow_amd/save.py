@@ -23,7 +23,10 @@ the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` 
 ``deflow_amd.nsfp`` (UNPINNED): no checkpoint, the ``nsfp_*`` keys (``nsfp.COMMAND_KEYS``) in the file's ``meta``.
 
 ``python -m deflow_amd.save model=fastnsf dataset_path=<dir> [res_name=fastnsf] [fastnsf_*=...]`` likewise for the flow optimised on a
-distance transform of ``deflow_amd.fastnsf`` (UNPINNED), with the ``fastnsf_*`` keys (``fastnsf.COMMAND_KEYS``)."""
+distance transform of ``deflow_amd.fastnsf`` (UNPINNED), with the ``fastnsf_*`` keys (``fastnsf.COMMAND_KEYS``).
+
+``python -m deflow_amd.save model=mbnsf dataset_path=<dir> [res_name=mbnsf] [mbnsf_*=...]`` likewise for that flow with the per-cluster
+rigidity term of ``deflow_amd.mbnsf`` (UNPINNED), with the ``mbnsf_*`` keys (``mbnsf.COMMAND_KEYS``)."""
 from __future__ import annotations
 
 import json
@@ -61,6 +64,13 @@ FASTNSF_USAGE = ("usage: python -m deflow_amd.save model=fastnsf dataset_path=<d
                  "[fastnsf_min_delta=1e-4] [fastnsf_check_every=50] [fastnsf_seed=0] [fastnsf_graph=false]\n"
                  "batch_size defaults to 4: per sample the distance-transform grid (2 bytes per voxel of point_cloud_range / fastnsf_cell, twice "
                  "while it is built) and the saved activations, (fastnsf_depth + 1) x N x 512 bytes, twice during the backward")
+MBNSF_USAGE = ("usage: python -m deflow_amd.save model=mbnsf dataset_path=<dir of .h5 files> [res_name=mbnsf] [scenes=a,b] [batch_size=4] "
+               "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
+               "[mbnsf_depth=7] [mbnsf_iters=1000] [mbnsf_lr=8e-3] [mbnsf_cell=0.1] [mbnsf_trunc=2.0] [mbnsf_patience=100] "
+               "[mbnsf_min_delta=1e-4] [mbnsf_check_every=50] [mbnsf_seed=0] [mbnsf_graph=false] [mbnsf_rigid_weight=10.0] "
+               "[mbnsf_rigid_pairs=4] [mbnsf_rigid_delta=0.2] [mbnsf_eps=0.7] [mbnsf_min_points=4] [mbnsf_min_cluster_size=20] "
+               "[mbnsf_max_cluster_points=8192]\n"
+               "batch_size defaults to 4: model=fastnsf's memory per sample plus the neighbour table, N x 2 mbnsf_rigid_pairs x 8 bytes")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -72,13 +82,14 @@ def _flag(k: str, v: str) -> bool:
 def parse_args(argv: List[str]) -> Dict[str, Any]:
     """key=value arguments -> this command's own options, plus under ``_rest`` ({key: "key=value"}) the hyper-parameter overrides that
     ``eval.resolve_config`` lays over the checkpoint's configuration.  Reads no file."""
-    from . import fastnsf, nsfp
+    from . import fastnsf, mbnsf, nsfp
     from .rigid import COMMAND_KEYS, params_from_command
     opt = dict(OWN_DEFAULTS)
     rest: Dict[str, str] = {}
     icp: Dict[str, str] = {}
     own_nsfp: Dict[str, str] = {}
     own_fast: Dict[str, str] = {}
+    own_mb: Dict[str, str] = {}
     for a in argv:
         if "=" not in a:
             raise SystemExit(f"expected key=value, got {a!r}")
@@ -110,6 +121,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             own_nsfp[k] = v
         elif k in fastnsf.COMMAND_KEYS:
             own_fast[k] = v
+        elif k in mbnsf.COMMAND_KEYS:
+            own_mb[k] = v
         elif k in DEFAULTS or k in _TARGET_ALIASES or k == "model.target.grid_feature_size":
             if k in ("batch_size", "num_workers"):
                 try:
@@ -124,7 +137,26 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
     opt["icpflow"] = rest.get("model") == "model=icpflow" or rest.get("model.name") == "model.name=icpflow"
     opt["nsfp"] = rest.get("model") == "model=nsfp" or rest.get("model.name") == "model.name=nsfp"
     opt["fastnsf"] = rest.get("model") == "model=fastnsf" or rest.get("model.name") == "model.name=fastnsf"
-    if opt["fastnsf"]:
+    opt["mbnsf"] = rest.get("model") == "model=mbnsf" or rest.get("model.name") == "model.name=mbnsf"
+    if opt["mbnsf"]:
+        if opt["checkpoint"] or opt["inference_dtype"]:
+            raise SystemExit("model=mbnsf has no weights: it takes neither checkpoint= nor inference_dtype=\n" + MBNSF_USAGE)
+        if icp:
+            raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + MBNSF_USAGE)
+        if own_nsfp:
+            raise SystemExit(f"{', '.join(sorted(own_nsfp))}: the nsfp_* keys belong to model=nsfp\n" + MBNSF_USAGE)
+        if own_fast:
+            raise SystemExit(f"{', '.join(sorted(own_fast))}: the fastnsf_* keys belong to model=fastnsf\n" + MBNSF_USAGE)
+        if not opt["dataset_path"]:
+            raise SystemExit(MBNSF_USAGE)
+        rest.pop("model", None), rest.pop("model.name", None)
+        rest.setdefault("batch_size", f"batch_size={mbnsf.COMMAND_BATCH_SIZE}")
+        opt["mbnsf_params"] = mbnsf.params_from_command(own_mb)
+        if opt["res_name"] is None:
+            opt["res_name"] = "mbnsf"
+    elif own_mb:
+        raise SystemExit(f"{', '.join(sorted(own_mb))}: the mbnsf_* keys belong to model=mbnsf\n" + MBNSF_USAGE)
+    elif opt["fastnsf"]:
         if opt["checkpoint"] or opt["inference_dtype"]:
             raise SystemExit("model=fastnsf has no weights: it takes neither checkpoint= nor inference_dtype=\n" + FASTNSF_USAGE)
         if icp:
@@ -306,6 +338,13 @@ def main(argv=None) -> int:
         meta = {"res_name": res_name, "checkpoint": None, "model": "fastnsf", "voxel_size": [float(v) for v in cfg["voxel_size"]],
                 "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
                 "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6l (UNPINNED)"}
+    elif opt["mbnsf"]:
+        from .mbnsf import MbNsf
+        cfg = parse_overrides(list(opt["_rest"].values()))
+        model = MbNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["mbnsf_params"])
+        meta = {"res_name": res_name, "checkpoint": None, "model": "mbnsf", "voxel_size": [float(v) for v in cfg["voxel_size"]],
+                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
+                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6m (UNPINNED)"}
     else:
         cfg = resolve_config(opt["checkpoint"], opt["_rest"])
         model = build_model(cfg).to(dev)

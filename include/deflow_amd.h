@@ -1006,6 +1006,36 @@ int df_dt_build(const float* ref, const int32_t* count, int B, int N, float ox, 
 int df_dt_lookup(const float* query, const int32_t* count, const uint16_t* dt2, int B, int N, float ox, float oy, float oz, float cell,
                  int GX, int GY, int GZ, int R, float* d, float* g, int32_t* cells /*nullable*/, uint8_t* clamped /*nullable*/, void* stream);
 
+/* ------------------------------------------------------------------ per-cluster rigidity term (model=mbnsf) ----
+ * The multi-body regulariser of the flow optimised on a distance transform.  UNPINNED: upstream's MBNSF source is
+ * absent and was not read; the definition is this project's own.  x [B,N,3] f32 is the first sweep (non-participating rows as 0), count
+ * [B] i32 its valid leading rows (clamped to [0, N]), labels [B,N] i32 its cluster labels (0: none; 1..Kcap), P = the pairs per row, 1..16.
+ * Lists.  seg_off [B, 2 Kcap + 1] and seg_rows [B, N + 1] are df_rigid_segments' output for N0 = N, N1 = 1 on the labels followed by one
+ *   column of zeros, the labels of rows >= count set to 0 first: list 2k = the rows of cluster k + 1 in ascending order, L[0 .. n-1].  A
+ *   cluster is eligible with 2 <= n <= max_cluster_points.  Rows >= count, rows of label 0 or of a label outside 1..Kcap, rows of an
+ *   ineligible cluster and rows their list does not hold have no partners.
+ * Pairs.  The row at position i of an eligible list has the FORWARD partners L[(i + s_k) mod n], s_k = 1 + floor((k - 1)(n - 1) / P),
+ *   k = 1..P (every s_k is in 1..n-1; repeats count as often as they occur), and the BACKWARD partners L[(i - s_k) mod n]: the rows
+ *   whose k-th forward partner it is.  M_b = P x (rows of sample b with partners) is the number of pair instances.
+ * df_iso_plan: -> nbr [B,N,2P] i32 (entries 0..P-1: the forward partners' rows for k = 1..P, entries P..2P-1: the backward ones; -1 in
+ *   all of them for a row without partners), r0 [B,N,2P] f32 (the rest distance |x_a - x_b| of each entry, 0 at -1), pairs [B] i32 = M_b.
+ *   Every element is written.  The integers are exact (pairs: one integer atomic add per block of 256 rows); two calls are bit-identical.
+ * Distances.  |a - b| = sqrt(fp32(fp32(fp32(dx dx) + fp32(dy dy)) + fp32(dz dz))) with dx = fp32(a.x - b.x) ...: differences first, no
+ *   fused multiply-add, so that an instance has the same r0, r1 and e from either of its ends.
+ * df_iso_pairs: w [B,N,3] f32 (the warped rows x + F), nbr and r0 as above, delta > 0 -> v [B,N] f32, g [B,N,3] f32.  For an entry with
+ *   partner q of row a: r1 = |w_a - w_q|, e = |r1 - r0|, rho(e) = e^2 for e <= delta and delta (2 e - delta) beyond (value and slope are
+ *   continuous at delta).  v[a] = the sum of rho over the row's P FORWARD entries in entry order, so that sum_a v[a] counts every instance
+ *   once; g[a] = the sum over all 2P entries in entry order of rho'(e) sign(r1 - r0) (w_a - w_q) / r1 (an entry with r1 == 0 adds its
+ *   value and no gradient): d (sum of rho over the instances) / d w_a, not normalised.  An entry outside [0, N) is skipped like -1.  One
+ *   thread per row; the row's table entries are read with 16-byte loads when P is even.  EVERY element of v and g is written (0 at a
+ *   row without partners); no atomics; two calls are bit-identical; g of the two rows of a 2-row cluster are exact negatives.
+ * P outside 1..16, B outside 1..65535, N < 1, B N 2P >= 2^31 (df_iso_plan: Kcap < 1 too): DF_E_SHAPE.  NULL pointers, max_cluster_points
+ * < 1, a delta that is not positive and finite: DF_E_ARG.  nbr / r0 not 16-byte, the other buffers not 4-byte aligned: DF_E_ALIGN.  No
+ * launch then.  Grids come from B and N only; the entries never allocate or synchronise and read nothing back. */
+int df_iso_plan(const float* x, const int32_t* count, const int32_t* labels, const int32_t* seg_off, const int32_t* seg_rows, int B, int N,
+                int Kcap, int P, int max_cluster_points, int32_t* nbr, float* r0, int32_t* pairs, void* stream);
+int df_iso_pairs(const float* w, const int32_t* nbr, const float* r0, int B, int N, int P, float delta, float* v, float* g, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
