@@ -234,10 +234,39 @@ def mbnsf_config(given: Dict[str, str]):
     return cfg, mbnsf.params_from_command(own)
 
 
+def floxels_config(given: Dict[str, str]):
+    """``model=floxels``: (configuration, floxels parameters) from the command line alone, as ``mbnsf_config``; batch_size defaults to
+    floxels.COMMAND_BATCH_SIZE.  ``icp_*``, ``nsfp_*``, ``fastnsf_*`` and ``mbnsf_*`` keys are refused.  Needs no GPU and reads no file."""
+    from . import fastnsf, floxels, mbnsf, nsfp, rigid
+    for k in ("checkpoint", "inference_dtype"):
+        if k in given:
+            raise SystemExit(f"model=floxels has no weights: it takes no {k}=")
+    for keys, owner in ((rigid.COMMAND_KEYS, "icpflow"), (nsfp.COMMAND_KEYS, "nsfp"), (fastnsf.COMMAND_KEYS, "fastnsf"),
+                        (mbnsf.COMMAND_KEYS, "mbnsf")):
+        wrong = sorted(k for k in given if k in keys)
+        if wrong:
+            raise SystemExit(f"{', '.join(wrong)}: the {'icp' if owner == 'icpflow' else owner}_* keys belong to model={owner}")
+    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in floxels.COMMAND_KEYS}
+    cfg = parse_overrides([a for k, a in given.items() if k not in floxels.COMMAND_KEYS and k != "model"])
+    cfg["model"] = "floxels"
+    if "batch_size" not in given:
+        cfg["batch_size"] = floxels.COMMAND_BATCH_SIZE
+    return cfg, floxels.params_from_command(own)
+
+
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
+    is_floxels = given.get("model") == "model=floxels"
+    if is_floxels and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        raise SystemExit("model=floxels writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
+                         "metrics, python -m deflow_amd.save model=floxels writes its flow")
+    if not is_floxels:
+        from .floxels import COMMAND_KEYS as FLOXELS_KEYS
+        wrong = sorted(k for k in given if k in FLOXELS_KEYS)
+        if wrong:
+            raise SystemExit(f"{', '.join(wrong)}: the floxels_* keys belong to model=floxels")
     is_mbnsf = given.get("model") == "model=mbnsf"
     if is_mbnsf and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         raise SystemExit("model=mbnsf writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
@@ -281,12 +310,15 @@ def main(argv=None):
         (cfg, fastnsf_params), path = fastnsf_config(given), None
     elif is_mbnsf:
         (cfg, mbnsf_params), path = mbnsf_config(given), None
+    elif is_floxels:
+        (cfg, floxels_params), path = floxels_config(given), None
     elif "checkpoint" not in given:
         raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE +
                          "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]"
                          "\n       python -m deflow_amd.eval model=nsfp [av2_mode=val] [val_data=<dir>|synthetic] [nsfp_*=]"
                          "\n       python -m deflow_amd.eval model=fastnsf [av2_mode=val] [val_data=<dir>|synthetic] [fastnsf_*=]"
-                         "\n       python -m deflow_amd.eval model=mbnsf [av2_mode=val] [val_data=<dir>|synthetic] [mbnsf_*=]")
+                         "\n       python -m deflow_amd.eval model=mbnsf [av2_mode=val] [val_data=<dir>|synthetic] [mbnsf_*=]"
+                         "\n       python -m deflow_amd.eval model=floxels [av2_mode=val] [val_data=<dir>|synthetic] [floxels_*=]")
     else:
         path = given["checkpoint"].split("=", 1)[1]
         cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
@@ -319,6 +351,9 @@ def main(argv=None):
     elif is_mbnsf:
         from .mbnsf import MbNsf
         model = MbNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **mbnsf_params)
+    elif is_floxels:
+        from .floxels import Floxels
+        model = Floxels(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **floxels_params)
     else:
         model = build_model(cfg).to(dev)
         res = model.load_from_checkpoint(path)

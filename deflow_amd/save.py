@@ -26,7 +26,10 @@ the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` 
 distance transform of ``deflow_amd.fastnsf`` (UNPINNED), with the ``fastnsf_*`` keys (``fastnsf.COMMAND_KEYS``).
 
 ``python -m deflow_amd.save model=mbnsf dataset_path=<dir> [res_name=mbnsf] [mbnsf_*=...]`` likewise for that flow with the per-cluster
-rigidity term of ``deflow_amd.mbnsf`` (UNPINNED), with the ``mbnsf_*`` keys (``mbnsf.COMMAND_KEYS``)."""
+rigidity term of ``deflow_amd.mbnsf`` (UNPINNED), with the ``mbnsf_*`` keys (``mbnsf.COMMAND_KEYS``).
+
+``python -m deflow_amd.save model=floxels dataset_path=<dir> [res_name=floxels] [floxels_*=...]`` likewise for the flow on a voxel grid
+of ``deflow_amd.floxels`` (UNPINNED), with the ``floxels_*`` keys (``floxels.COMMAND_KEYS``)."""
 from __future__ import annotations
 
 import json
@@ -71,6 +74,12 @@ MBNSF_USAGE = ("usage: python -m deflow_amd.save model=mbnsf dataset_path=<dir o
                "[mbnsf_rigid_pairs=4] [mbnsf_rigid_delta=0.2] [mbnsf_eps=0.7] [mbnsf_min_points=4] [mbnsf_min_cluster_size=20] "
                "[mbnsf_max_cluster_points=8192]\n"
                "batch_size defaults to 4: model=fastnsf's memory per sample plus the neighbour table, N x 2 mbnsf_rigid_pairs x 8 bytes")
+FLOXELS_USAGE = ("usage: python -m deflow_amd.save model=floxels dataset_path=<dir of .h5 files> [res_name=floxels] [scenes=a,b] [batch_size=4] "
+                 "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
+                 "[floxels_voxel=0.4] [floxels_smooth_weight=10.0] [floxels_iters=1000] [floxels_lr=0.05] [floxels_cell=0.1] "
+                 "[floxels_trunc=2.0] [floxels_patience=100] [floxels_min_delta=1e-4] [floxels_check_every=50] [floxels_graph=false]\n"
+                 "batch_size defaults to 4: per sample the distance-transform grid (2 bytes per voxel of point_cloud_range / floxels_cell, twice "
+                 "while it is built); the field and its five companions are 12 bytes per node of point_cloud_range / floxels_voxel each")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -82,7 +91,7 @@ def _flag(k: str, v: str) -> bool:
 def parse_args(argv: List[str]) -> Dict[str, Any]:
     """key=value arguments -> this command's own options, plus under ``_rest`` ({key: "key=value"}) the hyper-parameter overrides that
     ``eval.resolve_config`` lays over the checkpoint's configuration.  Reads no file."""
-    from . import fastnsf, mbnsf, nsfp
+    from . import fastnsf, floxels, mbnsf, nsfp
     from .rigid import COMMAND_KEYS, params_from_command
     opt = dict(OWN_DEFAULTS)
     rest: Dict[str, str] = {}
@@ -90,6 +99,7 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
     own_nsfp: Dict[str, str] = {}
     own_fast: Dict[str, str] = {}
     own_mb: Dict[str, str] = {}
+    own_flox: Dict[str, str] = {}
     for a in argv:
         if "=" not in a:
             raise SystemExit(f"expected key=value, got {a!r}")
@@ -123,6 +133,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             own_fast[k] = v
         elif k in mbnsf.COMMAND_KEYS:
             own_mb[k] = v
+        elif k in floxels.COMMAND_KEYS:
+            own_flox[k] = v
         elif k in DEFAULTS or k in _TARGET_ALIASES or k == "model.target.grid_feature_size":
             if k in ("batch_size", "num_workers"):
                 try:
@@ -138,7 +150,24 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
     opt["nsfp"] = rest.get("model") == "model=nsfp" or rest.get("model.name") == "model.name=nsfp"
     opt["fastnsf"] = rest.get("model") == "model=fastnsf" or rest.get("model.name") == "model.name=fastnsf"
     opt["mbnsf"] = rest.get("model") == "model=mbnsf" or rest.get("model.name") == "model.name=mbnsf"
-    if opt["mbnsf"]:
+    opt["floxels"] = rest.get("model") == "model=floxels" or rest.get("model.name") == "model.name=floxels"
+    if opt["floxels"]:
+        if opt["checkpoint"] or opt["inference_dtype"]:
+            raise SystemExit("model=floxels has no weights: it takes neither checkpoint= nor inference_dtype=\n" + FLOXELS_USAGE)
+        for wrong, owner in ((icp, "icpflow"), (own_nsfp, "nsfp"), (own_fast, "fastnsf"), (own_mb, "mbnsf")):
+            if wrong:
+                raise SystemExit(f"{', '.join(sorted(wrong))}: the {'icp' if owner == 'icpflow' else owner}_* keys belong to model={owner}\n" +
+                                 FLOXELS_USAGE)
+        if not opt["dataset_path"]:
+            raise SystemExit(FLOXELS_USAGE)
+        rest.pop("model", None), rest.pop("model.name", None)
+        rest.setdefault("batch_size", f"batch_size={floxels.COMMAND_BATCH_SIZE}")
+        opt["floxels_params"] = floxels.params_from_command(own_flox)
+        if opt["res_name"] is None:
+            opt["res_name"] = "floxels"
+    elif own_flox:
+        raise SystemExit(f"{', '.join(sorted(own_flox))}: the floxels_* keys belong to model=floxels\n" + FLOXELS_USAGE)
+    elif opt["mbnsf"]:
         if opt["checkpoint"] or opt["inference_dtype"]:
             raise SystemExit("model=mbnsf has no weights: it takes neither checkpoint= nor inference_dtype=\n" + MBNSF_USAGE)
         if icp:
@@ -338,6 +367,13 @@ def main(argv=None) -> int:
         meta = {"res_name": res_name, "checkpoint": None, "model": "fastnsf", "voxel_size": [float(v) for v in cfg["voxel_size"]],
                 "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
                 "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6l (UNPINNED)"}
+    elif opt["floxels"]:
+        from .floxels import Floxels
+        cfg = parse_overrides(list(opt["_rest"].values()))
+        model = Floxels(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["floxels_params"])
+        meta = {"res_name": res_name, "checkpoint": None, "model": "floxels", "voxel_size": [float(v) for v in cfg["voxel_size"]],
+                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
+                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6n (UNPINNED)"}
     elif opt["mbnsf"]:
         from .mbnsf import MbNsf
         cfg = parse_overrides(list(opt["_rest"].values()))

@@ -1036,6 +1036,52 @@ int df_iso_plan(const float* x, const int32_t* count, const int32_t* labels, con
                 int Kcap, int P, int max_cluster_points, int32_t* nbr, float* r0, int32_t* pairs, void* stream);
 int df_iso_pairs(const float* w, const int32_t* nbr, const float* r0, int B, int N, int P, float delta, float* v, float* g, void* stream);
 
+/* ------------------------------------------------------------------ flow field on a voxel grid (model=floxels) ----
+ * The field of the per-pair flow optimised without a net.  UNPINNED: upstream's Floxels source is absent and was
+ * not read; the definition is this project's own.  x [B,N,3] f32 is the first sweep, count [B] i32 its valid leading rows (clamped to
+ * [0, N]).  The grid has VX x VY x VZ nodes (each >= 2), node (i, j, k) at origin + voxel (i, j, k); NV = VX VY VZ nodes and
+ * NC = (VX-1)(VY-1)(VZ-1) cells per sample.  theta [B,VZ,VY,VX,3] f32: one 3-vector per node, x fastest, the components innermost.
+ * Rows.  A counted row with three finite coordinates takes part.  Per axis u = fp32((x - o) / voxel) (IEEE subtraction and division),
+ *   clamped to [0, V - 1]; i = min(floor(u), V - 2), t = u - i in [0, 1] (exact); cell = (iz (VY-1) + iy)(VX-1) + ix.  Every other row
+ *   has cell = -1 and t = 0, and no index is formed from it.
+ * df_vox_plan (once per pair): -> cell [B,N] i32, frac [B,N,3] f32 (tx, ty, tz); the rows that take part grouped by (sample, cell) with
+ *   df_cell_sort (key b NC + cell): idx_sorted [B N] i32 holds b N + row, the rows of one cell in ascending order, cell after cell and
+ *   sample after sample, and -1 in the slots behind the last grouped row; cell_rng [B NC, 2] i32 = every cell's (first, end) slot,
+ *   first == end for an empty cell; active [B,NV] u8 = 1 for the corners of every cell that holds a row (gathered per node from its at
+ *   most 8 incident cells' ranges, no atomics), else 0; pairs [B] i32 = M_b, the axis-adjacent node pairs with both ends active (one
+ *   integer atomic add per workgroup of 256 nodes after a memset).  Every element of every output is written; all of it is exact; two
+ *   calls are bit-identical.  ws: df_vox_plan_ws_bytes(B, N, VX, VY, VZ) bytes, 16-byte aligned (-1 for a refused shape).  The sort's
+ *   keys have 30 bits: df_vox_plan (only) also refuses B NC >= 2^30 - 1 with DF_E_SHAPE.
+ * Weights.  Corner (a, d, e) of a row's cell has the weight fp32(fp32(wx wy) wz), wx = tx for a = 1 and 1 - tx for a = 0, wy and wz
+ *   alike: the same bits in the read and in its transpose.
+ * df_vox_sample: theta, cell, frac -> F [B,N,3] f32 = the sum over the 8 corners of weight x theta[node], corners in the order e, d, a
+ *   (a fastest).  One thread per row; the two x-neighbours of a corner pair are 24 contiguous bytes.  Every element is written, 0 where
+ *   cell is outside [0, NC).
+ * df_vox_scatter: dF [B,N,3] f32 (rows that do not take part are never read: they may hold NaN), frac, idx_sorted, cell_rng -> dtheta
+ *   [B,NV,3] f32, the exact transpose of the read in gather form: a node sums weight_corner(t_r) dF_r over its at most 8 incident cells
+ *   in the order e, d, a (the node is corner (a, d, e) of the cell at (ix - a, iy - d, iz - e)) and over each cell's rows in ascending
+ *   order.  One thread per node.  A cell of up to 128 rows is added row by row to the node's running sum, the cells in the order above.  A
+ *   cell of more than 128 rows is summed by the node's whole wave after those: lane l adds the rows first + l, first + l + 64, ... in
+ *   order, the 64 partial sums are added in a fixed xor butterfly (32, 16, ..., 1; fp32 additions), and that total is added to the node's
+ *   sum, the long cells of a node in the order above.  Either way the result is a function of the cell's rows and their order alone: no
+ *   float atomics; two calls are bit-identical; a sample's result depends neither on B nor on the other samples.  Every node is written,
+ *   0 where nothing is incident.  Ranges are clipped to [0, B N] and entries outside the sample skipped.
+ * df_vox_smooth: theta, active -> v [B,NV] f32, g [B,NV,3] f32.  For an active node n and an active axis neighbour q:
+ *   d = fp32(theta_n - theta_q) per component, |d|^2 = fp32(fp32(fp32(dx dx) + fp32(dy dy)) + fp32(dz dz)).  v[n] = the sum of |d|^2 over
+ *   the FORWARD neighbours x+1, y+1, z+1 in that order, so that sum_n v[n] counts every pair once; g[n] = the sum of 2 d over the
+ *   neighbours x-1, x+1, y-1, y+1, z-1, z+1 in that order: d (sum of |d|^2 over the pairs) / d theta_n, not normalised.  No fused
+ *   multiply-add.  A node on the grid's face has no neighbour beyond it.  No atomics; every element is written, 0 at an inactive node.
+ * B outside 1..65535, N < 1, a V < 2, or 3 B N, 3 B NV or B NC >= 2^31: DF_E_SHAPE.  NULL pointers, a voxel that is not positive and
+ * finite, a NaN origin: DF_E_ARG.  Buffers not 4-byte (ws: 16-byte) aligned: DF_E_ALIGN.  No launch then.  Grids come from B, N and the
+ * grid's dimensions only; the entries never allocate or synchronise and read nothing back. */
+int64_t df_vox_plan_ws_bytes(int B, int N, int VX, int VY, int VZ);
+int df_vox_plan(const float* x, const int32_t* count, int B, int N, float ox, float oy, float oz, float voxel, int VX, int VY, int VZ,
+                int32_t* cell, float* frac, int32_t* idx_sorted, int32_t* cell_rng, uint8_t* active, int32_t* pairs, void* ws, void* stream);
+int df_vox_sample(const float* theta, const int32_t* cell, const float* frac, int B, int N, int VX, int VY, int VZ, float* F, void* stream);
+int df_vox_scatter(const float* dF, const float* frac, const int32_t* idx_sorted, const int32_t* cell_rng, int B, int N, int VX, int VY,
+                   int VZ, float* dtheta, void* stream);
+int df_vox_smooth(const float* theta, const uint8_t* active, int B, int VX, int VY, int VZ, float* v, float* g, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
