@@ -16,7 +16,10 @@ under ``<root>/test`` (``test_data=<dir>`` names the directory itself): per fram
 has a successor, ``<scene_id>/<timestamp>.feather`` with the fp16 flow of the masked rows, in one zip (``output=<zip>``, default
 ``<checkpoint stem>.av2_submit_v<version>.zip`` beside the checkpoint).  The rows are selected, rounded and laid out as the file's body on
 the GPU (deflow_amd/submit.py, DESIGN.md section 6g, UNPINNED); deflow_amd/feather.py wraps the metadata around it.  ``ground_source=
-auto|file|sidecar|online``, ``batch_size=``, ``num_workers=`` and ``inference_dtype=`` as in ``deflow_amd.save``."""
+auto|file|sidecar|online``, ``batch_size=``, ``num_workers=`` and ``inference_dtype=`` as in ``deflow_amd.save``.
+
+``python -m deflow_amd.eval model=<name> [av2_mode=val] [<prefix>_*=]`` evaluates a checkpoint-free pair model of the table in
+``deflow_amd.pairflow`` instead: no ``checkpoint=``, its own keys validated by its module, another model's keys refused."""
 from __future__ import annotations
 
 import json
@@ -26,6 +29,7 @@ from typing import Any, Dict, List
 
 import torch
 
+from . import pairflow
 from .train import DATA_KEYS, DEFAULTS, _TARGET_ALIASES, build_model, grid_from, parse_overrides, split_metrics_impl
 
 
@@ -163,162 +167,26 @@ def main_test(argv: List[str]) -> Dict[str, Any]:
     return result
 
 
-def icpflow_config(given: Dict[str, str]):
-    """``model=icpflow``: (configuration, rigid parameters) from the command line alone -- the defaults of deflow_amd.train under the keys
-    as typed ({key: "key=value"}), the ``icp_*`` keys validated by deflow_amd.rigid.  Needs no GPU and reads no file."""
-    from .rigid import COMMAND_KEYS, params_from_command
-    for k in ("checkpoint", "inference_dtype"):
-        if k in given:
-            raise SystemExit(f"model=icpflow has no weights: it takes no {k}=")
-    icp = {k: a.split("=", 1)[1] for k, a in given.items() if k in COMMAND_KEYS}
-    cfg = parse_overrides([a for k, a in given.items() if k not in COMMAND_KEYS and k != "model"])
-    cfg["model"] = "icpflow"
-    return cfg, params_from_command(icp)
-
-
-def nsfp_config(given: Dict[str, str]):
-    """``model=nsfp``: (configuration, nsfp parameters) from the command line alone, as ``icpflow_config``; batch_size defaults to
-    nsfp.COMMAND_BATCH_SIZE.  ``icp_*`` keys are refused.  Needs no GPU and reads no file."""
-    from . import nsfp, rigid
-    for k in ("checkpoint", "inference_dtype"):
-        if k in given:
-            raise SystemExit(f"model=nsfp has no weights: it takes no {k}=")
-    wrong = sorted(k for k in given if k in rigid.COMMAND_KEYS)
-    if wrong:
-        raise SystemExit(f"{', '.join(wrong)}: the icp_* keys belong to model=icpflow")
-    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in nsfp.COMMAND_KEYS}
-    cfg = parse_overrides([a for k, a in given.items() if k not in nsfp.COMMAND_KEYS and k != "model"])
-    cfg["model"] = "nsfp"
-    if "batch_size" not in given:
-        cfg["batch_size"] = nsfp.COMMAND_BATCH_SIZE
-    return cfg, nsfp.params_from_command(own)
-
-
-def fastnsf_config(given: Dict[str, str]):
-    """``model=fastnsf``: (configuration, fastnsf parameters) from the command line alone, as ``nsfp_config``; batch_size defaults to
-    fastnsf.COMMAND_BATCH_SIZE.  ``icp_*`` and ``nsfp_*`` keys are refused.  Needs no GPU and reads no file."""
-    from . import fastnsf, nsfp, rigid
-    for k in ("checkpoint", "inference_dtype"):
-        if k in given:
-            raise SystemExit(f"model=fastnsf has no weights: it takes no {k}=")
-    wrong = sorted(k for k in given if k in rigid.COMMAND_KEYS)
-    if wrong:
-        raise SystemExit(f"{', '.join(wrong)}: the icp_* keys belong to model=icpflow")
-    wrong = sorted(k for k in given if k in nsfp.COMMAND_KEYS)
-    if wrong:
-        raise SystemExit(f"{', '.join(wrong)}: the nsfp_* keys belong to model=nsfp")
-    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in fastnsf.COMMAND_KEYS}
-    cfg = parse_overrides([a for k, a in given.items() if k not in fastnsf.COMMAND_KEYS and k != "model"])
-    cfg["model"] = "fastnsf"
-    if "batch_size" not in given:
-        cfg["batch_size"] = fastnsf.COMMAND_BATCH_SIZE
-    return cfg, fastnsf.params_from_command(own)
-
-
-def mbnsf_config(given: Dict[str, str]):
-    """``model=mbnsf``: (configuration, mbnsf parameters) from the command line alone, as ``fastnsf_config``; batch_size defaults to
-    mbnsf.COMMAND_BATCH_SIZE.  ``icp_*``, ``nsfp_*`` and ``fastnsf_*`` keys are refused.  Needs no GPU and reads no file."""
-    from . import fastnsf, mbnsf, nsfp, rigid
-    for k in ("checkpoint", "inference_dtype"):
-        if k in given:
-            raise SystemExit(f"model=mbnsf has no weights: it takes no {k}=")
-    for keys, owner in ((rigid.COMMAND_KEYS, "icpflow"), (nsfp.COMMAND_KEYS, "nsfp"), (fastnsf.COMMAND_KEYS, "fastnsf")):
-        wrong = sorted(k for k in given if k in keys)
-        if wrong:
-            raise SystemExit(f"{', '.join(wrong)}: the {'icp' if owner == 'icpflow' else owner}_* keys belong to model={owner}")
-    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in mbnsf.COMMAND_KEYS}
-    cfg = parse_overrides([a for k, a in given.items() if k not in mbnsf.COMMAND_KEYS and k != "model"])
-    cfg["model"] = "mbnsf"
-    if "batch_size" not in given:
-        cfg["batch_size"] = mbnsf.COMMAND_BATCH_SIZE
-    return cfg, mbnsf.params_from_command(own)
-
-
-def floxels_config(given: Dict[str, str]):
-    """``model=floxels``: (configuration, floxels parameters) from the command line alone, as ``mbnsf_config``; batch_size defaults to
-    floxels.COMMAND_BATCH_SIZE.  ``icp_*``, ``nsfp_*``, ``fastnsf_*`` and ``mbnsf_*`` keys are refused.  Needs no GPU and reads no file."""
-    from . import fastnsf, floxels, mbnsf, nsfp, rigid
-    for k in ("checkpoint", "inference_dtype"):
-        if k in given:
-            raise SystemExit(f"model=floxels has no weights: it takes no {k}=")
-    for keys, owner in ((rigid.COMMAND_KEYS, "icpflow"), (nsfp.COMMAND_KEYS, "nsfp"), (fastnsf.COMMAND_KEYS, "fastnsf"),
-                        (mbnsf.COMMAND_KEYS, "mbnsf")):
-        wrong = sorted(k for k in given if k in keys)
-        if wrong:
-            raise SystemExit(f"{', '.join(wrong)}: the {'icp' if owner == 'icpflow' else owner}_* keys belong to model={owner}")
-    own = {k: a.split("=", 1)[1] for k, a in given.items() if k in floxels.COMMAND_KEYS}
-    cfg = parse_overrides([a for k, a in given.items() if k not in floxels.COMMAND_KEYS and k != "model"])
-    cfg["model"] = "floxels"
-    if "batch_size" not in given:
-        cfg["batch_size"] = floxels.COMMAND_BATCH_SIZE
-    return cfg, floxels.params_from_command(own)
-
-
 def main(argv=None):
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
-    is_floxels = given.get("model") == "model=floxels"
-    if is_floxels and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
-        raise SystemExit("model=floxels writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
-                         "metrics, python -m deflow_amd.save model=floxels writes its flow")
-    if not is_floxels:
-        from .floxels import COMMAND_KEYS as FLOXELS_KEYS
-        wrong = sorted(k for k in given if k in FLOXELS_KEYS)
-        if wrong:
-            raise SystemExit(f"{', '.join(wrong)}: the floxels_* keys belong to model=floxels")
-    is_mbnsf = given.get("model") == "model=mbnsf"
-    if is_mbnsf and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
-        raise SystemExit("model=mbnsf writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
-                         "metrics, python -m deflow_amd.save model=mbnsf writes its flow")
-    if not is_mbnsf:
-        from .mbnsf import COMMAND_KEYS as MBNSF_KEYS
-        wrong = sorted(k for k in given if k in MBNSF_KEYS)
-        if wrong:
-            raise SystemExit(f"{', '.join(wrong)}: the mbnsf_* keys belong to model=mbnsf")
-    icpflow = given.get("model") == "model=icpflow"
-    if icpflow and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
-        raise SystemExit("model=icpflow writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
-                         "metrics, python -m deflow_amd.save model=icpflow writes its flow")
-    is_nsfp = given.get("model") == "model=nsfp"
-    if is_nsfp and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
-        raise SystemExit("model=nsfp writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
-                         "metrics, python -m deflow_amd.save model=nsfp writes its flow")
-    is_fastnsf = given.get("model") == "model=fastnsf"
-    if is_fastnsf and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
-        raise SystemExit("model=fastnsf writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
-                         "metrics, python -m deflow_amd.save model=fastnsf writes its flow")
-    if not is_fastnsf:
-        from .fastnsf import COMMAND_KEYS as FASTNSF_KEYS
-        wrong = sorted(k for k in given if k in FASTNSF_KEYS)
-        if wrong:
-            raise SystemExit(f"{', '.join(wrong)}: the fastnsf_* keys belong to model=fastnsf")
-    if not is_nsfp and not icpflow and not is_fastnsf:
-        from .nsfp import COMMAND_KEYS as NSFP_KEYS
-        wrong = sorted(k for k in given if k in NSFP_KEYS)
-        if wrong:
-            raise SystemExit(f"{', '.join(wrong)}: the nsfp_* keys belong to model=nsfp")
+    pair = pairflow.selected(given)         # a checkpoint-free pair model (deflow_amd/pairflow.py), or None
+    if pair and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
+        raise SystemExit(f"model={pair.name} writes no leaderboard submission (av2_mode=test is out of its scope): av2_mode=val prints its "
+                         f"metrics, python -m deflow_amd.save model={pair.name} writes its flow")
+    wrong = pairflow.foreign_keys(given, pair)
+    if wrong:
+        raise SystemExit(wrong[1])
     if given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
         return main_test(args)          # the leaderboard submission: no metrics (the test split has no labels)
     if given.get("av2_mode", "av2_mode=val") != "av2_mode=val":
         raise SystemExit(f"unknown {given['av2_mode']} (val: the metrics, test: the leaderboard submission)")
-    if icpflow:
-        (cfg, icp_params), path = icpflow_config(given), None
-    elif is_nsfp:
-        (cfg, nsfp_params), path = nsfp_config(given), None
-    elif is_fastnsf:
-        (cfg, fastnsf_params), path = fastnsf_config(given), None
-    elif is_mbnsf:
-        (cfg, mbnsf_params), path = mbnsf_config(given), None
-    elif is_floxels:
-        (cfg, floxels_params), path = floxels_config(given), None
+    if pair:
+        (cfg, pair_params), path = pairflow.config(pair, given), None
     elif "checkpoint" not in given:
-        raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE +
-                         "\n       python -m deflow_amd.eval model=icpflow [av2_mode=val] [val_data=<dir>|synthetic] [icp_*=]"
-                         "\n       python -m deflow_amd.eval model=nsfp [av2_mode=val] [val_data=<dir>|synthetic] [nsfp_*=]"
-                         "\n       python -m deflow_amd.eval model=fastnsf [av2_mode=val] [val_data=<dir>|synthetic] [fastnsf_*=]"
-                         "\n       python -m deflow_amd.eval model=mbnsf [av2_mode=val] [val_data=<dir>|synthetic] [mbnsf_*=]"
-                         "\n       python -m deflow_amd.eval model=floxels [av2_mode=val] [val_data=<dir>|synthetic] [floxels_*=]")
+        raise SystemExit("usage: python -m deflow_amd.eval checkpoint=<path> [av2_mode=val] [val_data=<dir>|synthetic]\n" + TEST_USAGE + "".join(
+            f"\n       python -m deflow_amd.eval model={e.name} [av2_mode=val] [val_data=<dir>|synthetic] [{e.prefix}_*=]" for e in pairflow.TABLE))
     else:
         path = given["checkpoint"].split("=", 1)[1]
         cfg = resolve_config(path, given, skip=("leaderboard_version", "inference_dtype"))
@@ -339,21 +207,8 @@ def main(argv=None):
         official = DeviceMetrics(dev)
     else:
         official = OfficialMetrics()
-    if icpflow:
-        from .rigid import IcpFlow
-        model = IcpFlow(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **icp_params)
-    elif is_nsfp:
-        from .nsfp import Nsfp
-        model = Nsfp(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **nsfp_params)
-    elif is_fastnsf:
-        from .fastnsf import FastNsf
-        model = FastNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **fastnsf_params)
-    elif is_mbnsf:
-        from .mbnsf import MbNsf
-        model = MbNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **mbnsf_params)
-    elif is_floxels:
-        from .floxels import Floxels
-        model = Floxels(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **floxels_params)
+    if pair:
+        model = pairflow.build(pair, cfg, pair_params)
     else:
         model = build_model(cfg).to(dev)
         res = model.load_from_checkpoint(path)

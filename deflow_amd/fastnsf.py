@@ -15,10 +15,11 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
+from . import pairflow
 from ._lib import call, ptr, stream
 from .nsfp import (BETAS, EPS, MAX_DEPTH, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze, init_params, mlp_backward, mlp_forward,
                    param_stride)
-from .rigid import PairFlowModel
+from .pairflow import PairFlowModel, _tensor
 
 R_MAX = 255
 LINE_TILE = 256          # x positions per workgroup of the transform's passes (csrc/dt.hip: DT_TILE)
@@ -58,16 +59,6 @@ def dt_grid(grid_range: Sequence[float], cell: float, trunc: float):
         raise ValueError(f"dt_grid: grid_range / cell: {dims[0]} x {dims[1]} x {dims[2]} voxels do not fit 31 bits")
     origin = tuple(_f32(r[a] - R * cell) for a in range(3))
     return origin, dims, R
-
-
-def _tensor(fn: str, name: str, t, dtype, shape=None, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"{fn}: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"{fn}: {name} is on {t.device}, not on {device}")
-    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{fn}: {name} must be {dtype}" + (f" of shape {tuple(shape)}" if shape is not None else "") +
-                         f", got {t.dtype} {tuple(t.shape)}")
 
 
 def _rows(fn: str, name: str, t) -> Tuple[int, int]:
@@ -132,53 +123,21 @@ def dt_lookup(query: torch.Tensor, count: torch.Tensor, dt2: torch.Tensor, *, or
 
 
 def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
-    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
-    import ast
-    p: Dict[str, object] = {}
-    for k, v in given.items():
-        try:
-            p[COMMAND_KEYS[k]] = ast.literal_eval(v.capitalize() if v.lower() in ("true", "false") else v)
-        except (ValueError, SyntaxError):
-            raise SystemExit(f"bad value for {k}: {v!r}")
-    try:
-        return check_params(p)
-    except (ValueError, TypeError) as e:
-        raise SystemExit(f"bad value among the fastnsf_* keys: {e}")
+    return pairflow.params_from_command(pairflow.entry("fastnsf"), given)
 
 
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    out = dict(DEFAULTS)
-    for k, v in p.items():
-        if k not in DEFAULTS:
-            raise ValueError(f"fastnsf_optimize: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
-        out[k] = v
-
-    def integer(k, lo, hi):
-        v = out[k]
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= int(v) <= hi:
-            raise ValueError(f"fastnsf_optimize: {k} must be an integer in [{lo}, {hi}], got {v!r}")
-        out[k] = int(v)
-
-    integer("depth", 0, MAX_DEPTH)
-    integer("iters", 1, 1 << 20)
-    integer("patience", 1, 1 << 30)
-    integer("check_every", 0, 1 << 30)
-    integer("seed", 0, (1 << 63) - 1)
+    fn = "fastnsf_optimize"
+    out = pairflow.merged(fn, DEFAULTS, p)
+    for k, lo, hi in (("depth", 0, MAX_DEPTH), ("iters", 1, 1 << 20), ("patience", 1, 1 << 30), ("check_every", 0, 1 << 30),
+                      ("seed", 0, (1 << 63) - 1)):
+        pairflow.integer(fn, out, k, lo, hi)
     for k in ("lr", "cell", "trunc"):
-        if isinstance(out[k], bool) or not isinstance(out[k], (int, float)) or not (math.isfinite(out[k]) and out[k] > 0):
-            raise ValueError(f"fastnsf_optimize: {k} must be positive and finite, got {out[k]!r}")
-        out[k] = float(out[k])
-    R = int(round(out["trunc"] / out["cell"]))
-    if not 1 <= R <= R_MAX or abs(R * out["cell"] - out["trunc"]) > 1e-6 * out["trunc"]:
-        raise ValueError(f"fastnsf_optimize: trunc must be a whole number of cells, 1 to {R_MAX} of them, got trunc = {out['trunc']}, "
-                         f"cell = {out['cell']}")
-    if isinstance(out["min_delta"], bool) or not isinstance(out["min_delta"], (int, float)) or not (
-            math.isfinite(out["min_delta"]) and out["min_delta"] >= 0):
-        raise ValueError(f"fastnsf_optimize: min_delta must be finite and >= 0, got {out['min_delta']!r}")
-    out["min_delta"] = float(out["min_delta"])
-    if not isinstance(out["graph"], bool):
-        raise ValueError(f"fastnsf_optimize: graph must be True or False, got {out['graph']!r}")
+        pairflow.positive(fn, out, k)
+    pairflow.whole_cells(fn, out, R_MAX)
+    pairflow.nonneg(fn, out, "min_delta")
+    pairflow.flag(fn, out, "graph")
     return out
 
 

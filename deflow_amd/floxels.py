@@ -17,10 +17,11 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
+from . import pairflow
 from ._lib import call, ptr, stream
-from .fastnsf import R_MAX, _f32, _rows, _tensor, dt_build, dt_grid, dt_lookup
+from .fastnsf import R_MAX, _f32, _rows, dt_build, dt_grid, dt_lookup
 from .nsfp import BETAS, EPS, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze
-from .rigid import PairFlowModel
+from .pairflow import PairFlowModel, _tensor
 
 # every default of section 6n; all of them are arguments of floxels_optimize and Floxels, and `floxels_<name>=` keys of the commands
 DEFAULTS: Dict[str, object] = {"voxel": 0.4, "smooth_weight": 10.0, "iters": 1000, "lr": 0.05, "cell": 0.1, "trunc": 2.0, "patience": 100,
@@ -165,57 +166,21 @@ def vox_smooth(theta: torch.Tensor, active: torch.Tensor):
 
 
 def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
-    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
-    import ast
-    p: Dict[str, object] = {}
-    for k, v in given.items():
-        try:
-            p[COMMAND_KEYS[k]] = ast.literal_eval(v.capitalize() if v.lower() in ("true", "false") else v)
-        except (ValueError, SyntaxError):
-            raise SystemExit(f"bad value for {k}: {v!r}")
-    try:
-        return check_params(p)
-    except (ValueError, TypeError) as e:
-        raise SystemExit(f"bad value among the floxels_* keys: {e}")
+    return pairflow.params_from_command(pairflow.entry("floxels"), given)
 
 
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    out = dict(DEFAULTS)
-    for k, v in p.items():
-        if k not in DEFAULTS:
-            raise ValueError(f"floxels_optimize: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
-        out[k] = v
-
-    def number(k):
-        v = out[k]
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"floxels_optimize: {k} must be a finite number, got {v!r}")
-        return v
-
-    def integer(k, lo, hi):
-        v = number(k)
-        if int(v) != v or not lo <= int(v) <= hi:
-            raise ValueError(f"floxels_optimize: {k} must be an integer in [{lo}, {hi}], got {v!r}")
-        out[k] = int(v)
-
-    integer("iters", 1, 1 << 20)
-    integer("patience", 1, 1 << 30)
-    integer("check_every", 0, 1 << 30)
+    fn = "floxels_optimize"
+    out = pairflow.merged(fn, DEFAULTS, p)
+    for k, lo, hi in (("iters", 1, 1 << 20), ("patience", 1, 1 << 30), ("check_every", 0, 1 << 30)):
+        pairflow.integer(fn, out, k, lo, hi, finite=True)
     for k in ("voxel", "lr", "cell", "trunc"):
-        if number(k) <= 0:
-            raise ValueError(f"floxels_optimize: {k} must be positive and finite, got {out[k]!r}")
-        out[k] = float(out[k])
+        pairflow.positive(fn, out, k, finite=True)
     for k in ("smooth_weight", "min_delta"):
-        if number(k) < 0:
-            raise ValueError(f"floxels_optimize: {k} must be finite and >= 0, got {out[k]!r}")
-        out[k] = float(out[k])
-    R = int(round(out["trunc"] / out["cell"]))
-    if not 1 <= R <= R_MAX or abs(R * out["cell"] - out["trunc"]) > 1e-6 * out["trunc"]:
-        raise ValueError(f"floxels_optimize: trunc must be a whole number of cells, 1 to {R_MAX} of them, got trunc = {out['trunc']}, "
-                         f"cell = {out['cell']}")
-    if not isinstance(out["graph"], bool):
-        raise ValueError(f"floxels_optimize: graph must be True or False, got {out['graph']!r}")
+        pairflow.nonneg(fn, out, k, finite=True)
+    pairflow.whole_cells(fn, out, R_MAX)
+    pairflow.flag(fn, out, "graph")
     return out
 
 

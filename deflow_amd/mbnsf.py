@@ -16,11 +16,11 @@ from typing import Dict, Optional, Sequence
 
 import torch
 
-from . import fastnsf
+from . import fastnsf, pairflow
 from ._lib import call, ptr, stream
-from .fastnsf import _rows, _tensor, dt_build, dt_grid, dt_lookup, start_params
+from .fastnsf import _rows, dt_build, dt_grid, dt_lookup, start_params
 from .nsfp import BETAS, EPS, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze, mlp_backward, mlp_forward, param_stride
-from .rigid import PairFlowModel
+from .pairflow import PairFlowModel, _tensor
 
 P_MAX = 16               # pairs per row (csrc/iso.hip: ISO_PMAX)
 
@@ -35,55 +35,22 @@ COMMAND_BATCH_SIZE = 4
 
 
 def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
-    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
-    import ast
-    p: Dict[str, object] = {}
-    for k, v in given.items():
-        try:
-            p[COMMAND_KEYS[k]] = ast.literal_eval(v.capitalize() if v.lower() in ("true", "false") else v)
-        except (ValueError, SyntaxError):
-            raise SystemExit(f"bad value for {k}: {v!r}")
-    try:
-        return check_params(p)
-    except (ValueError, TypeError) as e:
-        raise SystemExit(f"bad value among the mbnsf_* keys: {e}")
+    return pairflow.params_from_command(pairflow.entry("mbnsf"), given)
 
 
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    out = dict(DEFAULTS)
-    for k, v in p.items():
-        if k not in DEFAULTS:
-            raise ValueError(f"mbnsf_optimize: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
-        out[k] = v
+    fn = "mbnsf_optimize"
+    out = pairflow.merged(fn, DEFAULTS, p)
     try:
         out.update(fastnsf.check_params({k: out[k] for k in fastnsf.DEFAULTS}))
     except ValueError as e:
         raise ValueError(str(e).replace("fastnsf_optimize:", "mbnsf_optimize:")) from None
-
-    def number(k):
-        v = out[k]
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"mbnsf_optimize: {k} must be a finite number, got {v!r}")
-        return v
-
-    def integer(k, lo, hi):
-        v = number(k)
-        if int(v) != v or not lo <= int(v) <= hi:
-            raise ValueError(f"mbnsf_optimize: {k} must be an integer in [{lo}, {hi}], got {v!r}")
-        out[k] = int(v)
-
-    if number("rigid_weight") < 0:
-        raise ValueError(f"mbnsf_optimize: rigid_weight must be finite and >= 0, got {out['rigid_weight']!r}")
-    out["rigid_weight"] = float(out["rigid_weight"])
-    for k in ("rigid_delta", "eps"):
-        if number(k) <= 0:
-            raise ValueError(f"mbnsf_optimize: {k} must be positive and finite, got {out[k]!r}")
-        out[k] = float(out[k])
-    integer("rigid_pairs", 1, P_MAX)
-    integer("min_points", 1, 1 << 30)
-    integer("min_cluster_size", 1, 1 << 30)
-    integer("max_cluster_points", 1, 1 << 30)
+    pairflow.nonneg(fn, out, "rigid_weight", finite=True)
+    pairflow.positive(fn, out, "rigid_delta", finite=True)
+    pairflow.positive(fn, out, "eps", finite=True)
+    for k, hi in (("rigid_pairs", P_MAX), ("min_points", 1 << 30), ("min_cluster_size", 1 << 30), ("max_cluster_points", 1 << 30)):
+        pairflow.integer(fn, out, k, 1, hi, finite=True)
     return out
 
 

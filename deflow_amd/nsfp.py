@@ -10,14 +10,16 @@ CUDA tensors only, like the rest of the library: there is no CPU fallback.  The 
 snapshot and the freeze live on the device, so one iteration can be captured as a HIP graph (``graph=True``)."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
+from . import pairflow
 from ._lib import call, ptr, stream
 from .chamfer import CELL, GRID_RANGE, _grid, chamfer_bwd
-from .rigid import PairFlowModel
+from .pairflow import PairFlowModel
 
 WIDTH = 128
 ROW_TILE = 64            # rows per workgroup of the forward / data-gradient kernels (csrc/mlp.hip: MT)
@@ -68,61 +70,25 @@ def init_params(depth: int, seed: int) -> torch.Tensor:
 
 
 def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
-    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
-    import ast
-    p: Dict[str, object] = {}
-    for k, v in given.items():
-        try:
-            p[COMMAND_KEYS[k]] = ast.literal_eval(v.capitalize() if v.lower() in ("true", "false") else v)
-        except (ValueError, SyntaxError):
-            raise SystemExit(f"bad value for {k}: {v!r}")
-    try:
-        return check_params(p)
-    except (ValueError, TypeError) as e:
-        raise SystemExit(f"bad value among the nsfp_* keys: {e}")
+    return pairflow.params_from_command(pairflow.entry("nsfp"), given)
 
 
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    out = dict(DEFAULTS)
-    for k, v in p.items():
-        if k not in DEFAULTS:
-            raise ValueError(f"nsfp_optimize: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
-        out[k] = v
-
-    def integer(k, lo, hi):
-        v = out[k]
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= int(v) <= hi:
-            raise ValueError(f"nsfp_optimize: {k} must be an integer in [{lo}, {hi}], got {v!r}")
-        out[k] = int(v)
-
-    integer("depth", 0, MAX_DEPTH)
-    integer("iters", 1, 1 << 20)
-    integer("patience", 1, 1 << 30)
-    integer("check_every", 0, 1 << 30)
-    integer("seed", 0, (1 << 63) - 1)
-    for k in ("lr", "trunc_d2"):
-        if isinstance(out[k], bool) or not isinstance(out[k], (int, float)) or not (math.isfinite(out[k]) and out[k] > 0):
-            raise ValueError(f"nsfp_optimize: {k} must be positive and finite, got {out[k]!r}")
-        out[k] = float(out[k])
-    if isinstance(out["min_delta"], bool) or not isinstance(out["min_delta"], (int, float)) or not (
-            math.isfinite(out["min_delta"]) and out["min_delta"] >= 0):
-        raise ValueError(f"nsfp_optimize: min_delta must be finite and >= 0, got {out['min_delta']!r}")
-    out["min_delta"] = float(out["min_delta"])
-    if not isinstance(out["graph"], bool):
-        raise ValueError(f"nsfp_optimize: graph must be True or False, got {out['graph']!r}")
+    fn = "nsfp_optimize"
+    out = pairflow.merged(fn, DEFAULTS, p)
+    for k, lo, hi in (("depth", 0, MAX_DEPTH), ("iters", 1, 1 << 20), ("patience", 1, 1 << 30), ("check_every", 0, 1 << 30),
+                      ("seed", 0, (1 << 63) - 1)):
+        pairflow.integer(fn, out, k, lo, hi)
+    pairflow.positive(fn, out, "lr")
+    pairflow.positive(fn, out, "trunc_d2")
+    pairflow.nonneg(fn, out, "min_delta")
+    pairflow.flag(fn, out, "graph")
     return out
 
 
 # ---- the MLP -------------------------------------------------------------------------------------------------------------------------
-def _tensor(fn: str, name: str, t, dtype, shape=None, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"{fn}: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"{fn}: {name} is on {t.device}, x is on {device}")
-    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{fn}: {name} must be {dtype}" + (f" of shape {tuple(shape)}" if shape is not None else "") +
-                         f", got {t.dtype} {tuple(t.shape)}")
+_tensor = functools.partial(pairflow._tensor, other="x is")     # (a device mismatch is reported against x)
 
 
 def _mlp_args(fn: str, x, count, params, depth) -> Tuple[int, int, int]:

@@ -15,7 +15,9 @@ from typing import Dict, Optional, Sequence
 
 import torch
 
+from . import pairflow
 from ._lib import call, ptr, stream
+from .pairflow import PairFlowModel  # noqa: F401  (rigid.PairFlowModel stays importable)
 
 STATUS_NAMES = {0: "empty", 1: "registered", 2: "one-sided", 3: "too large", 4: "inlier fraction", 5: "no vote / yaw / displacement"}
 R_MAX = 64
@@ -28,21 +30,11 @@ DEFAULTS: Dict[str, object] = {"eps": 0.7, "min_points": 4, "min_cluster_size": 
 
 # the commands' keys (save, eval): icp_<name>, the three names that start with icp_ already as they are
 COMMAND_KEYS: Dict[str, str] = {(k if k.startswith("icp_") else "icp_" + k): k for k in DEFAULTS}
+COMMAND_BATCH_SIZE = None   # the commands' batch_size has no default of this model's own
 
 
 def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
-    """{command key: value as typed} -> validated parameters; a bad value ends the command (SystemExit) before anything runs"""
-    import ast
-    p: Dict[str, object] = {}
-    for k, v in given.items():
-        try:
-            p[COMMAND_KEYS[k]] = ast.literal_eval(v)
-        except (ValueError, SyntaxError):
-            raise SystemExit(f"bad value for {k}: {v!r}")
-    try:
-        return check_params(p)
-    except (ValueError, TypeError) as e:
-        raise SystemExit(f"bad value among the icp_* keys: {e}")
+    return pairflow.params_from_command(pairflow.entry("icpflow"), given)
 
 
 def vote_radius(max_disp: float, vote_bin: float) -> int:
@@ -54,11 +46,7 @@ def vote_radius(max_disp: float, vote_bin: float) -> int:
 
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    out = dict(DEFAULTS)
-    for k, v in p.items():
-        if k not in DEFAULTS:
-            raise ValueError(f"rigid_cluster_flow: unknown parameter {k!r}; known: {', '.join(sorted(DEFAULTS))}")
-        out[k] = v
+    out = pairflow.merged("rigid_cluster_flow", DEFAULTS, p)
     for k in ("min_points", "min_cluster_size", "min_side", "max_cluster_points", "vote_cap", "icp_cap"):
         if isinstance(out[k], bool) or int(out[k]) != out[k] or int(out[k]) < 1:
             raise ValueError(f"rigid_cluster_flow: {k} must be an integer >= 1, got {out[k]!r}")
@@ -187,91 +175,6 @@ def rigid_cluster_flow(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tens
     if return_hist:
         return flow, rigid_id, table, vote, status, hist
     return flow, rigid_id, table, vote, status
-
-
-class PairFlowModel:
-    """What the weight-free estimators (``IcpFlow``, ``nsfp.Nsfp``) share: an object with the two methods of ``DeFlow`` the commands use --
-    ``forward_padded`` and ``forward`` -- and no weights.  point_cloud_range / voxel_size decide which rows count as decoded, by the
-    voxeliser's rule (floor((p - min) / voxel) inside the grid on all three axes, on the ego-compensated rows)."""
-
-    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6)):
-        name = type(self).__name__
-        if len(point_cloud_range) != 6 or len(voxel_size) != 3:
-            raise ValueError(f"{name}: point_cloud_range has 6 values and voxel_size 3")
-        self.point_cloud_range = [float(v) for v in point_cloud_range]
-        self.voxel_size = [float(v) for v in voxel_size]
-        if not all(v > 0 for v in self.voxel_size):
-            raise ValueError(f"{name}: voxel_size must be positive, got {voxel_size}")
-        self.grid = [int(round((self.point_cloud_range[3 + i] - self.point_cloud_range[i]) / self.voxel_size[i])) for i in range(3)]
-        if not all(g >= 1 for g in self.grid):
-            raise ValueError(f"{name}: empty point_cloud_range {point_cloud_range}")
-        self.training = False
-        self.last_state: Optional[dict] = None
-
-    # (the commands treat the model as an nn.Module)
-    def eval(self):
-        return self
-
-    def to(self, *a, **k):
-        return self
-
-    def parameters(self):
-        return iter(())
-
-    def _decoded(self, pts: torch.Tensor) -> torch.Tensor:
-        """[B,N] bool: the rows the voxeliser would keep (csrc/pillar_common.h: NaN rows and rows outside the grid are not decoded)"""
-        ok = ~torch.isnan(pts).any(dim=2)
-        for i in range(3):
-            f = torch.floor((pts[..., i] - self.point_cloud_range[i]) / self.voxel_size[i])
-            ok &= (f >= 0) & (f < float(self.grid[i]))
-        return ok
-
-    @staticmethod
-    def _compact(valid: torch.Tensor):
-        """stable: idx [B,N] i64 with the valid rows first in ascending order, counts [B] i32"""
-        idx = torch.argsort((~valid).to(torch.uint8), dim=1, stable=True)
-        return idx, valid.sum(dim=1).to(torch.int32)
-
-    def _pair(self, batch: Dict[str, torch.Tensor]) -> dict:
-        """the ego-compensated first sweep, the pose flow of every input row, and both sweeps' decoded rows compacted (stable)"""
-        from .deflow import batch_transform
-        pc0 = batch["pc0"].contiguous().float()
-        pc1 = batch["pc1"].contiguous().float()
-        if not pc0.is_cuda or not pc1.is_cuda:
-            raise TypeError(f"{type(self).__name__}: pc0 and pc1 must be CUDA tensors (deflow_amd has no CPU fallback)")
-        B, N, _ = pc0.shape
-        T = batch_transform(batch, pc0.device)
-        pc0s = torch.empty_like(pc0)
-        pose_flow = torch.empty_like(pc0)
-        call("df_ego_transform", ptr(pc0), ptr(T), B, N, ptr(pc0s), ptr(pose_flow), stream())
-        v0, v1 = self._decoded(pc0s), self._decoded(pc1)
-        idx0, counts0 = self._compact(v0)
-        idx1, counts1 = self._compact(v1)
-        g0 = torch.gather(pc0s, 1, idx0[..., None].expand(-1, -1, 3))
-        g1 = torch.gather(pc1, 1, idx1[..., None].expand(-1, -1, 3))
-        return {"pose_flow": pose_flow, "counts0": counts0, "counts1": counts1, "idx_c0": idx0, "idx_c1": idx1, "pc0s": pc0s,
-                "points_c0": g0, "points_c1": g1}
-
-    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
-        raise NotImplementedError
-
-    def forward(self, batch: Dict[str, torch.Tensor]):
-        """the dict of lists ``DeFlow.forward`` returns (one host read: the per-sample counts)"""
-        st = self.forward_padded(batch)
-        B = st["flow"].shape[0]
-        m = torch.stack([st["counts0"], st["counts1"]]).tolist()
-        m0, m1 = m[0], m[1]
-        return {
-            "flow": [st["flow"][b, :m0[b]] for b in range(B)],
-            "pose_flow": [st["pose_flow"][b] for b in range(B)],
-            "pc0_valid_point_idxes": [st["idx_c0"][b, :m0[b]] for b in range(B)],
-            "pc0_points_lst": [st["points_c0"][b, :m0[b]] for b in range(B)],
-            "pc1_valid_point_idxes": [st["idx_c1"][b, :m1[b]] for b in range(B)],
-            "pc1_points_lst": [st["points_c1"][b, :m1[b]] for b in range(B)],
-        }
-
-    def __call__(self, batch):
-        return self.forward(batch)
 
 
 class IcpFlow(PairFlowModel):

@@ -14,22 +14,11 @@ to the checkpoint's file stem; ``ground_source=auto|file|sidecar`` as ``HDF5Data
 batch (``ground.GroundSegmenter``) and needs no mask on disk.  ``av2_mode`` is refused: the leaderboard submission (a zip of feather files) is
 ``python -m deflow_amd.eval checkpoint=<ckpt> av2_mode=test dataset_path=<root>``.
 
-``python -m deflow_amd.save model=icpflow dataset_path=<dir> [res_name=icpflow] [ground_source=...] [icp_*=...]`` needs no checkpoint: the
-flow comes from the training-free rigid cluster flow of ``deflow_amd.rigid`` (UNPINNED).  ``voxel_size`` and
-``point_cloud_range`` decide which rows are decoded, the ``icp_*`` keys (``rigid.COMMAND_KEYS``) are its parameters; all of them go into
-the file's ``meta``.  ``python -m deflow_amd.train ... pseudo_flow=<res_name>`` then trains on the file as pseudo labels.
-
-``python -m deflow_amd.save model=nsfp dataset_path=<dir> [res_name=nsfp] [nsfp_*=...]`` is the same for the per-pair neural flow prior of
-``deflow_amd.nsfp`` (UNPINNED): no checkpoint, the ``nsfp_*`` keys (``nsfp.COMMAND_KEYS``) in the file's ``meta``.
-
-``python -m deflow_amd.save model=fastnsf dataset_path=<dir> [res_name=fastnsf] [fastnsf_*=...]`` likewise for the flow optimised on a
-distance transform of ``deflow_amd.fastnsf`` (UNPINNED), with the ``fastnsf_*`` keys (``fastnsf.COMMAND_KEYS``).
-
-``python -m deflow_amd.save model=mbnsf dataset_path=<dir> [res_name=mbnsf] [mbnsf_*=...]`` likewise for that flow with the per-cluster
-rigidity term of ``deflow_amd.mbnsf`` (UNPINNED), with the ``mbnsf_*`` keys (``mbnsf.COMMAND_KEYS``).
-
-``python -m deflow_amd.save model=floxels dataset_path=<dir> [res_name=floxels] [floxels_*=...]`` likewise for the flow on a voxel grid
-of ``deflow_amd.floxels`` (UNPINNED), with the ``floxels_*`` keys (``floxels.COMMAND_KEYS``)."""
+``python -m deflow_amd.save model=<name> dataset_path=<dir> [res_name=<name>] [ground_source=...] [<prefix>_*=...]`` needs no checkpoint:
+the flow comes from a checkpoint-free pair model of the table in ``deflow_amd.pairflow`` (DESIGN.md sections 6j to 6n, UNPINNED; 6o for
+the table).  ``voxel_size`` and ``point_cloud_range`` decide which rows are decoded, the model's own keys (its module's ``COMMAND_KEYS``)
+are its parameters; all of them go into the file's ``meta``.  Another model's keys are refused.  ``python -m deflow_amd.train ...
+pseudo_flow=<res_name>`` then trains on the file as pseudo labels."""
 from __future__ import annotations
 
 import json
@@ -43,6 +32,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import pairflow
 from .data import HDF5Dataset
 from .train import DEFAULTS, _TARGET_ALIASES
 
@@ -52,34 +42,6 @@ OWN_DEFAULTS: Dict[str, Any] = {"checkpoint": None, "dataset_path": None, "res_n
                                 "half": False, "overwrite": False, "inference_dtype": None}
 USAGE = ("usage: python -m deflow_amd.save checkpoint=<ckpt> dataset_path=<dir of .h5 files> [res_name=<checkpoint file stem>] [scenes=a,b] "
          "[batch_size=] [num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [inference_dtype=fp32|bf16]")
-ICP_USAGE = ("usage: python -m deflow_amd.save model=icpflow dataset_path=<dir of .h5 files> [res_name=icpflow] [scenes=a,b] [batch_size=] "
-             "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
-             "[icp_eps=] [icp_min_points=] [icp_min_cluster_size=] [icp_min_side=] [icp_max_cluster_points=] [icp_vote_cap=] [icp_vote_bin=] "
-             "[icp_max_disp=] [icp_cap=] [icp_iters=] [icp_max_dist=] [icp_min_inlier_frac=] [icp_max_yaw=]")
-NSFP_USAGE = ("usage: python -m deflow_amd.save model=nsfp dataset_path=<dir of .h5 files> [res_name=nsfp] [scenes=a,b] [batch_size=2] "
-              "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
-              "[nsfp_depth=7] [nsfp_iters=1000] [nsfp_lr=8e-3] [nsfp_trunc_d2=4.0] [nsfp_patience=100] [nsfp_min_delta=1e-4] "
-              "[nsfp_check_every=50] [nsfp_seed=0] [nsfp_graph=false]\n"
-              "batch_size defaults to 2: the saved activations are (nsfp_depth + 1) x N x 512 bytes per net evaluation and sample")
-FASTNSF_USAGE = ("usage: python -m deflow_amd.save model=fastnsf dataset_path=<dir of .h5 files> [res_name=fastnsf] [scenes=a,b] [batch_size=4] "
-                 "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
-                 "[fastnsf_depth=7] [fastnsf_iters=1000] [fastnsf_lr=8e-3] [fastnsf_cell=0.1] [fastnsf_trunc=2.0] [fastnsf_patience=100] "
-                 "[fastnsf_min_delta=1e-4] [fastnsf_check_every=50] [fastnsf_seed=0] [fastnsf_graph=false]\n"
-                 "batch_size defaults to 4: per sample the distance-transform grid (2 bytes per voxel of point_cloud_range / fastnsf_cell, twice "
-                 "while it is built) and the saved activations, (fastnsf_depth + 1) x N x 512 bytes, twice during the backward")
-MBNSF_USAGE = ("usage: python -m deflow_amd.save model=mbnsf dataset_path=<dir of .h5 files> [res_name=mbnsf] [scenes=a,b] [batch_size=4] "
-               "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
-               "[mbnsf_depth=7] [mbnsf_iters=1000] [mbnsf_lr=8e-3] [mbnsf_cell=0.1] [mbnsf_trunc=2.0] [mbnsf_patience=100] "
-               "[mbnsf_min_delta=1e-4] [mbnsf_check_every=50] [mbnsf_seed=0] [mbnsf_graph=false] [mbnsf_rigid_weight=10.0] "
-               "[mbnsf_rigid_pairs=4] [mbnsf_rigid_delta=0.2] [mbnsf_eps=0.7] [mbnsf_min_points=4] [mbnsf_min_cluster_size=20] "
-               "[mbnsf_max_cluster_points=8192]\n"
-               "batch_size defaults to 4: model=fastnsf's memory per sample plus the neighbour table, N x 2 mbnsf_rigid_pairs x 8 bytes")
-FLOXELS_USAGE = ("usage: python -m deflow_amd.save model=floxels dataset_path=<dir of .h5 files> [res_name=floxels] [scenes=a,b] [batch_size=4] "
-                 "[num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [voxel_size=] [point_cloud_range=] "
-                 "[floxels_voxel=0.4] [floxels_smooth_weight=10.0] [floxels_iters=1000] [floxels_lr=0.05] [floxels_cell=0.1] "
-                 "[floxels_trunc=2.0] [floxels_patience=100] [floxels_min_delta=1e-4] [floxels_check_every=50] [floxels_graph=false]\n"
-                 "batch_size defaults to 4: per sample the distance-transform grid (2 bytes per voxel of point_cloud_range / floxels_cell, twice "
-                 "while it is built); the field and its five companions are 12 bytes per node of point_cloud_range / floxels_voxel each")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -91,15 +53,9 @@ def _flag(k: str, v: str) -> bool:
 def parse_args(argv: List[str]) -> Dict[str, Any]:
     """key=value arguments -> this command's own options, plus under ``_rest`` ({key: "key=value"}) the hyper-parameter overrides that
     ``eval.resolve_config`` lays over the checkpoint's configuration.  Reads no file."""
-    from . import fastnsf, floxels, mbnsf, nsfp
-    from .rigid import COMMAND_KEYS, params_from_command
     opt = dict(OWN_DEFAULTS)
     rest: Dict[str, str] = {}
-    icp: Dict[str, str] = {}
-    own_nsfp: Dict[str, str] = {}
-    own_fast: Dict[str, str] = {}
-    own_mb: Dict[str, str] = {}
-    own_flox: Dict[str, str] = {}
+    own: Dict[str, str] = {}            # the keys of the checkpoint-free pair models (deflow_amd/pairflow.py), whichever model's
     for a in argv:
         if "=" not in a:
             raise SystemExit(f"expected key=value, got {a!r}")
@@ -125,16 +81,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             if v not in ("fp32", "bf16"):
                 raise SystemExit(f"bad value for inference_dtype: {v!r} (fp32, bf16)")
             opt[k] = v
-        elif k in COMMAND_KEYS:
-            icp[k] = v
-        elif k in nsfp.COMMAND_KEYS:
-            own_nsfp[k] = v
-        elif k in fastnsf.COMMAND_KEYS:
-            own_fast[k] = v
-        elif k in mbnsf.COMMAND_KEYS:
-            own_mb[k] = v
-        elif k in floxels.COMMAND_KEYS:
-            own_flox[k] = v
+        elif pairflow.owner(k):
+            own[k] = v
         elif k in DEFAULTS or k in _TARGET_ALIASES or k == "model.target.grid_feature_size":
             if k in ("batch_size", "num_workers"):
                 try:
@@ -146,86 +94,25 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             rest[k] = f"{k}={v}"
         else:
             raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted(OWN_DEFAULTS))}, and the hyper-parameters of deflow_amd.train")
-    opt["icpflow"] = rest.get("model") == "model=icpflow" or rest.get("model.name") == "model.name=icpflow"
-    opt["nsfp"] = rest.get("model") == "model=nsfp" or rest.get("model.name") == "model.name=nsfp"
-    opt["fastnsf"] = rest.get("model") == "model=fastnsf" or rest.get("model.name") == "model.name=fastnsf"
-    opt["mbnsf"] = rest.get("model") == "model=mbnsf" or rest.get("model.name") == "model.name=mbnsf"
-    opt["floxels"] = rest.get("model") == "model=floxels" or rest.get("model.name") == "model.name=floxels"
-    if opt["floxels"]:
+    pair = pairflow.selected(rest, keys=("model", "model.name"))
+    opt["model"], opt["params"] = (pair.name if pair else None), None       # a model of pairflow.TABLE and its parameters, or None
+    wrong = pairflow.foreign_keys(own, pair)
+    if pair:
+        usage = pairflow.usage(pair)
         if opt["checkpoint"] or opt["inference_dtype"]:
-            raise SystemExit("model=floxels has no weights: it takes neither checkpoint= nor inference_dtype=\n" + FLOXELS_USAGE)
-        for wrong, owner in ((icp, "icpflow"), (own_nsfp, "nsfp"), (own_fast, "fastnsf"), (own_mb, "mbnsf")):
-            if wrong:
-                raise SystemExit(f"{', '.join(sorted(wrong))}: the {'icp' if owner == 'icpflow' else owner}_* keys belong to model={owner}\n" +
-                                 FLOXELS_USAGE)
+            raise SystemExit(f"model={pair.name} has no weights: it takes neither checkpoint= nor inference_dtype=\n" + usage)
+        if wrong:
+            raise SystemExit(wrong[1] + "\n" + usage)
         if not opt["dataset_path"]:
-            raise SystemExit(FLOXELS_USAGE)
+            raise SystemExit(usage)
         rest.pop("model", None), rest.pop("model.name", None)
-        rest.setdefault("batch_size", f"batch_size={floxels.COMMAND_BATCH_SIZE}")
-        opt["floxels_params"] = floxels.params_from_command(own_flox)
+        if pairflow.module(pair).COMMAND_BATCH_SIZE is not None:
+            rest.setdefault("batch_size", f"batch_size={pairflow.module(pair).COMMAND_BATCH_SIZE}")
+        opt["params"] = pairflow.params_from_command(pair, own)
         if opt["res_name"] is None:
-            opt["res_name"] = "floxels"
-    elif own_flox:
-        raise SystemExit(f"{', '.join(sorted(own_flox))}: the floxels_* keys belong to model=floxels\n" + FLOXELS_USAGE)
-    elif opt["mbnsf"]:
-        if opt["checkpoint"] or opt["inference_dtype"]:
-            raise SystemExit("model=mbnsf has no weights: it takes neither checkpoint= nor inference_dtype=\n" + MBNSF_USAGE)
-        if icp:
-            raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + MBNSF_USAGE)
-        if own_nsfp:
-            raise SystemExit(f"{', '.join(sorted(own_nsfp))}: the nsfp_* keys belong to model=nsfp\n" + MBNSF_USAGE)
-        if own_fast:
-            raise SystemExit(f"{', '.join(sorted(own_fast))}: the fastnsf_* keys belong to model=fastnsf\n" + MBNSF_USAGE)
-        if not opt["dataset_path"]:
-            raise SystemExit(MBNSF_USAGE)
-        rest.pop("model", None), rest.pop("model.name", None)
-        rest.setdefault("batch_size", f"batch_size={mbnsf.COMMAND_BATCH_SIZE}")
-        opt["mbnsf_params"] = mbnsf.params_from_command(own_mb)
-        if opt["res_name"] is None:
-            opt["res_name"] = "mbnsf"
-    elif own_mb:
-        raise SystemExit(f"{', '.join(sorted(own_mb))}: the mbnsf_* keys belong to model=mbnsf\n" + MBNSF_USAGE)
-    elif opt["fastnsf"]:
-        if opt["checkpoint"] or opt["inference_dtype"]:
-            raise SystemExit("model=fastnsf has no weights: it takes neither checkpoint= nor inference_dtype=\n" + FASTNSF_USAGE)
-        if icp:
-            raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + FASTNSF_USAGE)
-        if own_nsfp:
-            raise SystemExit(f"{', '.join(sorted(own_nsfp))}: the nsfp_* keys belong to model=nsfp\n" + FASTNSF_USAGE)
-        if not opt["dataset_path"]:
-            raise SystemExit(FASTNSF_USAGE)
-        rest.pop("model", None), rest.pop("model.name", None)
-        rest.setdefault("batch_size", f"batch_size={fastnsf.COMMAND_BATCH_SIZE}")
-        opt["fastnsf_params"] = fastnsf.params_from_command(own_fast)
-        if opt["res_name"] is None:
-            opt["res_name"] = "fastnsf"
-    elif own_fast:
-        raise SystemExit(f"{', '.join(sorted(own_fast))}: the fastnsf_* keys belong to model=fastnsf\n" + FASTNSF_USAGE)
-    elif opt["nsfp"]:
-        if opt["checkpoint"] or opt["inference_dtype"]:
-            raise SystemExit("model=nsfp has no weights: it takes neither checkpoint= nor inference_dtype=\n" + NSFP_USAGE)
-        if icp:
-            raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + NSFP_USAGE)
-        if not opt["dataset_path"]:
-            raise SystemExit(NSFP_USAGE)
-        rest.pop("model", None), rest.pop("model.name", None)
-        rest.setdefault("batch_size", f"batch_size={nsfp.COMMAND_BATCH_SIZE}")
-        opt["nsfp_params"] = nsfp.params_from_command(own_nsfp)
-        if opt["res_name"] is None:
-            opt["res_name"] = "nsfp"
-    elif own_nsfp:
-        raise SystemExit(f"{', '.join(sorted(own_nsfp))}: the nsfp_* keys belong to model=nsfp\n" + NSFP_USAGE)
-    elif opt["icpflow"]:
-        if opt["checkpoint"] or opt["inference_dtype"]:
-            raise SystemExit("model=icpflow has no weights: it takes neither checkpoint= nor inference_dtype=\n" + ICP_USAGE)
-        if not opt["dataset_path"]:
-            raise SystemExit(ICP_USAGE)
-        rest.pop("model", None), rest.pop("model.name", None)
-        opt["icp"] = params_from_command(icp)
-        if opt["res_name"] is None:
-            opt["res_name"] = "icpflow"
-    elif icp:
-        raise SystemExit(f"{', '.join(sorted(icp))}: the icp_* keys belong to model=icpflow\n" + ICP_USAGE)
+            opt["res_name"] = pair.name
+    elif wrong:
+        raise SystemExit(wrong[1] + "\n" + pairflow.usage(wrong[0]))
     elif not opt["checkpoint"] or not opt["dataset_path"]:
         raise SystemExit(USAGE)
     if opt["res_name"] is None:
@@ -345,42 +232,14 @@ def main(argv=None) -> int:
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
     d, res_name, online = opt["dataset_path"], opt["res_name"], opt["ground_source"] == "online"
-    if opt["icpflow"]:
+    pair = pairflow.entry(opt["model"])
+    if pair:
         # no checkpoint, no weights: the configuration is the defaults under the command line
-        from .rigid import IcpFlow
         cfg = parse_overrides(list(opt["_rest"].values()))
-        model = IcpFlow(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["icp"])
-        meta = {"res_name": res_name, "checkpoint": None, "model": "icpflow", "voxel_size": [float(v) for v in cfg["voxel_size"]],
+        model = pairflow.build(pair, cfg, opt["params"])
+        meta = {"res_name": res_name, "checkpoint": None, "model": pair.name, "voxel_size": [float(v) for v in cfg["voxel_size"]],
                 "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
-                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6j (UNPINNED)"}
-    elif opt["nsfp"]:
-        from .nsfp import Nsfp
-        cfg = parse_overrides(list(opt["_rest"].values()))
-        model = Nsfp(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["nsfp_params"])
-        meta = {"res_name": res_name, "checkpoint": None, "model": "nsfp", "voxel_size": [float(v) for v in cfg["voxel_size"]],
-                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
-                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6k (UNPINNED)"}
-    elif opt["fastnsf"]:
-        from .fastnsf import FastNsf
-        cfg = parse_overrides(list(opt["_rest"].values()))
-        model = FastNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["fastnsf_params"])
-        meta = {"res_name": res_name, "checkpoint": None, "model": "fastnsf", "voxel_size": [float(v) for v in cfg["voxel_size"]],
-                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
-                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6l (UNPINNED)"}
-    elif opt["floxels"]:
-        from .floxels import Floxels
-        cfg = parse_overrides(list(opt["_rest"].values()))
-        model = Floxels(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["floxels_params"])
-        meta = {"res_name": res_name, "checkpoint": None, "model": "floxels", "voxel_size": [float(v) for v in cfg["voxel_size"]],
-                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
-                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6n (UNPINNED)"}
-    elif opt["mbnsf"]:
-        from .mbnsf import MbNsf
-        cfg = parse_overrides(list(opt["_rest"].values()))
-        model = MbNsf(point_cloud_range=cfg["point_cloud_range"], voxel_size=cfg["voxel_size"], **opt["mbnsf_params"])
-        meta = {"res_name": res_name, "checkpoint": None, "model": "mbnsf", "voxel_size": [float(v) for v in cfg["voxel_size"]],
-                "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]], "ground_source": opt["ground_source"],
-                "half": bool(opt["half"]), "params": dict(model.params), "definition": "DESIGN.md 6f, 6m (UNPINNED)"}
+                "half": bool(opt["half"]), "params": dict(model.params), "definition": f"DESIGN.md 6f, {pair.section} (UNPINNED)"}
     else:
         cfg = resolve_config(opt["checkpoint"], opt["_rest"])
         model = build_model(cfg).to(dev)

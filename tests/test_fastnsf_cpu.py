@@ -149,10 +149,10 @@ def test_check_params_and_start():
 def test_save_arguments():
     from deflow_amd import fastnsf, save
     opt = save.parse_args(["model=fastnsf", "dataset_path=/d"])
-    assert opt["fastnsf"] and not opt["nsfp"] and not opt["icpflow"] and opt["res_name"] == "fastnsf" and opt["checkpoint"] is None
-    assert opt["fastnsf_params"] == fastnsf.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={fastnsf.COMMAND_BATCH_SIZE}"}
+    assert opt["model"] == "fastnsf" and opt["res_name"] == "fastnsf" and opt["checkpoint"] is None
+    assert opt["params"] == fastnsf.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={fastnsf.COMMAND_BATCH_SIZE}"}
     opt = save.parse_args(["model=fastnsf", "dataset_path=/d", "res_name=r", "fastnsf_iters=4", "fastnsf_cell=0.4", "fastnsf_graph=true", "batch_size=3"])
-    assert opt["res_name"] == "r" and opt["fastnsf_params"]["iters"] == 4 and opt["fastnsf_params"]["cell"] == 0.4 and opt["fastnsf_params"]["graph"]
+    assert opt["res_name"] == "r" and opt["params"]["iters"] == 4 and opt["params"]["cell"] == 0.4 and opt["params"]["graph"]
     assert opt["_rest"] == {"batch_size": "batch_size=3"}
     for argv, what in ((["model=fastnsf"], "usage: python -m deflow_amd.save model=fastnsf"),
                        (["model=fastnsf", "dataset_path=/d", "checkpoint=a.ckpt"], "has no weights"),
@@ -171,25 +171,26 @@ def test_save_arguments():
             save.parse_args(argv)
     # existing invocations are unchanged
     opt = save.parse_args(["checkpoint=/x/best.ckpt", "dataset_path=/d", "model=fastflow3d"])
-    assert not opt["fastnsf"] and not opt["nsfp"] and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
+    assert opt["model"] is None and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
     assert save.parse_args(["model=icpflow", "dataset_path=/d"])["_rest"] == {}
     assert save.parse_args(["model=nsfp", "dataset_path=/d"])["_rest"] == {"batch_size": "batch_size=2"}
 
 
 def test_eval_and_train_arguments():
-    from deflow_amd import eval as ev, fastnsf, train
-    cfg, params = ev.fastnsf_config({"model": "model=fastnsf", "dataset_path": "dataset_path=/r", "fastnsf_iters": "fastnsf_iters=20"})
+    from deflow_amd import eval as ev, pairflow, fastnsf, train
+    config = lambda given: pairflow.config(pairflow.entry("fastnsf"), given)
+    cfg, params = config({"model": "model=fastnsf", "dataset_path": "dataset_path=/r", "fastnsf_iters": "fastnsf_iters=20"})
     assert cfg["model"] == "fastnsf" and cfg["val_data"] == os.path.join("/r", "val") and cfg["batch_size"] == fastnsf.COMMAND_BATCH_SIZE
     assert params["iters"] == 20 and params["depth"] == 7
-    assert ev.fastnsf_config({"model": "model=fastnsf", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
+    assert config({"model": "model=fastnsf", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
     with pytest.raises(SystemExit, match="no checkpoint="):
-        ev.fastnsf_config({"model": "model=fastnsf", "checkpoint": "checkpoint=a.ckpt"})
+        config({"model": "model=fastnsf", "checkpoint": "checkpoint=a.ckpt"})
     with pytest.raises(SystemExit, match="belong to model=icpflow"):
-        ev.fastnsf_config({"model": "model=fastnsf", "icp_iters": "icp_iters=2"})
+        config({"model": "model=fastnsf", "icp_iters": "icp_iters=2"})
     with pytest.raises(SystemExit, match="belong to model=nsfp"):
-        ev.fastnsf_config({"model": "model=fastnsf", "nsfp_iters": "nsfp_iters=2"})
+        config({"model": "model=fastnsf", "nsfp_iters": "nsfp_iters=2"})
     with pytest.raises(SystemExit, match="patience"):
-        ev.fastnsf_config({"model": "model=fastnsf", "fastnsf_patience": "fastnsf_patience=0"})
+        config({"model": "model=fastnsf", "fastnsf_patience": "fastnsf_patience=0"})
     with pytest.raises(SystemExit, match="av2_mode=test is out of its scope.*deflow_amd.save model=fastnsf"):
         ev.main(["model=fastnsf", "av2_mode=test", "dataset_path=/r"])
     for argv in (["checkpoint=a.ckpt", "fastnsf_iters=3"], ["model=nsfp", "fastnsf_iters=3"], ["model=icpflow", "fastnsf_iters=3"]):

@@ -253,13 +253,13 @@ def test_check_params_and_keys():
 def test_save_arguments():
     from deflow_amd import floxels, save
     opt = save.parse_args(["model=floxels", "dataset_path=/d"])
-    assert opt["floxels"] and not opt["mbnsf"] and not opt["fastnsf"] and not opt["nsfp"] and not opt["icpflow"]
+    assert opt["model"] == "floxels"
     assert opt["res_name"] == "floxels" and opt["checkpoint"] is None
-    assert opt["floxels_params"] == floxels.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={floxels.COMMAND_BATCH_SIZE}"}
+    assert opt["params"] == floxels.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={floxels.COMMAND_BATCH_SIZE}"}
     opt = save.parse_args(["model=floxels", "dataset_path=/d", "res_name=r", "floxels_iters=4", "floxels_smooth_weight=3", "floxels_graph=true",
                            "batch_size=3"])
-    assert opt["res_name"] == "r" and opt["floxels_params"]["iters"] == 4 and opt["floxels_params"]["smooth_weight"] == 3.0
-    assert opt["floxels_params"]["graph"] and opt["_rest"] == {"batch_size": "batch_size=3"}
+    assert opt["res_name"] == "r" and opt["params"]["iters"] == 4 and opt["params"]["smooth_weight"] == 3.0
+    assert opt["params"]["graph"] and opt["_rest"] == {"batch_size": "batch_size=3"}
     for argv, what in ((["model=floxels"], "usage: python -m deflow_amd.save model=floxels"),
                        (["model=floxels", "dataset_path=/d", "checkpoint=a.ckpt"], "has no weights"),
                        (["model=floxels", "dataset_path=/d", "inference_dtype=bf16"], "has no weights"),
@@ -282,7 +282,7 @@ def test_save_arguments():
             save.parse_args(argv)
     # existing invocations are unchanged
     opt = save.parse_args(["checkpoint=/x/best.ckpt", "dataset_path=/d", "model=fastflow3d"])
-    assert not opt["floxels"] and not opt["mbnsf"] and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
+    assert opt["model"] is None and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
     assert save.parse_args(["model=icpflow", "dataset_path=/d"])["_rest"] == {}
     assert save.parse_args(["model=nsfp", "dataset_path=/d"])["_rest"] == {"batch_size": "batch_size=2"}
     assert save.parse_args(["model=fastnsf", "dataset_path=/d"])["res_name"] == "fastnsf"
@@ -290,20 +290,21 @@ def test_save_arguments():
 
 
 def test_eval_and_train_arguments():
-    from deflow_amd import eval as ev, floxels, train
-    cfg, params = ev.floxels_config({"model": "model=floxels", "dataset_path": "dataset_path=/r", "floxels_iters": "floxels_iters=20"})
+    from deflow_amd import eval as ev, pairflow, floxels, train
+    config = lambda given: pairflow.config(pairflow.entry("floxels"), given)
+    cfg, params = config({"model": "model=floxels", "dataset_path": "dataset_path=/r", "floxels_iters": "floxels_iters=20"})
     assert cfg["model"] == "floxels" and cfg["val_data"] == os.path.join("/r", "val") and cfg["batch_size"] == floxels.COMMAND_BATCH_SIZE
     assert params["iters"] == 20 and params["voxel"] == 0.4 and params["smooth_weight"] == 10.0
-    assert ev.floxels_config({"model": "model=floxels", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
+    assert config({"model": "model=floxels", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
     with pytest.raises(SystemExit, match="no checkpoint="):
-        ev.floxels_config({"model": "model=floxels", "checkpoint": "checkpoint=a.ckpt"})
+        config({"model": "model=floxels", "checkpoint": "checkpoint=a.ckpt"})
     with pytest.raises(SystemExit, match="no inference_dtype="):
-        ev.floxels_config({"model": "model=floxels", "inference_dtype": "inference_dtype=bf16"})
+        config({"model": "model=floxels", "inference_dtype": "inference_dtype=bf16"})
     for key, owner in (("icp_iters", "icpflow"), ("nsfp_iters", "nsfp"), ("fastnsf_iters", "fastnsf"), ("mbnsf_iters", "mbnsf")):
         with pytest.raises(SystemExit, match=f"{key}: the {key.split('_')[0]}_\\* keys belong to model={owner}"):
-            ev.floxels_config({"model": "model=floxels", key: f"{key}=2"})
+            config({"model": "model=floxels", key: f"{key}=2"})
     with pytest.raises(SystemExit, match="voxel"):
-        ev.floxels_config({"model": "model=floxels", "floxels_voxel": "floxels_voxel=0"})
+        config({"model": "model=floxels", "floxels_voxel": "floxels_voxel=0"})
     with pytest.raises(SystemExit, match="model=floxels writes no leaderboard submission \\(av2_mode=test is out of its scope\\).*deflow_amd.save model=floxels"):
         ev.main(["model=floxels", "av2_mode=test", "dataset_path=/r"])
     for argv in (["checkpoint=a.ckpt", "floxels_iters=3"], ["model=nsfp", "floxels_iters=3"], ["model=icpflow", "floxels_iters=3"],

@@ -174,10 +174,10 @@ def test_check_params_and_keys():
 def test_save_arguments():
     from deflow_amd import mbnsf, save
     opt = save.parse_args(["model=mbnsf", "dataset_path=/d"])
-    assert opt["mbnsf"] and not opt["fastnsf"] and not opt["nsfp"] and not opt["icpflow"] and opt["res_name"] == "mbnsf" and opt["checkpoint"] is None
-    assert opt["mbnsf_params"] == mbnsf.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={mbnsf.COMMAND_BATCH_SIZE}"}
+    assert opt["model"] == "mbnsf" and opt["res_name"] == "mbnsf" and opt["checkpoint"] is None
+    assert opt["params"] == mbnsf.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={mbnsf.COMMAND_BATCH_SIZE}"}
     opt = save.parse_args(["model=mbnsf", "dataset_path=/d", "res_name=r", "mbnsf_iters=4", "mbnsf_rigid_weight=3", "mbnsf_graph=true", "batch_size=3"])
-    assert opt["res_name"] == "r" and opt["mbnsf_params"]["iters"] == 4 and opt["mbnsf_params"]["rigid_weight"] == 3.0 and opt["mbnsf_params"]["graph"]
+    assert opt["res_name"] == "r" and opt["params"]["iters"] == 4 and opt["params"]["rigid_weight"] == 3.0 and opt["params"]["graph"]
     assert opt["_rest"] == {"batch_size": "batch_size=3"}
     for argv, what in ((["model=mbnsf"], "usage: python -m deflow_amd.save model=mbnsf"),
                        (["model=mbnsf", "dataset_path=/d", "checkpoint=a.ckpt"], "has no weights"),
@@ -199,30 +199,31 @@ def test_save_arguments():
             save.parse_args(argv)
     # existing invocations are unchanged
     opt = save.parse_args(["checkpoint=/x/best.ckpt", "dataset_path=/d", "model=fastflow3d"])
-    assert not opt["mbnsf"] and not opt["fastnsf"] and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
+    assert opt["model"] is None and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
     assert save.parse_args(["model=icpflow", "dataset_path=/d"])["_rest"] == {}
     assert save.parse_args(["model=nsfp", "dataset_path=/d"])["_rest"] == {"batch_size": "batch_size=2"}
     assert save.parse_args(["model=fastnsf", "dataset_path=/d"])["res_name"] == "fastnsf"
 
 
 def test_eval_and_train_arguments():
-    from deflow_amd import eval as ev, mbnsf, train
-    cfg, params = ev.mbnsf_config({"model": "model=mbnsf", "dataset_path": "dataset_path=/r", "mbnsf_iters": "mbnsf_iters=20"})
+    from deflow_amd import eval as ev, pairflow, mbnsf, train
+    config = lambda given: pairflow.config(pairflow.entry("mbnsf"), given)
+    cfg, params = config({"model": "model=mbnsf", "dataset_path": "dataset_path=/r", "mbnsf_iters": "mbnsf_iters=20"})
     assert cfg["model"] == "mbnsf" and cfg["val_data"] == os.path.join("/r", "val") and cfg["batch_size"] == mbnsf.COMMAND_BATCH_SIZE
     assert params["iters"] == 20 and params["depth"] == 7 and params["rigid_weight"] == 10.0
-    assert ev.mbnsf_config({"model": "model=mbnsf", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
+    assert config({"model": "model=mbnsf", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
     with pytest.raises(SystemExit, match="no checkpoint="):
-        ev.mbnsf_config({"model": "model=mbnsf", "checkpoint": "checkpoint=a.ckpt"})
+        config({"model": "model=mbnsf", "checkpoint": "checkpoint=a.ckpt"})
     with pytest.raises(SystemExit, match="no inference_dtype="):
-        ev.mbnsf_config({"model": "model=mbnsf", "inference_dtype": "inference_dtype=bf16"})
+        config({"model": "model=mbnsf", "inference_dtype": "inference_dtype=bf16"})
     with pytest.raises(SystemExit, match="icp_iters: the icp_\\* keys belong to model=icpflow"):
-        ev.mbnsf_config({"model": "model=mbnsf", "icp_iters": "icp_iters=2"})
+        config({"model": "model=mbnsf", "icp_iters": "icp_iters=2"})
     with pytest.raises(SystemExit, match="nsfp_iters: the nsfp_\\* keys belong to model=nsfp"):
-        ev.mbnsf_config({"model": "model=mbnsf", "nsfp_iters": "nsfp_iters=2"})
+        config({"model": "model=mbnsf", "nsfp_iters": "nsfp_iters=2"})
     with pytest.raises(SystemExit, match="fastnsf_iters: the fastnsf_\\* keys belong to model=fastnsf"):
-        ev.mbnsf_config({"model": "model=mbnsf", "fastnsf_iters": "fastnsf_iters=2"})
+        config({"model": "model=mbnsf", "fastnsf_iters": "fastnsf_iters=2"})
     with pytest.raises(SystemExit, match="rigid_delta"):
-        ev.mbnsf_config({"model": "model=mbnsf", "mbnsf_rigid_delta": "mbnsf_rigid_delta=0"})
+        config({"model": "model=mbnsf", "mbnsf_rigid_delta": "mbnsf_rigid_delta=0"})
     with pytest.raises(SystemExit, match="model=mbnsf writes no leaderboard submission \\(av2_mode=test is out of its scope\\).*deflow_amd.save model=mbnsf"):
         ev.main(["model=mbnsf", "av2_mode=test", "dataset_path=/r"])
     for argv in (["checkpoint=a.ckpt", "mbnsf_iters=3"], ["model=nsfp", "mbnsf_iters=3"], ["model=icpflow", "mbnsf_iters=3"],

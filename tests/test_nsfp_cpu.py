@@ -123,12 +123,12 @@ def test_check_params():
 
 # ---- the commands' keys and refusals --------------------------------------------------------------------------------------------------
 def test_save_arguments():
-    from deflow_amd import nsfp, save
+    from deflow_amd import nsfp, pairflow, save
     opt = save.parse_args(["model=nsfp", "dataset_path=/d"])
-    assert opt["nsfp"] and not opt["icpflow"] and opt["res_name"] == "nsfp" and opt["checkpoint"] is None
-    assert opt["nsfp_params"] == nsfp.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={nsfp.COMMAND_BATCH_SIZE}"}
+    assert opt["model"] == "nsfp" and opt["res_name"] == "nsfp" and opt["checkpoint"] is None
+    assert opt["params"] == nsfp.DEFAULTS and opt["_rest"] == {"batch_size": f"batch_size={nsfp.COMMAND_BATCH_SIZE}"}
     opt = save.parse_args(["model=nsfp", "dataset_path=/d", "res_name=r", "nsfp_iters=4", "nsfp_depth=2", "nsfp_graph=true", "batch_size=3"])
-    assert opt["res_name"] == "r" and opt["nsfp_params"]["iters"] == 4 and opt["nsfp_params"]["depth"] == 2 and opt["nsfp_params"]["graph"]
+    assert opt["res_name"] == "r" and opt["params"]["iters"] == 4 and opt["params"]["depth"] == 2 and opt["params"]["graph"]
     assert opt["_rest"] == {"batch_size": "batch_size=3"}
     for argv, what in ((["model=nsfp"], "usage: python -m deflow_amd.save model=nsfp"),
                        (["model=nsfp", "dataset_path=/d", "checkpoint=a.ckpt"], "has no weights"),
@@ -142,25 +142,26 @@ def test_save_arguments():
                        (["model=nsfp", "dataset_path=/d", "av2_mode=test"], "takes no av2_mode")):
         with pytest.raises(SystemExit, match=what):
             save.parse_args(argv)
-    assert "512 bytes" in save.NSFP_USAGE
+    assert "512 bytes" in pairflow.usage(pairflow.entry("nsfp"))
     # existing invocations are unchanged
     opt = save.parse_args(["checkpoint=/x/best.ckpt", "dataset_path=/d", "model=fastflow3d"])
-    assert not opt["nsfp"] and not opt["icpflow"] and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
+    assert opt["model"] is None and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
     assert save.parse_args(["model=icpflow", "dataset_path=/d"])["_rest"] == {}
 
 
 def test_eval_and_train_arguments():
-    from deflow_amd import eval as ev, nsfp, train
-    cfg, params = ev.nsfp_config({"model": "model=nsfp", "dataset_path": "dataset_path=/r", "nsfp_iters": "nsfp_iters=20"})
+    from deflow_amd import eval as ev, pairflow, nsfp, train
+    config = lambda given: pairflow.config(pairflow.entry("nsfp"), given)
+    cfg, params = config({"model": "model=nsfp", "dataset_path": "dataset_path=/r", "nsfp_iters": "nsfp_iters=20"})
     assert cfg["model"] == "nsfp" and cfg["val_data"] == os.path.join("/r", "val") and cfg["batch_size"] == nsfp.COMMAND_BATCH_SIZE
     assert params["iters"] == 20 and params["depth"] == 7
-    assert ev.nsfp_config({"model": "model=nsfp", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
+    assert config({"model": "model=nsfp", "batch_size": "batch_size=5"})[0]["batch_size"] == 5
     with pytest.raises(SystemExit, match="no checkpoint="):
-        ev.nsfp_config({"model": "model=nsfp", "checkpoint": "checkpoint=a.ckpt"})
+        config({"model": "model=nsfp", "checkpoint": "checkpoint=a.ckpt"})
     with pytest.raises(SystemExit, match="belong to model=icpflow"):
-        ev.nsfp_config({"model": "model=nsfp", "icp_iters": "icp_iters=2"})
+        config({"model": "model=nsfp", "icp_iters": "icp_iters=2"})
     with pytest.raises(SystemExit, match="patience"):
-        ev.nsfp_config({"model": "model=nsfp", "nsfp_patience": "nsfp_patience=0"})
+        config({"model": "model=nsfp", "nsfp_patience": "nsfp_patience=0"})
     with pytest.raises(SystemExit, match="av2_mode=test is out of its scope.*deflow_amd.save model=nsfp"):   # names the alternative
         ev.main(["model=nsfp", "av2_mode=test", "dataset_path=/r"])
     with pytest.raises(SystemExit, match="belong to model=nsfp"):

@@ -139,10 +139,10 @@ def test_entry_points_reject_bad_arguments_without_launching():
 def test_save_arguments():
     from deflow_amd import rigid, save
     opt = save.parse_args(["model=icpflow", "dataset_path=/d"])
-    assert opt["icpflow"] and opt["res_name"] == "icpflow" and opt["checkpoint"] is None and opt["icp"] == rigid.DEFAULTS and opt["_rest"] == {}
+    assert opt["model"] == "icpflow" and opt["res_name"] == "icpflow" and opt["checkpoint"] is None and opt["params"] == rigid.DEFAULTS and opt["_rest"] == {}
     opt = save.parse_args(["model=icpflow", "dataset_path=/d", "res_name=r", "icp_vote_bin=0.25", "icp_iters=4", "icp_min_side=10",
                            "ground_source=online", "point_cloud_range=[-6.4,-6.4,-3,6.4,6.4,3]", "batch_size=2"])
-    assert opt["res_name"] == "r" and opt["icp"]["vote_bin"] == 0.25 and opt["icp"]["icp_iters"] == 4 and opt["icp"]["min_side"] == 10
+    assert opt["res_name"] == "r" and opt["params"]["vote_bin"] == 0.25 and opt["params"]["icp_iters"] == 4 and opt["params"]["min_side"] == 10
     assert sorted(opt["_rest"]) == ["batch_size", "point_cloud_range"] and opt["ground_source"] == "online"
     assert set(rigid.COMMAND_KEYS) == {"icp_eps", "icp_min_points", "icp_min_cluster_size", "icp_min_side", "icp_max_cluster_points",
                                        "icp_vote_cap", "icp_vote_bin", "icp_max_disp", "icp_cap", "icp_iters", "icp_max_dist",
@@ -159,19 +159,20 @@ def test_save_arguments():
             save.parse_args(argv)
     # existing invocations are unchanged
     opt = save.parse_args(["checkpoint=/x/best.ckpt", "dataset_path=/d", "model=fastflow3d"])
-    assert not opt["icpflow"] and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
+    assert opt["model"] is None and opt["res_name"] == "best" and opt["_rest"] == {"model": "model=fastflow3d"}
 
 
 def test_eval_and_train_arguments():
-    from deflow_amd import eval as ev, rigid, train
-    cfg, params = ev.icpflow_config({"model": "model=icpflow", "dataset_path": "dataset_path=/r", "icp_max_yaw": "icp_max_yaw=0.2",
+    from deflow_amd import eval as ev, pairflow, rigid, train
+    config = lambda given: pairflow.config(pairflow.entry("icpflow"), given)
+    cfg, params = config({"model": "model=icpflow", "dataset_path": "dataset_path=/r", "icp_max_yaw": "icp_max_yaw=0.2",
                                      "batch_size": "batch_size=2"})
     assert cfg["model"] == "icpflow" and cfg["val_data"] == os.path.join("/r", "val") and cfg["batch_size"] == 2
     assert params["max_yaw"] == 0.2 and params["vote_bin"] == rigid.DEFAULTS["vote_bin"]
     with pytest.raises(SystemExit, match="no checkpoint="):
-        ev.icpflow_config({"model": "model=icpflow", "checkpoint": "checkpoint=a.ckpt"})
+        config({"model": "model=icpflow", "checkpoint": "checkpoint=a.ckpt"})
     with pytest.raises(SystemExit, match="min_inlier_frac"):
-        ev.icpflow_config({"model": "model=icpflow", "icp_min_inlier_frac": "icp_min_inlier_frac=-1"})
+        config({"model": "model=icpflow", "icp_min_inlier_frac": "icp_min_inlier_frac=-1"})
     with pytest.raises(SystemExit, match="av2_mode=test is out of its scope"):            # refused before anything touches a GPU
         ev.main(["model=icpflow", "av2_mode=test", "dataset_path=/r"])
     with pytest.raises(SystemExit, match="unknown model 'icpflow'"):                      # the trainer has nothing to train there
