@@ -208,6 +208,9 @@ _SIGS = {
     "df_vox_sample": [P, P, P, I, I, I, I, I, P, P],
     "df_vox_scatter": [P, P, P, P, I, I, I, I, I, P, P],
     "df_vox_smooth": [P, P, I, I, I, I, P, P, P],
+    "df_refine_fit": [P, P, P, P, P, I, I, I, I, I, I, F, F, F, F, F, F, F, P, P, P],
+    "df_refine_score": [P, P, P, P, P, P, P, P, I, I, I, F, F, P, P],
+    "df_refine_apply": [P, P, P, P, P, P, I, I, I, P, P, P],
     "df_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
     "df_adam_step_dev": [P, P, P, P, L, F, F, F, F, P, F, P],
 }

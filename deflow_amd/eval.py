@@ -167,7 +167,9 @@ def main_test(argv: List[str]) -> Dict[str, Any]:
     return result
 
 
-def main(argv=None):
+def main(argv=None, wrap=None):
+    # wrap: optional callable (model, None) -> model, applied to the finished model before the first batch (python -m deflow_amd.refine
+    # eval passes one); without it the command is what it was
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
@@ -218,6 +220,8 @@ def main(argv=None):
         model.eval()
         if "inference_dtype" in given:
             model.inference_dtype = given["inference_dtype"].split("=", 1)[1]
+    if wrap is not None:
+        model = wrap(model, None)
     B = int(cfg["batch_size"])
     if cfg["val_data"] != "synthetic":
         from .data import HDF5Dataset, SceneLoader, ShardedSampler

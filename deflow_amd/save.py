@@ -223,7 +223,9 @@ def save_scene(sweep_flow_for, pairs: ScenePairs, batch_size: int, device, *, ha
     return out
 
 
-def main(argv=None) -> int:
+def main(argv=None, wrap=None) -> int:
+    """wrap: optional callable (model, meta) -> model, applied to the finished model before any sweep runs; it may amend the flow file's
+    meta (``python -m deflow_amd.refine save`` passes one).  Without it the command is what it was."""
     opt = parse_args(list(sys.argv[1:] if argv is None else argv))
     assert torch.cuda.is_available(), "the save command runs on the HIP engine only"
     from .eval import resolve_config
@@ -253,7 +255,9 @@ def main(argv=None) -> int:
         meta = {"res_name": res_name, "checkpoint": os.path.basename(opt["checkpoint"]), "model": cfg["model"],
                 "voxel_size": [float(v) for v in cfg["voxel_size"]], "point_cloud_range": [float(v) for v in cfg["point_cloud_range"]],
                 "ground_source": opt["ground_source"], "half": bool(opt["half"]), "definition": "DESIGN.md 6f (UNPINNED)"}
-    scenes = opt["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
+    if wrap is not None:
+        model = wrap(model, meta)
+    scenes =opt["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
     flows_for: Dict[int, SweepFlow] = {}
 
     def sweep_flow_for(B: int) -> SweepFlow:

@@ -1082,6 +1082,63 @@ int df_vox_scatter(const float* dF, const float* frac, const int32_t* idx_sorted
                    int VZ, float* dtheta, void* stream);
 int df_vox_smooth(const float* theta, const uint8_t* active, int B, int VX, int VY, int VZ, float* v, float* g, void* stream);
 
+/* ------------------------------------------------------------------ per-cluster rigid snap of a model's flow (the refine command) ----
+ * UNPINNED: the recipe follows the rigid refinement of Chodosh et al., "Re-evaluating LiDAR scene flow" (WACV'24) -- cluster the first
+ * sweep, fit one robust rigid motion per cluster to the flow a model produced, give the rows of an accepted cluster that motion -- but no
+ * upstream source was read and every choice below is this project's own.  Lengths in metres; fp32(.) is one
+ * correctly rounded operation, no contraction.  Per sample: x [Nc,3] (the decoded rows of the ego-compensated first sweep, compacted),
+ * f [Nc,3] (the model's residual flow of those rows), count their valid leading rows (clamped to [0, Nc]).
+ *   a. clusters  labels [B,Nc] i32: df_dbscan_* with eps = 0.7, min_points = 4, min_cluster_size = 20 over x (0 = none, 1..K); the labels
+ *                of rows >= count set to 0.  Slot k = label - 1 < Kcap = max(Nc / min_cluster_size, 1).  Lists: seg_off [B, 2 Kcap + 1] and
+ *                seg_rows [B, Nc + 1] are df_rigid_segments' output for N0 = Nc, N1 = 1 on the labels followed by one column of zeros:
+ *                list 2k = the rows of cluster k + 1 in ascending order.
+ *   b. rows      a row of a list TAKES PART when it is < count and its x and f are finite.  Status, tested in this order: 0 no rows in the
+ *                list; 3 more than max_cluster_points (8192) rows in the list (they are not read); 2 fewer than min_rows (8) rows take part.
+ *   c. fit       yaw + translation, iteratively re-weighted least squares with Huber weights.  Anchor a = the list's first row that takes
+ *                part; s = fp32(x - a), d = fp32(s + f).  w = 1 in the first fit; exactly iters (4) re-weightings, iters + 1 fits.  One fit:
+ *                W = sum w, ms = sum(fp32(w s)) / W, md = sum(fp32(w d)) / W, u = fp32(s - ms), v = fp32(d - md),
+ *                theta = atan2f(sum fp32(w fp32(fp32(u.x v.y) - fp32(u.y v.x))), sum fp32(w fp32(fp32(u.x v.x) + fp32(u.y v.y)))),
+ *                t = md - Rz(theta) ms with c = cosf(theta), s = sinf(theta): t.x = fp32(md.x - fp32(fp32(c ms.x) - fp32(s ms.y))),
+ *                t.y = fp32(md.y - fp32(fp32(s ms.x) + fp32(c ms.y))), t.z = fp32(md.z - ms.z).  Residual of a row under a fit:
+ *                p.x = fp32(fp32(fp32(c s.x) - fp32(s s.y)) + t.x), p.y = fp32(fp32(fp32(s s.x) + fp32(c s.y)) + t.y), p.z = fp32(s.z + t.z),
+ *                e = fp32(p - d), r2 = fp32(fp32(fp32(e.x e.x) + fp32(e.y e.y)) + fp32(e.z e.z)), r = sqrt(r2) correctly rounded.  The next
+ *                fit's w = 1 for r <= delta (0.1), else fp32(delta / r) (0 when r is not finite).  After the last fit, from its residuals:
+ *                inlier_frac = fp32(#(r <= inlier_dist (0.2)) / rows that take part), rms = sqrt(fp32(sum r2 / rows that take part)).
+ *                Every sum runs in a fixed order: thread t of 256 adds the list positions t, t + 256, ... in ascending order, the 64 lanes
+ *                of a wave are added in an xor butterfly (32, 16, ..., 1), then waves 0..3 in order.  Two calls are bit-identical, and a
+ *                slot's result depends neither on B nor on the other samples or slots.
+ *   d. accept    status 4 unless inlier_frac >= min_inlier_frac (0.5); else 5 unless |theta| <= max_yaw (0.35) and disp <= max_disp (3.4),
+ *                disp = |Rz(theta) c + t - c| for the unweighted centroid c = sum(s) / rows of the rows that take part (z: t.z), products
+ *                and sums rounded one by one, the root correctly rounded; else 6 (static) when disp <= static_disp (0.05) and |theta| <=
+ *                static_yaw (0.02): theta and t are then written as 0, the identity; else 1.
+ *   e. check     with f' the flow that (f) would write: d2_before / d2_after [B,Nc] = df_chamfer_nn's squared distances of x + f and
+ *                x + f' to the second sweep, max_dist2 = check_trunc^2 (check_trunc 2.0).  Per slot of status 1 or 6, c_before / c_after =
+ *                fp32(sum / rows) over the rows that take part of min(sqrt(d2), check_trunc), check_trunc for a row without a neighbour
+ *                (inf, NaN, d2 > check_trunc^2), summed in the order of (c).  c_after > fp32(c_before + check_tol) (0.05) turns the status
+ *                into 7 and the slot is left alone.  A sample with count1 <= 0 (no second sweep): every slot passes, c_before = c_after = 0.
+ *   f. rows      a row that takes part in a status-1 slot: flow = (fp32(p.x - s.x), fp32(p.y - s.y), t.z), p as in (c); in a status-6 slot:
+ *                flow = 0; rigid_id = its label for both.  EVERY other row -- label 0 or outside 1..Kcap, another status, rows that do not
+ *                take part, rows >= count -- keeps f bit for bit (NaN payloads included) and gets rigid_id = 0.
+ * df_refine_fit: -> table [B,Kcap,12] f32 = (theta, tx, ty, tz, inlier_frac, rms, rows used, status, c_before = 0, c_after = 0, 0, 0); the
+ *   first six are 0 for status 0, 2, 3; rows used = the rows that take part (status 3: the list's length); anchor [B,Kcap] i32 = the
+ *   anchor's row, -1 without one.  Every element of both is written.  One workgroup per (sample, slot), rows re-read from global memory in
+ *   every pass, no workspace.
+ * df_refine_score: d2_before, d2_after, count1 [B] i32 -> table columns 8, 9 and the status by (e); the other columns are not touched.
+ * df_refine_apply: table, anchor -> flow_out [B,Nc,3] f32, rigid_id [B,Nc] i32, every element written exactly once.  It serves both the
+ *   provisional f' of (e) and the final output.
+ * B outside 1..65535, Nc < 1, B Nc >= 2^31: DF_E_SHAPE.  NULL pointers, Kcap outside [1, Nc], iters outside [0, 64], min_rows or
+ * max_cluster_points < 1, a delta / inlier_dist / check_trunc that is not positive and finite, any other threshold negative or not finite:
+ * DF_E_ARG.  Buffers not 4-byte aligned: DF_E_ALIGN.  No launch then.  Grids come from B, Nc and Kcap only, never from a device value; no
+ * float atomics; the entries never allocate or synchronise and read nothing back. */
+int df_refine_fit(const float* x, const float* flow, const int32_t* count, const int32_t* seg_off, const int32_t* seg_rows, int B, int Nc,
+                  int Kcap, int min_rows, int max_cluster_points, int iters, float delta, float inlier_dist, float min_inlier_frac,
+                  float max_yaw, float max_disp, float static_disp, float static_yaw, float* table, int32_t* anchor, void* stream);
+int df_refine_score(const float* x, const float* flow, const int32_t* count, const int32_t* count1, const int32_t* seg_off,
+                    const int32_t* seg_rows, const float* d2_before, const float* d2_after, int B, int Nc, int Kcap, float check_trunc,
+                    float check_tol, float* table, void* stream);
+int df_refine_apply(const float* x, const float* flow, const int32_t* count, const int32_t* labels, const float* table,
+                    const int32_t* anchor, int B, int Nc, int Kcap, float* flow_out, int32_t* rigid_id, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */
