@@ -4,22 +4,23 @@ time against a lookup in the truncated distance transform of the second sweep, w
 UNPINNED: the recipe is FastNSF's (Li, Zheng & Lucey, ICCV'23) -- the target sweep is turned once into a distance-transform grid, the loss
 is a lookup in it, there is no inverse net and no per-iteration search -- but upstream's source is absent, and every choice here is this
 project's own.  The definition is in DESIGN.md section 6l and include/deflow_amd.h; tests/helpers/dt_ref.py restates it in torch.  The
-transform and its lookup run on csrc/dt.hip, the MLP on csrc/mlp.hip (``deflow_amd.nsfp``'s wrappers), the update on df_adam_step_dev.
+transform and its lookup run on csrc/dt.hip, the MLP on csrc/mlp.hip (``deflow_amd.nsfp``'s wrappers); the loop, its snapshot and freeze
+and its Adam update are ``deflow_amd.pairopt``'s.  ``DataTerm`` and ``optimize_net`` are shared with ``mbnsf`` and ``floxels``.
 
-CUDA tensors only, like the rest of the library: there is no CPU fallback.  The loop makes no host decision (``nsfp``'s snapshot and
-freeze, on the device), so one iteration can be captured as a HIP graph (``graph=True``)."""
+CUDA tensors only, like the rest of the library: there is no CPU fallback.  The loop makes no host decision, so one iteration can be
+captured as a HIP graph (``graph=True``)."""
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
 from . import pairflow
 from ._lib import call, ptr, stream
-from .nsfp import (BETAS, EPS, MAX_DEPTH, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze, init_params, mlp_backward, mlp_forward,
-                   param_stride)
-from .pairflow import PairFlowModel, _tensor
+from .nsfp import MAX_DEPTH, init_params, mlp_backward, mlp_forward, param_stride
+from .pairflow import _tensor
+from .pairopt import Loop, OptimisedPairModel, mean_and_weight, pair_clouds, rows
 
 R_MAX = 255
 LINE_TILE = 256          # x positions per workgroup of the transform's passes (csrc/dt.hip: DT_TILE)
@@ -34,41 +35,31 @@ COMMAND_KEYS: Dict[str, str] = {"fastnsf_" + k: k for k in DEFAULTS}
 COMMAND_BATCH_SIZE = 4
 
 
-def _f32(v: float) -> float:
+def f32(v: float) -> float:
     return float(torch.tensor(float(v), dtype=torch.float32))
 
 
-def dt_grid(grid_range: Sequence[float], cell: float, trunc: float):
+def dt_grid(grid_range: Sequence[float], cell: float, trunc: float, fn: str = "dt_grid"):
     """(minx, miny, minz, maxx, maxy, maxz), cell, trunc -> origin (3 floats, as fp32 holds them), dims (GX, GY, GZ), R.
     R = round(trunc / cell) voxels, G_a = ceil((max_a - min_a) / cell) + 2 R, origin_a = min_a - R cell: a position within trunc of an
-    in-range point is inside the grid.  ValueError names the argument.  Launches nothing."""
+    in-range point is inside the grid.  ValueError names the argument, against ``fn``.  Launches nothing."""
     if len(grid_range) != 6 or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in grid_range):
-        raise ValueError(f"dt_grid: grid_range must be 6 finite values (minx, miny, minz, maxx, maxy, maxz), got {grid_range!r}")
+        raise ValueError(f"{fn}: grid_range must be 6 finite values (minx, miny, minz, maxx, maxy, maxz), got {grid_range!r}")
     for name, v in (("cell", cell), ("trunc", trunc)):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0):
-            raise ValueError(f"dt_grid: {name} must be positive and finite, got {v!r}")
+            raise ValueError(f"{fn}: {name} must be positive and finite, got {v!r}")
     cell, trunc = float(cell), float(trunc)
     R = int(round(trunc / cell))
     if not 1 <= R <= R_MAX or abs(R * cell - trunc) > 1e-6 * trunc:
-        raise ValueError(f"dt_grid: trunc must be a whole number of cells, 1 to {R_MAX} of them, got trunc = {trunc}, cell = {cell}")
+        raise ValueError(f"{fn}: trunc must be a whole number of cells, 1 to {R_MAX} of them, got trunc = {trunc}, cell = {cell}")
     r = [float(v) for v in grid_range]
     if not all(r[3 + a] > r[a] for a in range(3)):
-        raise ValueError(f"dt_grid: grid_range is empty: {grid_range!r}")
+        raise ValueError(f"{fn}: grid_range is empty: {grid_range!r}")
     dims = tuple(int(math.ceil((r[3 + a] - r[a]) / cell - 1e-6)) + 2 * R for a in range(3))      # (102.4 / 0.1 is 1024 + 1e-13)
     if math.prod(dims) >= 2 ** 31:
-        raise ValueError(f"dt_grid: grid_range / cell: {dims[0]} x {dims[1]} x {dims[2]} voxels do not fit 31 bits")
-    origin = tuple(_f32(r[a] - R * cell) for a in range(3))
+        raise ValueError(f"{fn}: grid_range / cell: {dims[0]} x {dims[1]} x {dims[2]} voxels do not fit 31 bits")
+    origin = tuple(f32(r[a] - R * cell) for a in range(3))
     return origin, dims, R
-
-
-def _rows(fn: str, name: str, t) -> Tuple[int, int]:
-    _tensor(fn, name, t, torch.float32)
-    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{fn}: {name} must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got {tuple(t.shape)}")
-    B, N = int(t.shape[0]), int(t.shape[1])
-    if B > 65535 or 3 * B * N >= 2 ** 31:
-        raise ValueError(f"{fn}: {name}: 1 <= B <= 65535 and 3 * B * N < 2^31 expected, got B = {B}, N = {N}")
-    return B, N
 
 
 def _grid_args(fn: str, origin, cell, dims, radius):
@@ -85,7 +76,7 @@ def _grid_args(fn: str, origin, cell, dims, radius):
 def dt_build(ref: torch.Tensor, count: torch.Tensor, *, origin: Sequence[float], cell: float, dims: Sequence[int], radius: int) -> torch.Tensor:
     """ref [B,N,3] f32 with count [B] i32 valid leading rows -> dt2 [B,GZ,GY,GX] u16: min(R^2, squared distance in voxels to the nearest
     occupied voxel of the sample).  Exact (integers); two calls are bit-identical; no host synchronisation."""
-    B, N = _rows("dt_build", "ref", ref)
+    B, N = rows("dt_build", "ref", ref)
     _tensor("dt_build", "count", count, torch.int32, (B,), ref.device)
     _grid_args("dt_build", origin, cell, dims, radius)
     GX, GY, GZ = dims
@@ -105,7 +96,7 @@ def dt_lookup(query: torch.Tensor, count: torch.Tensor, dt2: torch.Tensor, *, or
     gradient; 0 on an axis whose position was clamped), and with return_cells also cells [B,N,3] i32 (the lower corner used) and clamped
     [B,N] u8 (bit a: axis a was clamped).  Rows behind the count: 0; counted non-finite rows: d = radius * cell, g = 0.  No host
     synchronisation."""
-    B, N = _rows("dt_lookup", "query", query)
+    B, N = rows("dt_lookup", "query", query)
     _tensor("dt_lookup", "count", count, torch.int32, (B,), query.device)
     _tensor("dt_lookup", "dt2", dt2, torch.uint16, None, query.device)
     if dt2.dim() != 4 or dt2.shape[0] != B or not dt2.is_contiguous():
@@ -126,9 +117,8 @@ def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
     return pairflow.params_from_command(pairflow.entry("fastnsf"), given)
 
 
-def check_params(p: Dict[str, object]) -> Dict[str, object]:
-    """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    fn = "fastnsf_optimize"
+def check_params(p: Dict[str, object], fn: str = "fastnsf_optimize") -> Dict[str, object]:
+    """validated copy of a parameter dict (ValueError naming the argument, against ``fn``); launches nothing"""
     out = pairflow.merged(fn, DEFAULTS, p)
     for k, lo, hi in (("depth", 0, MAX_DEPTH), ("iters", 1, 1 << 20), ("patience", 1, 1 << 30), ("check_every", 0, 1 << 30),
                       ("seed", 0, (1 << 63) - 1)):
@@ -146,6 +136,66 @@ def start_params(depth: int, seed: int) -> torch.Tensor:
     return init_params(depth, seed)[:1].clone()
 
 
+class DataTerm:
+    """The data term fastnsf, mbnsf and floxels share, built once per pair: the transform of the second sweep (pc1, n1) on ``grid``
+    (dt_grid's result, with its cell) and m0, the participating rows of the first sweep (the transform leaves non-finite rows of the
+    second sweep out itself)."""
+
+    def __init__(self, pc1: torch.Tensor, n1: torch.Tensor, grid, cell: float, m0: torch.Tensor):
+        self.origin, dims, self.R = grid
+        self.cell, self.m0 = cell, m0
+        self.dt2 = dt_build(pc1, n1, origin=self.origin, cell=cell, dims=dims, radius=self.R)
+        self.inf = torch.full(m0.shape, math.inf, dtype=torch.float32, device=m0.device)
+
+    def __call__(self, W: torch.Tensor, n0: torch.Tensor):
+        """the warped rows W [B,N0,3] -> data [B] (the mean lookup over m0), d data / d W [B,N0,3] (g / max(n, 1) on m0, 0 elsewhere)
+        and the lookup's cells"""
+        d, g, cells, _ = dt_lookup(W, n0, self.dt2, origin=self.origin, cell=self.cell, radius=self.R, return_cells=True)
+        data, weight = mean_and_weight(torch.where(self.m0, d, self.inf))
+        return data, g * weight[..., None], cells
+
+
+def optimize_net(fn: str, pair, p: Dict[str, object], grid, init: Optional[torch.Tensor], term: Optional[Callable] = None,
+                 weight: float = 0.0):
+    """fastnsf's loop on pair_clouds' result, validated parameters and dt_grid's result: loss = data, or data + weight x value with
+    ``term``: W [B,N0,3] -> (value [B], its gradient [B,N0,3] already scaled by weight and the term's own normalisation).  With a term,
+    info gains last_terms [B,2] (data, value of the last iteration).  -> flow, info as fastnsf_optimize's."""
+    depth, B = p["depth"], pair.B
+    S = param_stride(depth)
+    start = start_params(depth, p["seed"]) if init is None else init
+    if not isinstance(start, torch.Tensor) or tuple(start.shape) != (1, S) or start.dtype != torch.float32:
+        raise ValueError(f"{fn}: init must be a float32 tensor of shape (1, {S})")
+    x0, n0, m0 = pair.x0, pair.n0, pair.m0                                 # (rows outside m0 are 0 for the net and left out of the loss)
+    with torch.no_grad():
+        data_term = DataTerm(pair.pc1, pair.n1, grid, p["cell"], m0)
+        arena = start.to(pair.dev)[None].repeat(B, 1, 1).contiguous()       # [B][1][S]
+        loop = Loop(arena, x0, p)
+        fpar = arena[:, 0]
+        last = {"cells": None}
+        if term is not None:
+            last["last_terms"] = torch.zeros(B, 2, dtype=torch.float32, device=pair.dev)
+
+        def iteration():
+            F, acts = mlp_forward(x0, n0, fpar, depth)
+            F = F * m0[..., None]
+            W = x0 + F
+            data, dF, cells = data_term(W, n0)
+            loss = data
+            if term is not None:
+                value, g = term(W)
+                loss = data + weight * value
+                dF = dF + g
+            mlp_backward(x0, n0, fpar, depth, acts, dF, need_dx=False, dparams=loop.grads[:, 0])
+            loop.snapshot(loss, F)
+            loop.update()
+            if term is not None:
+                last["last_terms"].copy_(torch.stack([data, value], dim=1))
+            last["cells"] = cells
+
+        loop.run(iteration)
+        return loop.result(m0, params=arena, **last)
+
+
 def fastnsf_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *, grid_range: Sequence[float],
                      init: Optional[torch.Tensor] = None, **params):
     """pc0s [B,N0,3] f32 (first sweep, in the second sweep's frame) with count0 [B] i32 valid leading rows; pc1 [B,N1,3], count1 alike;
@@ -155,75 +205,17 @@ def fastnsf_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor
     grads (of the last iteration), cells [B,N0,3] i32 (the last iteration's lookup cells), iters_run (host int).  Keywords: DEFAULTS;
     init: the [1, param_stride] start (else start_params(depth, seed)).  Uses no torch autograd.  No host synchronisation
     unless check_every > 0 (one read of the frozen flags per check_every iterations)."""
-    B, N0 = _rows("fastnsf_optimize", "pc0s", pc0s)
-    B1, N1 = _rows("fastnsf_optimize", "pc1", pc1)
-    dev = pc0s.device
-    if B1 != B or pc1.device != dev:
-        raise ValueError(f"fastnsf_optimize: pc1 must have the batch size ({B}) and device of pc0s, got {tuple(pc1.shape)} on {pc1.device}")
-    for name, c in (("count0", count0), ("count1", count1)):
-        _tensor("fastnsf_optimize", name, c, torch.int32, (B,), dev)
+    pair = pair_clouds("fastnsf_optimize", pc0s, count0, pc1, count1)
     p = check_params(params)
-    depth, iters, cell = p["depth"], p["iters"], p["cell"]
-    origin, dims, R = dt_grid(grid_range, cell, p["trunc"])
-    S = param_stride(depth)
-    start = start_params(depth, p["seed"]) if init is None else init
-    if not isinstance(start, torch.Tensor) or tuple(start.shape) != (1, S) or start.dtype != torch.float32:
-        raise ValueError(f"fastnsf_optimize: init must be a float32 tensor of shape (1, {S})")
-    with torch.no_grad():
-        pc0s, pc1 = pc0s.detach().contiguous(), pc1.detach().contiguous()
-        n0, n1 = count0.contiguous().clamp(0, N0), count1.contiguous().clamp(0, N1)
-        # participating rows of the first sweep; everything else is 0 for the net and left out of the loss (the transform leaves
-        # non-finite rows of the second sweep out itself)
-        m0 = (torch.arange(N0, device=dev)[None] < n0[:, None]) & torch.isfinite(pc0s).all(dim=2)
-        x0 = torch.where(m0[..., None], pc0s, torch.zeros_like(pc0s))
-        dt2 = dt_build(pc1, n1, origin=origin, cell=cell, dims=dims, radius=R)
-        arena = start.to(dev)[None].repeat(B, 1, 1).contiguous()       # [B][1][S]
-        grads = torch.zeros_like(arena)
-        exp_avg, exp_avg_sq = torch.zeros_like(arena), torch.zeros_like(arena)
-        step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        st = _loop_state(B, iters, x0)
-        st["cells"] = None
-        fpar = arena[:, 0]
-        inf = torch.full((B, N0), math.inf, dtype=torch.float32, device=dev)
-
-        def iteration():
-            F, acts = mlp_forward(x0, n0, fpar, depth)
-            F = F * m0[..., None]
-            W = x0 + F
-            d, g, cells, _ = dt_lookup(W, n0, dt2, origin=origin, cell=cell, radius=R, return_cells=True)
-            loss, weight = _mean_and_weight(torch.where(m0, d, inf))        # the mean over the participating rows, and 1 / max(n, 1) on them
-            mlp_backward(x0, n0, fpar, depth, acts, g * weight[..., None], need_dx=False, dparams=grads[:, 0])
-            _snapshot_and_freeze(st, loss, F, t_dev, p)
-            step_dev.add_(1)
-            call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), arena.numel(), p["lr"], BETAS[0], BETAS[1], EPS,
-                 ptr(step_dev), 1.0, stream())
-            st["cells"] = cells
-
-        ran = _run(iteration, st, p)
-        flow = st["best_flow"] * m0[..., None]
-    info = {"best_loss": st["best"], "loss_history": st["history"], "stalled": st["stalled"], "frozen": st["frozen"], "params": arena,
-            "grads": grads, "cells": st["cells"], "iters_run": ran}
-    return flow, info
+    return optimize_net("fastnsf_optimize", pair, p, dt_grid(grid_range, p["cell"], p["trunc"]), init)
 
 
-class FastNsf(PairFlowModel):
+class FastNsf(OptimisedPairModel):
     """``model=fastnsf``: ``nsfp.Nsfp``'s interface -- ``forward_padded`` and ``forward`` with ``DeFlow``'s keys, no weights -- around
     ``fastnsf_optimize``.  Every keyword besides point_cloud_range / voxel_size is one of DEFAULTS; the transform's grid covers
     point_cloud_range."""
+    optimize, check_params = staticmethod(fastnsf_optimize), staticmethod(check_params)
 
-    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
-        super().__init__(point_cloud_range, voxel_size)
-        self.params = check_params(params)
-        dt_grid(self.point_cloud_range, self.params["cell"], self.params["trunc"])        # refuse a grid that does not fit here
+    def check_grid(self) -> None:
+        dt_grid(self.point_cloud_range, self.params["cell"], self.params["trunc"])
 
-    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
-        """flow [B,N,3]: row i < counts0[b] is the residual flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind
-        them; pose_flow [B,N,3] of every input row.  Reads nothing back when check_every = 0."""
-        st = self._pair(batch)
-        flow, info = fastnsf_optimize(st["points_c0"], st["counts0"], st["points_c1"], st["counts1"], grid_range=self.point_cloud_range,
-                                      **self.params)
-        st.update({"flow": flow, "best_loss": info["best_loss"], "loss_history": info["loss_history"], "stalled": info["stalled"],
-                   "frozen": info["frozen"]})
-        self.last_state = st
-        return st

@@ -5,8 +5,8 @@ smoothness term that ties neighbouring active nodes together.  There is no net, 
 UNPINNED: the idea is Floxels' (Hoffmann et al., CVPR'25) -- a voxel grid instead of a coordinate MLP -- but upstream's source is absent
 and was not read; every choice here is this project's own.  The definition is in DESIGN.md section 6n and include/deflow_amd.h;
 tests/helpers/vox_ref.py restates it in numpy and torch.  The plan, the read, its transpose and the stencil run on csrc/voxflow.hip, the
-transform and its lookup on csrc/dt.hip (``deflow_amd.fastnsf``'s wrappers), the update on df_adam_step_dev; the loop's snapshot and freeze
-are ``nsfp``'s, unchanged.
+transform and its lookup on csrc/dt.hip (``deflow_amd.fastnsf``'s wrappers and data term); the loop, its snapshot and freeze and its
+Adam update are ``deflow_amd.pairopt``'s.
 
 CUDA tensors only, like the rest of the library: there is no CPU fallback.  The loop makes no host decision, so one iteration can be
 captured as a HIP graph (``graph=True``): a linear chain on one stream."""
@@ -19,9 +19,9 @@ import torch
 
 from . import pairflow
 from ._lib import call, ptr, stream
-from .fastnsf import R_MAX, _f32, _rows, dt_build, dt_grid, dt_lookup
-from .nsfp import BETAS, EPS, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze
-from .pairflow import PairFlowModel, _tensor
+from .fastnsf import R_MAX, DataTerm, dt_grid, f32
+from .pairflow import _tensor
+from .pairopt import Loop, OptimisedPairModel, pair_clouds, rows, sample_sum
 
 # every default of section 6n; all of them are arguments of floxels_optimize and Floxels, and `floxels_<name>=` keys of the commands
 DEFAULTS: Dict[str, object] = {"voxel": 0.4, "smooth_weight": 10.0, "iters": 1000, "lr": 0.05, "cell": 0.1, "trunc": 2.0, "patience": 100,
@@ -33,24 +33,24 @@ COMMAND_KEYS: Dict[str, str] = {"floxels_" + k: k for k in DEFAULTS}
 COMMAND_BATCH_SIZE = 4
 
 
-def vox_grid(grid_range: Sequence[float], voxel: float):
+def vox_grid(grid_range: Sequence[float], voxel: float, fn: str = "vox_grid"):
     """(minx, miny, minz, maxx, maxy, maxz), voxel -> origin (3 floats, as fp32 holds them), dims (VX, VY, VZ): V_a =
     ceil((max_a - min_a) / voxel - 1e-6) + 1 nodes per axis, at least 2; node (i, j, k) sits at origin + voxel (i, j, k).  ValueError
-    names the argument.  Launches nothing."""
+    names the argument, against ``fn``.  Launches nothing."""
     if len(grid_range) != 6 or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in grid_range):
-        raise ValueError(f"vox_grid: grid_range must be 6 finite values (minx, miny, minz, maxx, maxy, maxz), got {grid_range!r}")
+        raise ValueError(f"{fn}: grid_range must be 6 finite values (minx, miny, minz, maxx, maxy, maxz), got {grid_range!r}")
     if isinstance(voxel, bool) or not isinstance(voxel, (int, float)) or not (math.isfinite(voxel) and voxel > 0):
-        raise ValueError(f"vox_grid: voxel must be positive and finite, got {voxel!r}")
+        raise ValueError(f"{fn}: voxel must be positive and finite, got {voxel!r}")
     r = [float(v) for v in grid_range]
     if not all(r[3 + a] > r[a] for a in range(3)):
-        raise ValueError(f"vox_grid: grid_range is empty: {grid_range!r}")
+        raise ValueError(f"{fn}: grid_range is empty: {grid_range!r}")
     steps = [(r[3 + a] - r[a]) / float(voxel) for a in range(3)]
     if max(steps) >= 2 ** 31:
-        raise ValueError(f"vox_grid: grid_range / voxel: {max(steps):.3g} nodes on one axis do not fit 31 bits")
+        raise ValueError(f"{fn}: grid_range / voxel: {max(steps):.3g} nodes on one axis do not fit 31 bits")
     dims = tuple(max(int(math.ceil(s - 1e-6)) + 1, 2) for s in steps)                      # (102.4 / 0.4 is 256 + 3e-14)
     if 3 * math.prod(dims) >= 2 ** 31:
-        raise ValueError(f"vox_grid: grid_range / voxel: 3 x {dims[0]} x {dims[1]} x {dims[2]} node components do not fit 31 bits")
-    return tuple(_f32(r[a]) for a in range(3)), dims
+        raise ValueError(f"{fn}: grid_range / voxel: 3 x {dims[0]} x {dims[1]} x {dims[2]} node components do not fit 31 bits")
+    return tuple(f32(r[a]) for a in range(3)), dims
 
 
 def _dims(fn: str, dims, B: int, N: int = 1) -> Tuple[int, int, int]:
@@ -81,7 +81,7 @@ def vox_plan(x: torch.Tensor, count: torch.Tensor, *, origin: Sequence[float], v
     part), frac [B,N,3] f32, idx_sorted [B N] i32 (b N + row, grouped by (sample, cell), ascending inside a cell; -1 behind the grouped
     rows), cell_rng [B NC, 2] i32, active [B,NV] u8, pairs [B] i32 (M_b), and dims.  Exact; two calls are bit-identical; workspaces come
     from torch's allocator; no host synchronisation."""
-    B, N = _rows("vox_plan", "x", x)
+    B, N = rows("vox_plan", "x", x)
     dev = x.device
     _tensor("vox_plan", "count", count, torch.int32, (B,), dev)
     if len(origin) != 3 or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in origin):
@@ -136,7 +136,7 @@ def vox_scatter(dF: torch.Tensor, frac: torch.Tensor, idx_sorted: torch.Tensor, 
     """dF [B,N,3] f32 (rows that do not take part may hold anything), frac, idx_sorted, cell_rng (vox_plan's) -> dtheta [B,NV,3] f32: the
     exact transpose of vox_sample, summed per node in a fixed order.  No atomics: two calls are bit-identical and a sample's result does
     not depend on its batch.  Every node is written, 0 where nothing is incident; no host synchronisation."""
-    B, N = _rows("vox_scatter", "dF", dF)
+    B, N = rows("vox_scatter", "dF", dF)
     dev = dF.device
     VX, VY, VZ = _dims("vox_scatter", dims, B, N)
     NV, NC = VX * VY * VZ, (VX - 1) * (VY - 1) * (VZ - 1)
@@ -184,13 +184,10 @@ def check_params(p: Dict[str, object]) -> Dict[str, object]:
     return out
 
 
+
+
 def _grids(fn: str, grid_range, p: Dict[str, object]):
-    try:
-        origin, dims, R = dt_grid(grid_range, p["cell"], p["trunc"])
-        vorigin, vdims = vox_grid(grid_range, p["voxel"])
-    except ValueError as e:
-        raise ValueError(str(e).replace("dt_grid:", fn + ":").replace("vox_grid:", fn + ":")) from None
-    return origin, dims, R, vorigin, vdims
+    return dt_grid(grid_range, p["cell"], p["trunc"], fn=fn), vox_grid(grid_range, p["voxel"], fn=fn)
 
 
 def floxels_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *, grid_range: Sequence[float],
@@ -204,89 +201,55 @@ def floxels_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor
     n_pairs [B] i32 (M_b), last_terms [B,2] (data, smooth of the last iteration), plan (vox_plan's dict), iters_run (host int).
     Keywords: DEFAULTS; init: the [VZ,VY,VX,3] float32 start of every sample (else zero).  The start is deterministic: there is no seed.
     Uses no torch autograd.  No host synchronisation unless check_every > 0 (one read of the frozen flags per check_every iterations)."""
-    B, N0 = _rows("floxels_optimize", "pc0s", pc0s)
-    B1, N1 = _rows("floxels_optimize", "pc1", pc1)
-    dev = pc0s.device
-    if B1 != B or pc1.device != dev:
-        raise ValueError(f"floxels_optimize: pc1 must have the batch size ({B}) and device of pc0s, got {tuple(pc1.shape)} on {pc1.device}")
-    for name, c in (("count0", count0), ("count1", count1)):
-        _tensor("floxels_optimize", name, c, torch.int32, (B,), dev)
+    fn = "floxels_optimize"
+    pair = pair_clouds(fn, pc0s, count0, pc1, count1)
     p = check_params(params)
-    iters, cell, sw = p["iters"], p["cell"], p["smooth_weight"]
-    origin, dims, R, vorigin, vdims = _grids("floxels_optimize", grid_range, p)
-    VX, VY, VZ = _dims("floxels_optimize", vdims, B, N0)
+    sw = p["smooth_weight"]
+    grid, (vorigin, vdims) = _grids(fn, grid_range, p)
+    B, x0, n0 = pair.B, pair.x0, pair.n0                     # (rows outside m0 have cell = -1 (F = 0) and are left out of the loss)
+    VX, VY, VZ = _dims(fn, vdims, B, pair.N0)
     NV = VX * VY * VZ
     if init is not None and (not isinstance(init, torch.Tensor) or tuple(init.shape) != (VZ, VY, VX, 3) or init.dtype != torch.float32):
-        raise ValueError(f"floxels_optimize: init must be a float32 tensor of shape ({VZ}, {VY}, {VX}, 3)")
+        raise ValueError(f"{fn}: init must be a float32 tensor of shape ({VZ}, {VY}, {VX}, 3)")
     with torch.no_grad():
-        pc0s, pc1 = pc0s.detach().contiguous(), pc1.detach().contiguous()
-        n0, n1 = count0.contiguous().clamp(0, N0), count1.contiguous().clamp(0, N1)
-        # participating rows of the first sweep; everything else has cell = -1 (F = 0) and is left out of the loss
-        m0 = (torch.arange(N0, device=dev)[None] < n0[:, None]) & torch.isfinite(pc0s).all(dim=2)
-        x0 = torch.where(m0[..., None], pc0s, torch.zeros_like(pc0s))
         # the rows' cells and fractions, their grouping, the active nodes and the number of pairs: once per pair
-        plan = vox_plan(pc0s, n0, origin=vorigin, voxel=p["voxel"], dims=vdims)
+        plan = vox_plan(pair.pc0s, n0, origin=vorigin, voxel=p["voxel"], dims=vdims)
         inv_m = 1.0 / plan["pairs"].clamp_min(1).to(torch.float32)             # 1 / max(M_b, 1)
         g_scale = (sw * inv_m)[:, None, None]
-        dt2 = dt_build(pc1, n1, origin=origin, cell=cell, dims=dims, radius=R)
-        # flat arenas padded to a multiple of 4 (df_adam_step_dev's n % 4 == 0); theta and the gradient are views into theirs
+        data_term = DataTerm(pair.pc1, pair.n1, grid, p["cell"], pair.m0)
+        # a flat arena padded to a multiple of 4 (the Adam entry's n % 4 == 0); theta and the gradient are views into theirs
         n_par = 3 * B * NV
-        n_pad = (n_par + 3) // 4 * 4
-        arena = torch.zeros(n_pad, dtype=torch.float32, device=dev)
-        grads = torch.zeros_like(arena)
-        exp_avg, exp_avg_sq = torch.zeros_like(arena), torch.zeros_like(arena)
-        theta = arena[:n_par].view(B, VZ, VY, VX, 3)
-        gview = grads[:n_par].view(B, NV, 3)
+        loop = Loop(torch.zeros((n_par + 3) // 4 * 4, dtype=torch.float32, device=pair.dev), x0, p)
+        theta = loop.arena[:n_par].view(B, VZ, VY, VX, 3)
+        gview = loop.grads[:n_par].view(B, NV, 3)
         if init is not None:
-            theta.copy_(init.to(dev)[None].expand(B, VZ, VY, VX, 3))
-        step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        st = _loop_state(B, iters, x0)
-        st["cells"] = None
-        last_terms = torch.zeros(B, 2, dtype=torch.float32, device=dev)
-        inf = torch.full((B, N0), math.inf, dtype=torch.float32, device=dev)
+            theta.copy_(init.to(pair.dev)[None].expand(B, VZ, VY, VX, 3))
+        last_terms = torch.zeros(B, 2, dtype=torch.float32, device=pair.dev)
+        last = {"cells": None}
 
         def iteration():
             F = vox_sample(theta, plan["cell"], plan["frac"])
-            W = x0 + F
-            d, g, cells, _ = dt_lookup(W, n0, dt2, origin=origin, cell=cell, radius=R, return_cells=True)
-            data, weight = _mean_and_weight(torch.where(m0, d, inf))        # the mean over the participating rows, and 1 / max(n, 1) on them
+            data, dF, cells = data_term(x0 + F, n0)
             v, gs = vox_smooth(theta, plan["active"])
-            smooth = torch.stack([row.clone().sum() for row in v.unbind(0)]) * inv_m       # _mean_and_weight's rule: sample by sample
+            smooth = sample_sum(v) * inv_m
             loss = data + sw * smooth
-            dth = vox_scatter(g * weight[..., None], plan["frac"], plan["idx_sorted"], plan["cell_rng"], dims=vdims)
+            dth = vox_scatter(dF, plan["frac"], plan["idx_sorted"], plan["cell_rng"], dims=vdims)
             torch.addcmul(dth, gs, g_scale, out=gview)                      # (both are 0 at an inactive node: Adam leaves it at 0)
-            _snapshot_and_freeze(st, loss, F, t_dev, p)
-            step_dev.add_(1)
-            call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), arena.numel(), p["lr"], BETAS[0], BETAS[1], EPS,
-                 ptr(step_dev), 1.0, stream())
+            loop.snapshot(loss, F)
+            loop.update()
             last_terms.copy_(torch.stack([data, smooth], dim=1))
-            st["cells"] = cells
+            last["cells"] = cells
 
-        ran = _run(iteration, st, p)
-        flow = st["best_flow"] * m0[..., None]
-    info = {"best_loss": st["best"], "loss_history": st["history"], "stalled": st["stalled"], "frozen": st["frozen"], "theta": theta,
-            "grads": gview, "cells": st["cells"], "iters_run": ran, "n_pairs": plan["pairs"], "last_terms": last_terms, "plan": plan}
-    return flow, info
+        loop.run(iteration)
+        return loop.result(pair.m0, theta=theta, grads=gview, n_pairs=plan["pairs"], last_terms=last_terms, plan=plan, **last)
 
 
-class Floxels(PairFlowModel):
+class Floxels(OptimisedPairModel):
     """``model=floxels``: ``fastnsf.FastNsf``'s interface -- ``forward_padded`` and ``forward`` with ``DeFlow``'s keys, no weights -- around
     ``floxels_optimize``.  Every keyword besides point_cloud_range / voxel_size is one of DEFAULTS; the field's grid and the transform's
     cover point_cloud_range."""
+    optimize, check_params = staticmethod(floxels_optimize), staticmethod(check_params)
+    KEEP = ("n_pairs", "last_terms")
 
-    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
-        super().__init__(point_cloud_range, voxel_size)
-        self.params = check_params(params)
-        _grids("Floxels", self.point_cloud_range, self.params)                               # refuse grids that do not fit here
-
-    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
-        """flow [B,N,3]: row i < counts0[b] is the residual flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind
-        them; pose_flow [B,N,3] of every input row.  Reads nothing back when check_every = 0."""
-        st = self._pair(batch)
-        flow, info = floxels_optimize(st["points_c0"], st["counts0"], st["points_c1"], st["counts1"], grid_range=self.point_cloud_range,
-                                      **self.params)
-        st.update({"flow": flow, "best_loss": info["best_loss"], "loss_history": info["loss_history"], "stalled": info["stalled"],
-                   "frozen": info["frozen"], "n_pairs": info["n_pairs"], "last_terms": info["last_terms"]})
-        self.last_state = st
-        return st
+    def check_grid(self) -> None:
+        _grids("Floxels", self.point_cloud_range, self.params)

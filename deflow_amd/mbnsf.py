@@ -5,7 +5,7 @@ distances between rows of one cluster of the first sweep, so that the rows of on
 UNPINNED: the idea is MBNSF's multi-body regulariser (Vidanapathirana et al., 3DV'24), but upstream's source is absent and was not read;
 every choice here is this project's own.  The definition is in DESIGN.md section 6m and include/deflow_amd.h; tests/helpers/iso_ref.py
 restates it in torch.  The clusters come from ``cluster.dbscan`` once per pair, their ordered row lists from df_rigid_segments, the
-neighbour table and the term from csrc/iso.hip; everything else is ``fastnsf``'s and ``nsfp``'s, unchanged.
+neighbour table and the term from csrc/iso.hip; everything else is ``fastnsf.optimize_net``, handed the term, on ``pairopt``'s loop.
 
 CUDA tensors only, like the rest of the library: there is no CPU fallback.  The loop makes no host decision, so one iteration can be
 captured as a HIP graph (``graph=True``): a linear chain on one stream."""
@@ -18,9 +18,9 @@ import torch
 
 from . import fastnsf, pairflow
 from ._lib import call, ptr, stream
-from .fastnsf import _rows, dt_build, dt_grid, dt_lookup, start_params
-from .nsfp import BETAS, EPS, _loop_state, _mean_and_weight, _run, _snapshot_and_freeze, mlp_backward, mlp_forward, param_stride
-from .pairflow import PairFlowModel, _tensor
+from .fastnsf import FastNsf, dt_grid, optimize_net
+from .pairflow import _tensor
+from .pairopt import pair_clouds, rows, sample_sum
 
 P_MAX = 16               # pairs per row (csrc/iso.hip: ISO_PMAX)
 
@@ -42,10 +42,7 @@ def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
     fn = "mbnsf_optimize"
     out = pairflow.merged(fn, DEFAULTS, p)
-    try:
-        out.update(fastnsf.check_params({k: out[k] for k in fastnsf.DEFAULTS}))
-    except ValueError as e:
-        raise ValueError(str(e).replace("fastnsf_optimize:", "mbnsf_optimize:")) from None
+    out.update(fastnsf.check_params({k: out[k] for k in fastnsf.DEFAULTS}, fn=fn))
     pairflow.nonneg(fn, out, "rigid_weight", finite=True)
     pairflow.positive(fn, out, "rigid_delta", finite=True)
     pairflow.positive(fn, out, "eps", finite=True)
@@ -74,7 +71,7 @@ def iso_plan(x: torch.Tensor, count: torch.Tensor, labels: torch.Tensor, *, pair
     r0 [B,N,2 pairs] f32 (their rest distances, 0 at -1), n_pairs [B] i32 (the pair instances M_b).  Labels of rows behind the count are
     ignored.  status: optional i32[1] that is added to for a label outside [0, kcap].  Exact integers; two calls are bit-identical;
     workspaces come from torch's allocator; no host synchronisation."""
-    B, N = _rows("iso_plan", "x", x)
+    B, N = rows("iso_plan", "x", x)
     dev = x.device
     _tensor("iso_plan", "count", count, torch.int32, (B,), dev)
     _tensor("iso_plan", "labels", labels, torch.int32, (B, N), dev)
@@ -115,7 +112,7 @@ def iso_pairs(w: torch.Tensor, nbr: torch.Tensor, r0: torch.Tensor, *, delta: fl
     """w [B,N,3] f32 (the warped rows), nbr / r0 [B,N,2P] (iso_plan's) -> v [B,N] f32 (the penalty summed over each row's P forward
     instances) and g [B,N,3] f32 (d (sum of the penalties) / d w, not normalised).  Every element is written, 0 at a row without
     partners; no atomics: two calls are bit-identical.  No host synchronisation."""
-    B, N = _rows("iso_pairs", "w", w)
+    B, N = rows("iso_pairs", "w", w)
     _table("iso_pairs", "nbr", nbr, torch.int32, B, N, w.device)
     _table("iso_pairs", "r0", r0, torch.float32, B, N, w.device)
     if r0.shape != nbr.shape:
@@ -138,97 +135,38 @@ def mbnsf_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, 
     rows, xy cells over grid_range).  info holds fastnsf's keys and labels [B,N0] i32, n_pairs [B] i32 (the pair instances M_b),
     cluster_status i32[1] (dbscan's and the lists' status word, 0 on a sane input), last_terms [B,2] (data, iso of the last iteration).
     Keywords: DEFAULTS.  Uses no torch autograd.  No host synchronisation unless check_every > 0."""
-    B, N0 = _rows("mbnsf_optimize", "pc0s", pc0s)
-    B1, N1 = _rows("mbnsf_optimize", "pc1", pc1)
-    dev = pc0s.device
-    if B1 != B or pc1.device != dev:
-        raise ValueError(f"mbnsf_optimize: pc1 must have the batch size ({B}) and device of pc0s, got {tuple(pc1.shape)} on {pc1.device}")
-    for name, c in (("count0", count0), ("count1", count1)):
-        _tensor("mbnsf_optimize", name, c, torch.int32, (B,), dev)
+    fn = "mbnsf_optimize"
+    pair = pair_clouds(fn, pc0s, count0, pc1, count1)
     if labels is not None:
-        _tensor("mbnsf_optimize", "labels", labels, torch.int32, (B, N0), dev)
+        _tensor(fn, "labels", labels, torch.int32, (pair.B, pair.N0), pair.dev)
     p = check_params(params)
-    depth, iters, cell = p["depth"], p["iters"], p["cell"]
-    try:
-        origin, dims, R = dt_grid(grid_range, cell, p["trunc"])
-    except ValueError as e:
-        raise ValueError(str(e).replace("dt_grid:", "mbnsf_optimize:")) from None
-    S = param_stride(depth)
-    start = start_params(depth, p["seed"]) if init is None else init
-    if not isinstance(start, torch.Tensor) or tuple(start.shape) != (1, S) or start.dtype != torch.float32:
-        raise ValueError(f"mbnsf_optimize: init must be a float32 tensor of shape (1, {S})")
-    rw, P = p["rigid_weight"], p["rigid_pairs"]
+    grid = dt_grid(grid_range, p["cell"], p["trunc"], fn=fn)
+    x0, n0, m0 = pair.x0, pair.n0, pair.m0
     with torch.no_grad():
-        pc0s, pc1 = pc0s.detach().contiguous(), pc1.detach().contiguous()
-        n0, n1 = count0.contiguous().clamp(0, N0), count1.contiguous().clamp(0, N1)
-        m0 = (torch.arange(N0, device=dev)[None] < n0[:, None]) & torch.isfinite(pc0s).all(dim=2)
-        x0 = torch.where(m0[..., None], pc0s, torch.zeros_like(pc0s))
         # the clusters, their neighbour table and the number of pair instances: once per pair
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=pair.dev)
         if labels is None:
             from .cluster import dbscan
             labels, _ = dbscan(x0, n0, mask=m0, eps=p["eps"], min_points=p["min_points"], min_cluster_size=p["min_cluster_size"],
                                grid_range=(grid_range[0], grid_range[1], grid_range[3], grid_range[4]), status=status)
         labels = torch.where(m0, labels, torch.zeros_like(labels)).contiguous()
-        nbr, r0, n_pairs = iso_plan(x0, n0, labels, pairs=P, max_cluster_points=p["max_cluster_points"],
-                                    kcap=kcap(N0, p["min_cluster_size"]), status=status)
+        nbr, r0, n_pairs = iso_plan(x0, n0, labels, pairs=p["rigid_pairs"], max_cluster_points=p["max_cluster_points"],
+                                    kcap=kcap(pair.N0, p["min_cluster_size"]), status=status)
         inv_m = 1.0 / n_pairs.clamp_min(1).to(torch.float32)               # 1 / max(M_b, 1)
-        g_scale = (rw * inv_m)[:, None, None]
-        dt2 = dt_build(pc1, n1, origin=origin, cell=cell, dims=dims, radius=R)
-        arena = start.to(dev)[None].repeat(B, 1, 1).contiguous()       # [B][1][S]
-        grads = torch.zeros_like(arena)
-        exp_avg, exp_avg_sq = torch.zeros_like(arena), torch.zeros_like(arena)
-        step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        st = _loop_state(B, iters, x0)
-        st["cells"] = None
-        last_terms = torch.zeros(B, 2, dtype=torch.float32, device=dev)
-        fpar = arena[:, 0]
-        inf = torch.full((B, N0), math.inf, dtype=torch.float32, device=dev)
+        g_scale = (p["rigid_weight"] * inv_m)[:, None, None]
 
-        def iteration():
-            F, acts = mlp_forward(x0, n0, fpar, depth)
-            F = F * m0[..., None]
-            W = x0 + F
-            d, g, cells, _ = dt_lookup(W, n0, dt2, origin=origin, cell=cell, radius=R, return_cells=True)
-            data, weight = _mean_and_weight(torch.where(m0, d, inf))
+        def iso(W):
             v, gi = iso_pairs(W, nbr, r0, delta=p["rigid_delta"])
-            iso = torch.stack([row.clone().sum() for row in v.unbind(0)]) * inv_m      # _mean_and_weight's rule: sample by sample
-            loss = data + rw * iso
-            dF = g * weight[..., None] + g_scale * gi                       # (gi is 0 outside m0: those rows have no partners)
-            mlp_backward(x0, n0, fpar, depth, acts, dF, need_dx=False, dparams=grads[:, 0])
-            _snapshot_and_freeze(st, loss, F, t_dev, p)
-            step_dev.add_(1)
-            call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), arena.numel(), p["lr"], BETAS[0], BETAS[1], EPS,
-                 ptr(step_dev), 1.0, stream())
-            last_terms.copy_(torch.stack([data, iso], dim=1))
-            st["cells"] = cells
+            return sample_sum(v) * inv_m, g_scale * gi                      # (gi is 0 outside m0: those rows have no partners)
 
-        ran = _run(iteration, st, p)
-        flow = st["best_flow"] * m0[..., None]
-    info = {"best_loss": st["best"], "loss_history": st["history"], "stalled": st["stalled"], "frozen": st["frozen"], "params": arena,
-            "grads": grads, "cells": st["cells"], "iters_run": ran, "labels": labels, "n_pairs": n_pairs, "cluster_status": status,
-            "last_terms": last_terms}
+    flow, info = optimize_net(fn, pair, p, grid, init, term=iso, weight=p["rigid_weight"])
+    info.update({"labels": labels, "n_pairs": n_pairs, "cluster_status": status})
     return flow, info
 
 
-class MbNsf(PairFlowModel):
+class MbNsf(FastNsf):
     """``model=mbnsf``: ``fastnsf.FastNsf``'s interface -- ``forward_padded`` and ``forward`` with ``DeFlow``'s keys, no weights -- around
     ``mbnsf_optimize``.  Every keyword besides point_cloud_range / voxel_size is one of DEFAULTS; the transform's grid covers
     point_cloud_range."""
-
-    def __init__(self, point_cloud_range=(-51.2, -51.2, -3, 51.2, 51.2, 3), voxel_size=(0.2, 0.2, 6), **params):
-        super().__init__(point_cloud_range, voxel_size)
-        self.params = check_params(params)
-        dt_grid(self.point_cloud_range, self.params["cell"], self.params["trunc"])        # refuse a grid that does not fit here
-
-    def forward_padded(self, batch: Dict[str, torch.Tensor]) -> dict:
-        """flow [B,N,3]: row i < counts0[b] is the residual flow of input row idx_c0[b,i] (the decoded rows in ascending order), 0 behind
-        them; pose_flow [B,N,3] of every input row.  Reads nothing back when check_every = 0."""
-        st = self._pair(batch)
-        flow, info = mbnsf_optimize(st["points_c0"], st["counts0"], st["points_c1"], st["counts1"], grid_range=self.point_cloud_range,
-                                    **self.params)
-        st.update({"flow": flow, "best_loss": info["best_loss"], "loss_history": info["loss_history"], "stalled": info["stalled"],
-                   "frozen": info["frozen"], "labels": info["labels"], "n_pairs": info["n_pairs"], "last_terms": info["last_terms"]})
-        self.last_state = st
-        return st
+    optimize, check_params = staticmethod(mbnsf_optimize), staticmethod(check_params)
+    KEEP = ("labels", "n_pairs", "last_terms")

@@ -2,6 +2,7 @@
 float64, the grid, the parameter checks and the commands' keys and refusals."""
 import os
 import pickle
+import re
 import shutil
 
 import numpy as np
@@ -127,6 +128,10 @@ def test_check_params_and_start():
         assert a.shape == (1, nsfp.param_stride(depth)) and a.dtype == torch.float32 and torch.equal(a[0], nsfp.init_params(depth, seed)[0])
     src = open(fastnsf.__file__).read()
     assert 'start_params(depth, p["seed"]) if init is None' in src and "repeat(B, 1, 1)" in src      # every sample starts from that copy
+    # the optimiser uses no autograd, and the loop, its Adam call and its graph capture are pairopt's, imported and not copied
+    assert "requires_grad" not in src and ".backward(" not in src and "from .pairopt import" in src
+    assert "df_adam_step_dev" not in src and "torch.cuda.graph" not in src and "CUDAGraph" not in src
+    assert re.search(r"def \w*(snapshot|freeze|run)\w*\(", src) is None
     # CPU tensors are refused by name
     x, c = torch.zeros(1, 4, 3), torch.zeros(1, dtype=torch.int32)
     with pytest.raises(TypeError, match="ref must be a CUDA tensor"):

@@ -3,6 +3,7 @@ gradients against finite differences in float64, the transpose identity, the pla
 commands' keys and refusals."""
 import os
 import pickle
+import re
 import shutil
 
 import numpy as np
@@ -243,10 +244,11 @@ def test_check_params_and_keys():
         floxels.Floxels(voxel=0.01)
     m = floxels.Floxels(iters=5, smooth_weight=1.0)
     assert m.eval() is m and m.to("cuda") is m and list(m.parameters()) == [] and m.params["iters"] == 5 and m.params["smooth_weight"] == 1.0
-    # the optimiser uses no autograd and no net, and the loops it reuses are imported, not copied
+    # the optimiser uses no autograd and no net, and the loop, its Adam call and its graph capture are pairopt's, imported and not copied
     src = open(floxels.__file__).read()
-    assert "requires_grad" not in src and ".backward(" not in src and "mlp_forward" not in src and "from .nsfp import" in src
-    assert "_snapshot_and_freeze(st, loss, F, t_dev, p)" in src and "_run(iteration, st, p)" in src and "df_adam_step_dev" in src
+    assert "requires_grad" not in src and ".backward(" not in src and "mlp_forward" not in src and "from .pairopt import" in src
+    assert "df_adam_step_dev" not in src and "torch.cuda.graph" not in src and "CUDAGraph" not in src
+    assert re.search(r"def \w*(snapshot|freeze|run)\w*\(", src) is None
 
 
 # ---- the commands' keys and refusals --------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 against finite differences in float64 -- the parameter checks and the commands' keys and refusals."""
 import os
 import pickle
+import re
 import shutil
 
 import numpy as np
@@ -165,9 +166,12 @@ def test_check_params_and_keys():
         mbnsf.MbNsf(point_cloud_range=(-200, -200, -20, 200, 200, 20))
     m = mbnsf.MbNsf(iters=5, rigid_weight=1.0)
     assert m.eval() is m and m.to("cuda") is m and list(m.parameters()) == [] and m.params["iters"] == 5 and m.params["rigid_weight"] == 1.0
-    # nothing of the term leaves the estimator's own module: the optimiser uses no autograd and the loops it reuses are imported
+    # nothing of the term leaves the estimator's own module: the optimiser uses no autograd, and the loop, its Adam call and its graph
+    # capture are pairopt's, imported and not copied
     src = open(mbnsf.__file__).read()
-    assert "requires_grad" not in src and ".backward(" not in src and "from .nsfp import" in src and "_snapshot_and_freeze(st, loss, F, t_dev, p)" in src
+    assert "requires_grad" not in src and ".backward(" not in src and "from .pairopt import" in src
+    assert "df_adam_step_dev" not in src and "torch.cuda.graph" not in src and "CUDAGraph" not in src
+    assert re.search(r"def \w*(snapshot|freeze|run)\w*\(", src) is None
 
 
 # ---- the commands' keys and refusals --------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@ parameter checks and the commands' keys and refusals."""
 import math
 import os
 import pickle
+import re
 import shutil
 
 import numpy as np
@@ -88,7 +89,12 @@ def test_seeded_initialisation():
             assert float(blk.abs().max()) <= lim and float(blk.abs().max()) > 0.9 * lim and abs(float(blk.mean())) < 0.1 * lim
     assert not a[:, nsfp.num_params(2):].any()
     # every sample of a batch starts from the same copy: the arena is this block repeated (nsfp_optimize: start[None].repeat(B, 1, 1))
-    assert "repeat(B, 1, 1)" in open(nsfp.__file__).read()
+    src = open(nsfp.__file__).read()
+    assert "repeat(B, 1, 1)" in src
+    # the loop, its Adam call and its graph capture are pairopt's, imported and not copied
+    assert "requires_grad" not in src and ".backward(" not in src and "from .pairopt import" in src
+    assert "df_adam_step_dev" not in src and "torch.cuda.graph" not in src and "CUDAGraph" not in src
+    assert re.search(r"def \w*(snapshot|freeze|run)\w*\(", src) is None
 
 
 def test_check_params():

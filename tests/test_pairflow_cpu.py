@@ -214,3 +214,49 @@ def test_check_params_messages_are_the_recorded_ones(name):
                 m.params_from_command({key: repr(v)})
             assert str(err.value) == f"bad value among the {e.prefix}_* keys: {text}"
     assert m.check_params({}) == m.DEFAULTS
+
+
+# ---- the texts that name the caller -------------------------------------------------------------------------------------------------------
+# recorded from the parent of the commit that gave dt_grid, vox_grid and fastnsf.check_params their fn= argument: until then mbnsf and
+# floxels caught these errors and replaced the prefix in the text
+R, BIG = (-51.2, -51.2, -3, 51.2, 51.2, 3), (-200, -200, -20, 200, 200, 20)
+DT_GRID = [((R[:4], 0.1, 2.0), "grid_range must be 6 finite values (minx, miny, minz, maxx, maxy, maxz), got (-51.2, -51.2, -3, 51.2)"),
+           ((R, 0, 2.0), "cell must be positive and finite, got 0"),
+           ((R, 0.1, True), "trunc must be positive and finite, got True"),
+           ((R, 0.3, 2.0), "trunc must be a whole number of cells, 1 to 255 of them, got trunc = 2.0, cell = 0.3"),
+           (((0, 0, 0, 1, 1, 0), 0.1, 2.0), "grid_range is empty: (0, 0, 0, 1, 1, 0)"),
+           ((BIG, 0.1, 2.0), "grid_range / cell: 4040 x 4040 x 440 voxels do not fit 31 bits")]
+VOX_GRID = [((R[:4], 0.4), "grid_range must be 6 finite values (minx, miny, minz, maxx, maxy, maxz), got (-51.2, -51.2, -3, 51.2)"),
+            ((R, -0.4), "voxel must be positive and finite, got -0.4"),
+            (((0, 0, 0, 1, 1, 0), 0.4), "grid_range is empty: (0, 0, 0, 1, 1, 0)"),
+            ((R, 1e-9), "grid_range / voxel: 1.02e+11 nodes on one axis do not fit 31 bits"),
+            ((R, 0.01), "grid_range / voxel: 3 x 10241 x 10241 x 601 node components do not fit 31 bits")]
+FASTNSF_AS_MBNSF = [({"seed": -1}, "mbnsf_optimize: seed must be an integer in [0, 9223372036854775807], got -1"),
+                    ({"trunc": float("nan")}, "mbnsf_optimize: trunc must be positive and finite, got nan"),
+                    ({"patience": 0}, "mbnsf_optimize: patience must be an integer in [1, 1073741824], got 0"),
+                    ({"depth": 16}, "mbnsf_optimize: depth must be an integer in [0, 15], got 16")]
+
+
+def _text(call, *args, **kw):
+    with pytest.raises(ValueError) as err:
+        call(*args, **kw)
+    return str(err.value)
+
+
+def test_messages_that_name_the_caller_are_the_recorded_ones():
+    from deflow_amd import fastnsf, floxels, mbnsf
+    for args, text in DT_GRID:
+        assert _text(fastnsf.dt_grid, *args) == "dt_grid: " + text                       # fastnsf_optimize and FastNsf report it as dt_grid's
+        for fn in ("mbnsf_optimize", "floxels_optimize", "Floxels"):
+            assert _text(fastnsf.dt_grid, *args, fn=fn) == f"{fn}: {text}"
+    for args, text in VOX_GRID:
+        assert _text(floxels.vox_grid, *args) == "vox_grid: " + text
+        for fn in ("floxels_optimize", "Floxels"):
+            assert _text(floxels.vox_grid, *args, fn=fn) == f"{fn}: {text}"
+    for bad, text in FASTNSF_AS_MBNSF:
+        assert _text(mbnsf.check_params, bad) == text == _text(fastnsf.check_params, bad, fn="mbnsf_optimize")
+        assert _text(fastnsf.check_params, bad) == text.replace("mbnsf_optimize:", "fastnsf_optimize:")
+    # the models' constructors refuse a grid that does not fit with the same texts as before
+    assert _text(fastnsf.FastNsf, point_cloud_range=BIG) == _text(mbnsf.MbNsf, point_cloud_range=BIG) == "dt_grid: " + DT_GRID[5][1]
+    assert _text(floxels.Floxels, point_cloud_range=BIG) == "Floxels: " + DT_GRID[5][1]
+    assert _text(floxels.Floxels, voxel=0.01) == "Floxels: " + VOX_GRID[4][1]

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from deflow_amd import fastnsf, nsfp  # noqa: E402
+from deflow_amd import fastnsf, nsfp, pairopt  # noqa: E402
 from nsfp_bench import median_ms  # noqa: E402
 
 RANGE = (-51.2, -51.2, -3.0, 51.2, 51.2, 3.0)
@@ -74,7 +74,7 @@ def main():
     res["fastnsf"]["split_ms"] = {
         "mlp_forward": round(median_ms(lambda: nsfp.mlp_forward(p0, cnt, par, depth)), 4),
         "lookup": round(ms_lookup, 4),
-        "loss_reduction": round(median_ms(lambda: nsfp._mean_and_weight(d)), 4),
+        "loss_reduction": round(median_ms(lambda: pairopt.mean_and_weight(d)), 4),
         "mlp_backward without dx": round(median_ms(lambda: nsfp.mlp_backward(p0, cnt, par, depth, acts, dy, need_dx=False)), 4)}
     res["unexamined"] = ("no hardware counters were collected: where the transform's passes spend their time (L2 hits of the window reads, "
                          "the 2-byte accesses) is not examined; the rows are uniformly random, so the grid is far more occupied than a real "

@@ -19,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from deflow_amd import fastnsf, floxels, nsfp  # noqa: E402
+from deflow_amd import fastnsf, floxels, pairopt  # noqa: E402
 from deflow_amd._lib import call, ptr, stream  # noqa: E402
 from nsfp_bench import median_ms  # noqa: E402
 
@@ -124,23 +124,22 @@ def main():
     step = torch.ones(1, dtype=torch.int32, device=dev)
     weight = torch.full((1, N), 1.0 / N, device=dev)
     scale1 = torch.full((1, 1, 1), 1e-3, device=dev)
-    st = nsfp._loop_state(1, 4, p0)
-    t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+    state = pairopt.Loop(torch.zeros(4, device=dev), p0, dict(D, iters=4))
     loss = torch.ones(1, device=dev)
 
     def snapshot():
-        t_dev.zero_()
-        nsfp._snapshot_and_freeze(st, loss, dF, t_dev, D)
+        state.t_dev.zero_()
+        state.snapshot(loss, dF)
 
     hip = {"vox_sample": res["uniform_rows"]["vox_sample"]["ms"],
            "dt_lookup": round(graph_ms(lambda: fastnsf.dt_lookup(p0, cnt, dt2, origin=origin, cell=D["cell"], radius=R, return_cells=True)), 4),
            "vox_smooth": res["uniform_rows"]["vox_smooth"]["ms"], "vox_scatter": res["uniform_rows"]["vox_scatter"]["ms"],
            "adam_step": round(graph_ms(lambda: call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(m1), ptr(m2), arena.numel(), D["lr"],
-                                                     nsfp.BETAS[0], nsfp.BETAS[1], nsfp.EPS, ptr(step), 1.0, stream())), 4)}
+                                                     pairopt.BETAS[0], pairopt.BETAS[1], pairopt.EPS, ptr(step), 1.0, stream())), 4)}
     tor = {"x0 + F": round(graph_ms(lambda: p0 + dF), 4),
-           "data mean and weight": round(graph_ms(lambda: nsfp._mean_and_weight(d)), 4),
+           "data mean and weight": round(graph_ms(lambda: pairopt.mean_and_weight(d)), 4),
            "g x weight": round(graph_ms(lambda: g * weight[..., None]), 4),
-           "smooth reduction": round(graph_ms(lambda: torch.stack([row.clone().sum() for row in v.unbind(0)])), 4),
+           "smooth reduction": round(graph_ms(lambda: pairopt.sample_sum(v)), 4),
            "gradient addcmul": round(graph_ms(lambda: torch.addcmul(dth, gs, scale1, out=gview)), 4),
            "snapshot and freeze": round(graph_ms(snapshot), 4)}
     it = res["floxels"]["ms_per_iteration_graph"]

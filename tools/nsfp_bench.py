@@ -16,7 +16,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from deflow_amd import nsfp  # noqa: E402
+from deflow_amd import nsfp, pairopt  # noqa: E402
 from deflow_amd._lib import call, ptr, stream  # noqa: E402
 from deflow_amd.chamfer import chamfer_bwd  # noqa: E402
 
@@ -73,7 +73,7 @@ def main():
     search = nsfp._Search(1, nsfp.GRID_RANGE, nsfp.CELL, 4.0, dev)
     grid1 = search.build(p1, cnt, lab)
     d2, idx = search.nn(W, cnt, lab, grid1)
-    g = nsfp._mean_and_weight(d2)[1]
+    g = pairopt.mean_and_weight(d2)[1]
     buf = torch.zeros_like(W)
     grads, m, v = torch.zeros_like(arena), torch.zeros_like(arena), torch.zeros_like(arena)
     step = torch.ones(1, dtype=torch.int32, device=dev)
@@ -81,10 +81,10 @@ def main():
     ms_bwd = median_ms(lambda: nsfp.mlp_backward(p0, cnt, par, depth, acts, dy, need_dx=True))
     ms_nn = median_ms(lambda: search.nn(W, cnt, lab, grid1))
     ms_build = median_ms(lambda: search.build(W, cnt, lab))
-    ms_red = median_ms(lambda: nsfp._mean_and_weight(d2))
+    ms_red = median_ms(lambda: pairopt.mean_and_weight(d2))
     ms_cq = median_ms(lambda: chamfer_bwd(W, p1, idx, g, buf, None))
     ms_cr = median_ms(lambda: chamfer_bwd(W, p1, idx, g, None, buf))
-    ms_adam = median_ms(lambda: call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(m), ptr(v), arena.numel(), 8e-3, 0.9, 0.999, 1e-8,
+    ms_adam = median_ms(lambda: call("df_adam_step_dev", ptr(arena), ptr(grads), ptr(m), ptr(v), arena.numel(), 8e-3, *pairopt.BETAS, pairopt.EPS,
                                      ptr(step), 1.0, stream()))
     hid = depth * 128 * 128
     flop_fwd = 2.0 * N * (3 * 128 + hid + 128 * 3)
