@@ -10,6 +10,7 @@
 //                      until the distance from the query to the edge of the scanned square -- a lower bound for every row not seen yet,
 //                      valid without z -- exceeds the best distance found (or max_dist2).  At most G rings: every loop is bounded by the
 //                      grid's extent, whatever the input.
+//                      The walk itself is nn_search.h's nn_ring_search, which df_reg_accumulate (register.hip) runs too.
 //   df_chamfer_bwd     gather part: dquery[i] += 2 g_i (q_i - ref[idx_i]); scatter part: dref[k] += sum over the queries i with
 //                      idx_i == k of 2 g_i (ref_k - q_i), the pairs segmented by k with the same counting sort and summed in ascending i
 //                      by ONE thread per ref row -- no float atomics, a repeated call is bit-identical.
@@ -18,20 +19,11 @@
 #include <math.h>
 
 #include "common.h"
+#include "nn_search.h"
 
 namespace {
 
 constexpr uint32_t NN_DROP = 0xffffffffu;   // key of a row that does not take part (df_cell_sort drops keys >= ncells)
-
-__device__ __forceinline__ bool nn_finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// cell coordinate of a FINITE coordinate: clamped in float first, so that no out-of-range float is ever converted to int
-__device__ __forceinline__ int nn_cell(float v, float lo, float inv_cell, int G, float* pos /* clamped position, cell units */) {
-  const float f = fminf(fmaxf((v - lo) * inv_cell, 0.f), (float)G);
-  *pos = f;
-  const int c = (int)f;
-  return c > G - 1 ? G - 1 : c;
-}
 
 __global__ __launch_bounds__(256) void nn_keys_kernel(const float* __restrict__ ref, const int32_t* __restrict__ rcount,
                                                       const int32_t* __restrict__ rlabel, int Nr, float minx, float miny, float inv_cell,
@@ -87,50 +79,9 @@ __global__ __launch_bounds__(256) void chamfer_nn_kernel(const float* __restrict
     part = nn_finite3(qx, qy, qz);
   }
   if (part) {
-    const float inv_cell = 1.0f / cell;
-    float px, py;
-    const int cx = nn_cell(qx, minx, inv_cell, G, &px), cy = nn_cell(qy, miny, inv_cell, G, &py);
-    const int32_t* rng = cell_rng + (int64_t)b * G * G * 2;
-    auto scan = [&](int s, int e) {
-      for (int p = s; p < e; ++p) {
-        const f32x4 v = sorted[p];
-        const float dx = v.x - qx, dy = v.y - qy, dz = v.z - qz;
-        const float d = dx * dx + dy * dy + dz * dz;
-        const float w = v.w;
-        const int j = __builtin_bit_cast(int, w);
-        if (d < best || (d == best && j < bi)) {
-          best = d;
-          bi = j;
-        }
-      }
-    };
-    int r = 0;
-    for (; r <= G; ++r) {                                  // at most G + 1 rings: bounded by the grid's extent
-      const int x0 = cx - r, x1 = cx + r, y0 = cy - r, y1 = cy + r;
-      const int xa = x0 < 0 ? 0 : x0, xb = x1 > G - 1 ? G - 1 : x1;
-      const int ya = y0 < 0 ? 0 : y0, yb = y1 > G - 1 ? G - 1 : y1;
-      for (int y = ya; y <= yb; ++y) {
-        const int32_t* rr = rng + (int64_t)y * G * 2;
-        if (y == y0 || y == y1) {
-          scan(rr[2 * xa], rr[2 * xb + 1]);                // a whole row of the ring: adjacent cells are one contiguous span
-        } else {
-          if (x0 >= 0) scan(rr[2 * x0], rr[2 * x0 + 1]);
-          if (x1 <= G - 1) scan(rr[2 * x1], rr[2 * x1 + 1]);
-        }
-      }
-      // every row not seen yet lies in a cell outside the square [x0, x1] x [y0, y1], hence -- border cells hold rows clamped INTO the
-      // range, and a query outside it is measured from its clamped position, which only shortens -- at least as far in x or y as the
-      // nearest side of the square that still has cells beyond it.  (cells: positions in cell units)
-      float lb = INFINITY;
-      if (x0 > 0) lb = fminf(lb, px - (float)x0);
-      if (x1 < G - 1) lb = fminf(lb, (float)(x1 + 1) - px);
-      if (y0 > 0) lb = fminf(lb, py - (float)y0);
-      if (y1 < G - 1) lb = fminf(lb, (float)(y1 + 1) - py);
-      if (!(lb < INFINITY)) break;                         // the square covers the grid
-      lb = fmaxf(lb - 2e-3f, 0.f) * cell;                  // slack for the rounding of the cell coordinates (< 1e-3 cell at G <= 4096)
-      const float lb2 = lb * lb;
-      if (lb2 > best || lb2 > max_dist2) break;            // (equal: keep going -- an equal distance with a lower row index may follow)
-    }
+    f32x4 unused;
+    const int r = nn_ring_search<false>(qx, qy, qz, cell_rng + (int64_t)b * G * G * 2, sorted, minx, miny, cell, G, max_dist2, best, bi,
+                                        unused);        // (nn_search.h: the walk df_reg_accumulate runs too)
     if (far_count && r >= 2) atomicAdd(far_count, 1);
     if (!(best <= max_dist2)) {
       best = INFINITY;
@@ -185,9 +136,6 @@ __global__ __launch_bounds__(256) void chamfer_bwd_scatter_kernel(const float* _
 }
 
 inline int64_t al16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-// rows of one padded tensor are addressed as 32-bit sorted positions and keys: B * N (and, for the grid, B * G * G) must stay below 2^30
-inline bool nn_rows_ok(int B, int N) { return B > 0 && N > 0 && (int64_t)B * N < 0x3fffffffll; }
-inline bool nn_grid_ok(int B, int G) { return G > 0 && G <= 4096 && (int64_t)B * G * G < 0x3fffffffll; }
 
 }  // namespace
 

@@ -24,7 +24,7 @@ namespace {
 
 constexpr uint32_t CL_CORE = 0x80000000u;     // top bit of a record's index word (row indices stay below 2^30)
 
-// identical arithmetic to chamfer.hip's nn_cell (the cell the grid build filed the row under)
+// identical arithmetic to nn_search.h's nn_cell (the cell the grid build filed the row under)
 __device__ __forceinline__ int cl_cell(float v, float lo, float inv_cell, int G) {
   const float f = fminf(fmaxf((v - lo) * inv_cell, 0.f), (float)G);
   const int c = (int)f;

@@ -30,12 +30,13 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import torch
 
 from .h5scene import H5File
+from .odometry import check_pose_source, load_pose_sidecar, sweep_pose
 
 
 class HDF5Dataset:
     def __init__(self, directory: str, max_open_files: int = 8, eval: bool = False, dynamic_key: str = "dufo_label",
                  dynamic_sidecar: Optional[str] = ".dufo.npz", ground_sidecar: str = ".ground.npz", ground_source: str = "auto",
-                 flow_sidecar: Optional[str] = None):
+                 flow_sidecar: Optional[str] = None, pose_source: str = "auto", pose_sidecar: Optional[str] = ".pose.npz"):
         """``dynamic_key``: the per-sweep dataset holding the per-point dynamic flag (non-zero = dynamic) that online cluster labels
         start from (``Trainer(cluster_labels=...)``).  UNPINNED: ``dufo_label`` is the name recalled from upstream's process.py (the
         DUFO pass writes it before HDBSCAN turns it into ``label``), hence an argument.  When both sweeps of a pair hold it, the item
@@ -55,6 +56,11 @@ class HDF5Dataset:
         per timestamp (pseudo labels, e.g. of ``save model=icpflow``) -- with ``flow_is_valid`` all true and
         ``flow_category_indices`` all zero.  A missing file or timestamp is a KeyError naming that command, an array whose length differs
         from the sweep's rows a ValueError.  A group that has ``flow`` keeps it.  None: the items the directory always gave.
+        ``pose_source`` / ``pose_sidecar``: where ``pose0`` / ``pose1`` come from, like ``ground_source``.  "auto": a group's own ``pose``
+        dataset wins (every file that holds one gives the items it always gave); a group without one takes its pose from
+        ``<directory>/<scene_id><pose_sidecar>`` -- the file ``python -m deflow_amd.odometry data_dir=<directory>`` writes: one float64
+        [4,4] per timestamp, registered on the GPU by the odometry of DESIGN.md section 6r (UNPINNED).  "file": the dataset only.
+        "sidecar": the sidecar only, which must exist.  A sidecar that is missing or lacks a timestamp is a ValueError naming that command.
         ``eval=True`` (the evaluation entry): read ``index_eval.pkl`` -- the frames of the official validation benchmark, the ones
         that carry an ``eval_mask`` -- when the directory has one, as upstream's dataset does for ``av2_mode=val`` (recalled: the
         module is in the absent submodule); ``index_total.pkl`` lists every sweep of every scene."""
@@ -70,6 +76,9 @@ class HDF5Dataset:
         if flow_sidecar is not None and (not flow_sidecar or os.sep in str(flow_sidecar)):
             raise ValueError(f"flow_sidecar must be the res_name of a flow file, got {flow_sidecar!r}")
         self.flow_sidecar = flow_sidecar
+        check_pose_source(pose_source, pose_sidecar)
+        self.pose_source, self.pose_sidecar = pose_source, pose_sidecar
+        self._pose_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
         self._flow_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
         self._sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()       # cached per scene like the open files (None: no file)
         self._ground_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
@@ -144,6 +153,23 @@ class HDF5Dataset:
                              "another version of the scene file")
         return flow.float()
 
+    def _pose(self, scene_id: str, ts: str, group) -> torch.Tensor:
+        """the pose of one sweep, by ``pose_source``"""
+        source = getattr(self, "pose_source", "auto")
+        if source == "file" or (source == "auto" and "pose" in group):
+            return torch.from_numpy(group["pose"].read())
+        with self._lock:
+            known = scene_id in self._pose_sidecars
+            side = self._pose_sidecars.get(scene_id)
+        if not known:
+            side = load_pose_sidecar(self.directory, scene_id, self.pose_sidecar)
+            with self._lock:
+                self._pose_sidecars[scene_id] = side
+                while len(self._pose_sidecars) > self._max_open:
+                    self._pose_sidecars.popitem(last=False)
+        return torch.from_numpy(sweep_pose(group, side, scene_id=scene_id, ts=ts, pose_source=source, pose_sidecar=self.pose_sidecar,
+                                           directory=self.directory))
+
     def _ground(self, scene_id: str, ts: str, group, rows: int) -> torch.Tensor:
         """the ground mask of one sweep, by ``ground_source``"""
         if self.ground_source == "file" or (self.ground_source == "auto" and "ground_mask" in group):
@@ -174,8 +200,8 @@ class HDF5Dataset:
         t = lambda d: torch.from_numpy(d.read())
         pc0, pc1 = t(g0["lidar"])[:, :3], t(g1["lidar"])[:, :3]
         item = {"scene_id": scene_id, "timestamp": int(timestamp),
-                "pc0": pc0, "gm0": self._ground(scene_id, timestamp, g0, pc0.shape[0]), "pose0": t(g0["pose"]),
-                "pc1": pc1, "gm1": self._ground(scene_id, f.sweeps[k + 1], g1, pc1.shape[0]), "pose1": t(g1["pose"])}
+                "pc0": pc0, "gm0": self._ground(scene_id, timestamp, g0, pc0.shape[0]), "pose0": self._pose(scene_id, timestamp, g0),
+                "pc1": pc1, "gm1": self._ground(scene_id, f.sweeps[k + 1], g1, pc1.shape[0]), "pose1": self._pose(scene_id, f.sweeps[k + 1], g1)}
         if "flow" in g0:
             item.update(flow=t(g0["flow"]), flow_is_valid=t(g0["flow_is_valid"]),
                         flow_category_indices=t(g0["flow_category_indices"]))

@@ -30,7 +30,7 @@ from typing import Any, Dict, List
 import torch
 
 from . import pairflow
-from .train import DATA_KEYS, DEFAULTS, _TARGET_ALIASES, build_model, grid_from, parse_overrides, split_metrics_impl
+from .train import DATA_KEYS, DEFAULTS, _TARGET_ALIASES, build_model, grid_from, parse_overrides, split_metrics_impl, split_pose_source
 
 
 def resolve_config(path: str, given: dict, skip=()) -> dict:
@@ -172,6 +172,7 @@ def main(argv=None, wrap=None):
     # eval passes one); without it the command is what it was
     # metrics_impl=host|device: where the metrics are accumulated; not a hyper-parameter, taken off before parse_overrides
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
+    pose_source, args = split_pose_source(args)      # where poses are read (HDF5Dataset(pose_source=...)); not a hyper-parameter either
     given = {a.split("=", 1)[0].lstrip("+"): a for a in args if "=" in a}
     pair = pairflow.selected(given)         # a checkpoint-free pair model (deflow_amd/pairflow.py), or None
     if pair and given.get("av2_mode", "av2_mode=val") == "av2_mode=test":
@@ -225,7 +226,7 @@ def main(argv=None, wrap=None):
     B = int(cfg["batch_size"])
     if cfg["val_data"] != "synthetic":
         from .data import HDF5Dataset, SceneLoader, ShardedSampler
-        ds = HDF5Dataset(str(cfg["val_data"]), eval=True)      # index_eval.pkl (the benchmark's frames) when the directory has one
+        ds = HDF5Dataset(str(cfg["val_data"]), eval=True, pose_source=pose_source)      # index_eval.pkl (the benchmark's frames) when the directory has one
         batches = SceneLoader(ds, B, ShardedSampler(len(ds), shuffle=False), device=dev,
                               num_workers=max(0, int(cfg["num_workers"])), drop_last=False)
     else:

@@ -1,0 +1,399 @@
+"""Sweep-to-sweep odometry on the GPU: the per-sweep ``pose`` of a raw recording, the last per-sweep input of the self-supervised chain
+that nothing in the tree produced (``HDF5Dataset`` reads it for ``pose0`` / ``pose1``, ``voidmap.sweep_frames`` puts every sweep in one
+frame with it).
+
+UNPINNED: people with their own recordings are normally sent to an external LiDAR odometry for this.  What runs here is this project's own
+definition -- include/deflow_amd.h and DESIGN.md section 6r -- a scan-to-scan, point-to-point ICP with Geman-McClure weights in 6 degrees
+of freedom: no map, no loop closure, no motion un-distortion, and nothing about its accuracy on real sweeps has been measured.  Scene flow
+needs only the relative transform of consecutive sweeps (the reference's ``ego_motion``), which is what it estimates; the poses are those
+transforms chained.
+
+``register`` is the op (CUDA tensors only: there is no CPU fallback, every iteration is two launches and nothing in it reads a device
+value back); ``register_sweeps`` / ``scene_poses`` run it over the consecutive sweeps of a recording, and
+``python -m deflow_amd.odometry data_dir=<dir>`` writes ``<scene_id>.pose.npz`` beside every scene, which ``HDF5Dataset`` and the void map
+pick up (``pose_source``) when the file has no ``pose``."""
+from __future__ import annotations
+
+import json
+import math
+import os
+import sys
+import time
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ._lib import call, ptr, stream
+from .chamfer import GRID_RANGE, _grid
+
+SIDECAR_SUFFIX = ".pose.npz"
+POSE_SOURCES = ("auto", "file", "sidecar")
+# this project's own choices, unmeasured: gate distances of the levels (kernel = max_dist / 3), iterations per level, the grids' cell
+LEVELS = (2.0, 1.0, 0.5)
+DEFAULTS: Dict[str, Any] = {"xy_range": GRID_RANGE, "cell": 1.0, "stride": 4, "levels": LEVELS, "iters": 8, "min_inliers": 50,
+                            "planar": False}
+SCENE_DEFAULTS: Dict[str, Any] = {"min_range": 3.0, "max_range": 51.2}
+
+
+def _tensor(name: str, t, dtype, shape, device=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"register: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    if device is not None and t.device != device:
+        raise ValueError(f"register: {name} is on {t.device}, src on {device}")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"register: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def _mask(name: str, m, shape, device) -> Optional[torch.Tensor]:
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor) or not m.is_cuda or m.device != device or tuple(m.shape) != tuple(shape) or m.dtype.is_floating_point:
+        raise ValueError(f"register: {name} must be an integer or bool CUDA tensor of shape {tuple(shape)} on {device}")
+    return m.to(torch.int32).contiguous()
+
+
+def schedule(levels, iters) -> List[Tuple[float, int]]:
+    """levels: gate distances (each then runs ``iters`` iterations) or (max_dist, iters) pairs -> [(max_dist, iters), ...]"""
+    out = []
+    try:
+        for lv in levels:
+            d, n = (lv if isinstance(lv, (tuple, list)) else (lv, iters))
+            d, n = float(d), int(n)
+            if not (math.isfinite(d) and d > 0) or not 0 <= n <= 1024:
+                raise ValueError
+            out.append((d, n))
+    except (TypeError, ValueError):
+        raise ValueError(f"register: levels must be positive finite distances or (distance, iterations 0..1024) pairs, got {levels!r} "
+                         f"with iters={iters!r}") from None
+    if not out:
+        raise ValueError("register: levels must name at least one level")
+    return out
+
+
+def _file(points, count, mask, B, N, minx, miny, cell, G):
+    """df_nn_grid_build of one cloud -> (cell_rng, rows)"""
+    dev = points.device
+    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
+    rows = torch.empty(B * N, 4, dtype=torch.float32, device=dev)
+    ws = torch.empty(call("df_nn_grid_ws_bytes", B, N, G), dtype=torch.uint8, device=dev)
+    call("df_nn_grid_build", ptr(points), ptr(count), ptr(mask), B, N, minx, miny, float(cell), G, ptr(cell_rng), ptr(rows), ptr(ws), stream())
+    return cell_rng, rows
+
+
+def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_d: torch.Tensor, *, init: Optional[torch.Tensor] = None,
+             mask_s: Optional[torch.Tensor] = None, mask_d: Optional[torch.Tensor] = None, xy_range: Sequence[float] = DEFAULTS["xy_range"],
+             cell: float = DEFAULTS["cell"], stride: int = DEFAULTS["stride"], levels=DEFAULTS["levels"], iters: int = DEFAULTS["iters"],
+             min_inliers: int = DEFAULTS["min_inliers"], planar: bool = DEFAULTS["planar"], rows: bool = False):
+    """src [B,Ns,3] f32 with count_s [B] i32 valid leading rows, dst [B,Nd,3] with count_d [B]; optional integer / bool masks [B,Ns], [B,Nd]
+    (only rows with mask > 0 take part; non-finite rows never do).  init: [B,4,4] floating CUDA tensor, identity when None.
+    -> (T [B,4,4] float64 with dst ~ R src + t, info).  info: ``status`` [B] i32 of the last iteration (0 updated, 2 fewer than min_inliers
+    inliers, 3 singular: T was left alone in that iteration), ``log`` [B, total iterations + 1, 4] f32 = (inliers, weighted mean squared
+    residual, |omega|, |v|) of every iteration and, last, of the final T; rows=True adds the final per-row ``q`` [B,Ns,3], ``idx`` [B,Ns],
+    ``d2`` [B,Ns], ``w`` [B,Ns].  levels: gate distances, each run for ``iters`` iterations with kernel = distance / 3,
+    or (distance, iterations) pairs.  A fixed number of launches, no early stop, no host synchronisation."""
+    if not isinstance(src, torch.Tensor) or not isinstance(dst, torch.Tensor) or src.dim() != 3 or dst.dim() != 3 or src.shape[2] != 3 or \
+            dst.shape[2] != 3 or src.shape[0] != dst.shape[0]:
+        raise ValueError("register: src [B,Ns,3] and dst [B,Nd,3] expected, got "
+                         f"{tuple(getattr(src, 'shape', ()))} and {tuple(getattr(dst, 'shape', ()))}")
+    B, Ns, _ = src.shape
+    Nd = dst.shape[1]
+    if B == 0 or Ns == 0 or Nd == 0:
+        raise ValueError("register: empty batch or zero padded rows")
+    _tensor("src", src, torch.float32, (B, Ns, 3))
+    dev = src.device
+    _tensor("dst", dst, torch.float32, (B, Nd, 3), dev)
+    _tensor("count_s", count_s, torch.int32, (B,), dev)
+    _tensor("count_d", count_d, torch.int32, (B,), dev)
+    if int(stride) != stride or not 1 <= int(stride) <= 1024:
+        raise ValueError(f"register: stride must be an integer in 1..1024, got {stride!r}")
+    if int(min_inliers) != min_inliers or int(min_inliers) < 0:
+        raise ValueError(f"register: min_inliers must be an integer >= 0, got {min_inliers!r}")
+    plan = schedule(levels, iters)
+    try:
+        minx, miny, G = _grid(B, xy_range, cell)
+    except (TypeError, ValueError):
+        raise ValueError(f"register: bad grid (xy_range {tuple(xy_range)}, cell {cell})") from None
+    if init is None:
+        T = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1)
+    else:
+        if not isinstance(init, torch.Tensor) or not init.is_cuda or init.device != dev or tuple(init.shape) != (B, 4, 4) or \
+                not init.dtype.is_floating_point:
+            raise ValueError(f"register: init must be a floating CUDA tensor of shape {(B, 4, 4)} on {dev}")
+        T = init.detach().to(torch.float64).contiguous().clone()
+    src, dst = src.detach().contiguous(), dst.detach().contiguous()
+    count_s, count_d = count_s.contiguous(), count_d.contiguous()
+    ms, md = _mask("mask_s", mask_s, (B, Ns), dev), _mask("mask_d", mask_d, (B, Nd), dev)
+
+    s_rng, s_rows = _file(src, count_s, ms, B, Ns, minx, miny, cell, G)
+    d_rng, d_rows = _file(dst, count_d, md, B, Nd, minx, miny, cell, G)
+    nblk = (Ns + 255) // 256
+    slab = call("df_reg_ws_bytes", B, Ns)
+    if slab <= 0:
+        raise ValueError(f"register: B = {B} samples of Ns = {Ns} rows are beyond the entries' limits (B <= 65535, B Ns < 2^30)")
+    partial = torch.empty(slab // 8, dtype=torch.float64, device=dev)
+    total = sum(n for _, n in plan)
+    log = torch.zeros(total + 1, B, 4, dtype=torch.float32, device=dev)
+    status = torch.full((B,), 2, dtype=torch.int32, device=dev)      # (no iteration at all: nothing was updated)
+    s = stream()
+
+    def accumulate(max_dist, outs=(None, None, None, None)):
+        call("df_reg_accumulate", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), minx, miny, float(cell), G, B, Ns, int(stride), ptr(T),
+             float(max_dist) ** 2, (float(max_dist) / 3.0) ** 2, ptr(partial), *(ptr(o) for o in outs), s)
+
+    it = 0
+    for max_dist, n in plan:
+        for _ in range(n):
+            accumulate(max_dist)
+            call("df_reg_solve", ptr(partial), B, nblk, int(min_inliers), int(bool(planar)), ptr(T), ptr(log[it]), ptr(status), s)
+            it += 1
+    info: Dict[str, torch.Tensor] = {"status": status}
+    outs = (None, None, None, None)
+    if rows:
+        outs = (torch.empty(B, Ns, 3, dtype=torch.float32, device=dev), torch.empty(B, Ns, dtype=torch.int32, device=dev),
+                torch.empty(B, Ns, dtype=torch.float32, device=dev), torch.empty(B, Ns, dtype=torch.float32, device=dev))
+        info.update(zip(("q", "idx", "d2", "w"), outs))
+    accumulate(plan[-1][0], outs)                                      # the final T's rows and log: nothing is solved
+    call("df_reg_solve", ptr(partial), B, nblk, int(min_inliers), int(bool(planar)), None, ptr(log[total]), None, s)
+    info["log"] = log.permute(1, 0, 2)
+    return T, info
+
+
+# ---- recordings -------------------------------------------------------------------------------------------------------------------------
+def chain_poses(rel: Sequence[np.ndarray]) -> List[np.ndarray]:
+    """rel[k] maps sweep k into sweep k + 1's frame -> the poses: pose_0 = I, pose_{k+1} = pose_k @ inv(rel[k]), float64"""
+    poses = [np.eye(4, dtype=np.float64)]
+    for T in rel:
+        poses.append(poses[-1] @ np.linalg.inv(np.asarray(T, dtype=np.float64)))
+    return poses
+
+
+def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Optional[np.ndarray]]] = None, *, init: str = "previous",
+                    min_range: float = SCENE_DEFAULTS["min_range"], max_range: float = SCENE_DEFAULTS["max_range"], device="cuda",
+                    report: Optional[dict] = None, **params) -> List[np.ndarray]:
+    """Relative transforms of consecutive sweeps given as arrays [N_i, >= 3], each in its own vehicle frame, in time order:
+    -> rel[k] float64 [4,4] mapping sweep k into sweep k + 1's frame, one B = 1 ``register`` per pair.  ground: per sweep None or a 0 / 1
+    array [N_i]; ground rows do not take part.  Rows take part only at a horizontal distance from the frame's origin in
+    [min_range, max_range].  The first pair starts from identity; init="previous": each later pair from the previous pair's result
+    (constant velocity), "identity": every pair from identity.  A pair whose status is not 0 keeps its initial transform.
+    report: a dict that receives the parameters, the failed pairs and the final inliers / residual of every pair."""
+    if init not in ("previous", "identity"):
+        raise ValueError(f"register_sweeps: init must be 'previous' or 'identity', got {init!r}")
+    if not (0 <= float(min_range) < float(max_range)):
+        raise ValueError(f"register_sweeps: 0 <= min_range < max_range expected, got {min_range}, {max_range}")
+    unknown = sorted(set(params) - set(DEFAULTS))
+    if unknown:
+        raise TypeError(f"register_sweeps: unknown parameters {unknown}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError("register_sweeps: device must be a CUDA device (deflow_amd has no CPU fallback)")
+    clouds = []
+    for k, lidar in enumerate(lidars):
+        p = np.ascontiguousarray(np.asarray(lidar)[:, :3], dtype=np.float32)
+        with np.errstate(invalid="ignore"):
+            rng = np.hypot(p[:, 0].astype(np.float64), p[:, 1].astype(np.float64))
+            keep = (rng >= min_range) & (rng <= max_range)
+        if ground is not None and ground[k] is not None:
+            g = np.asarray(ground[k]).reshape(-1)
+            if g.shape[0] != p.shape[0]:
+                raise ValueError(f"register_sweeps: {g.shape[0]} ground flags for sweep {k}, which has {p.shape[0]} rows")
+            keep &= g == 0
+        if p.shape[0] == 0:
+            p, keep = np.full((1, 3), np.nan, dtype=np.float32), np.zeros(1, dtype=bool)
+        clouds.append((torch.from_numpy(p).to(device)[None], torch.full((1,), p.shape[0], dtype=torch.int32, device=device),
+                       torch.from_numpy(keep.astype(np.int32)).to(device)[None]))
+    start = torch.eye(4, dtype=torch.float64, device=device)[None]
+    Ts, stats = [], []
+    for k in range(len(clouds) - 1):
+        (ps, cs, ms), (pd, cd, md) = clouds[k], clouds[k + 1]
+        T, info = register(ps, cs, pd, cd, init=start, mask_s=ms, mask_d=md, **params)
+        ok = (info["status"] == 0).reshape(1, 1, 1)
+        T = torch.where(ok, T, start)                                  # a failed pair keeps its initial transform
+        Ts.append(T)
+        stats.append(torch.cat((info["status"].to(torch.float32), info["log"][0, -1, :2])))
+        if init == "previous":
+            start = T
+    if not Ts:
+        rel, st = [], np.zeros((0, 3), dtype=np.float32)
+    else:
+        rel = list(torch.cat(Ts).cpu().numpy())                        # the one read-back, after every pair was queued
+        st = torch.stack(stats).cpu().numpy()
+    if report is not None:
+        report.update(params={**DEFAULTS, **params, "min_range": float(min_range), "max_range": float(max_range), "init": init},
+                      failed=[{"pair": int(k), "status": int(s[0])} for k, s in enumerate(st) if int(s[0]) != 0],
+                      inliers=[float(s[1]) for s in st], residual=[float(s[2]) for s in st])
+    return rel
+
+
+def scene_poses(h5_path: str, *, ground_source: str = "auto", init: str = "previous", device="cuda", report: Optional[dict] = None,
+                **params) -> Dict[str, np.ndarray]:
+    """Poses of every sweep of a preprocessed scene file, sweeps taken in timestamp order: {timestamp: float64 [4,4]}, the first sweep's
+    frame as the world (pose_0 = I, pose_{k+1} = pose_k @ inv(T_k)).  ground_source="auto": ground rows are left out where the group holds
+    a ``ground_mask`` or ``<scene_id>.ground.npz`` (python -m deflow_amd.ground) has the sweep; "none": every row is used."""
+    from .ground import SIDECAR_SUFFIX as GROUND_SUFFIX
+    from .h5scene import H5File
+    if ground_source not in ("auto", "none"):
+        raise ValueError(f"scene_poses: ground_source must be 'auto' or 'none', got {ground_source!r}")
+    side = None
+    gpath = h5_path[:-3] + GROUND_SUFFIX if h5_path.endswith(".h5") else None
+    if ground_source == "auto" and gpath and os.path.exists(gpath):
+        with np.load(gpath, allow_pickle=False) as z:
+            side = {k: z[k] for k in z.files if k != "meta"}
+    with H5File(h5_path) as f:
+        keys = sorted(f.keys(), key=int)
+        lidars = [f[k]["lidar"].read() for k in keys]
+        ground: List[Optional[np.ndarray]] = [None] * len(keys)
+        if ground_source == "auto":
+            for i, k in enumerate(keys):
+                if "ground_mask" in f[k]:
+                    ground[i] = f[k]["ground_mask"].read()
+                elif side is not None and k in side:
+                    ground[i] = side[k]
+    rel = register_sweeps(lidars, ground, init=init, device=device, report=report, **params)
+    if report is not None:
+        report["params"]["ground_source"] = ground_source
+        report["ground_masks"] = sum(g is not None for g in ground)
+    return dict(zip(keys, chain_poses(rel)))
+
+
+def _plain(v):
+    if isinstance(v, (tuple, list)):
+        return [_plain(x) for x in v]
+    return v
+
+
+def write_sidecar(path: str, poses: Dict[str, np.ndarray], meta: Dict[str, Any]) -> None:
+    """<scene_id>.pose.npz: one float64 [4,4] per timestamp and the parameters as a JSON string under ``meta``; written atomically"""
+    tmp = path + ".tmp.npz"
+    np.savez(tmp, meta=np.array(json.dumps({k: _plain(v) for k, v in meta.items()}, sort_keys=True)),
+             **{str(k): np.asarray(v, dtype=np.float64).reshape(4, 4) for k, v in poses.items()})
+    os.replace(tmp, path)
+
+
+def read_sidecar(path: str) -> Dict[str, np.ndarray]:
+    """the per-timestamp poses of a sidecar (without ``meta``)"""
+    with np.load(path, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files if k != "meta"}
+
+
+# ---- the readers' side: where a sweep's pose comes from ---------------------------------------------------------------------------------
+def check_pose_source(pose_source: str, pose_sidecar: Optional[str]) -> None:
+    if pose_source not in POSE_SOURCES:
+        raise ValueError(f"pose_source must be 'auto', 'file' or 'sidecar', got {pose_source!r}")
+    if pose_source == "sidecar" and not pose_sidecar:
+        raise ValueError("pose_source='sidecar' needs a pose_sidecar suffix")
+
+
+def load_pose_sidecar(directory: str, scene_id: str, pose_sidecar: Optional[str] = SIDECAR_SUFFIX) -> Optional[Dict[str, np.ndarray]]:
+    """the poses of ``<directory>/<scene_id><pose_sidecar>``, None when there is no such file (or no suffix)"""
+    if not pose_sidecar:
+        return None
+    path = os.path.join(directory, f"{scene_id}{pose_sidecar}")
+    return read_sidecar(path) if os.path.exists(path) else None
+
+
+def sweep_pose(group, side: Optional[Dict[str, np.ndarray]], *, scene_id: str, ts: str, pose_source: str = "auto",
+               pose_sidecar: Optional[str] = SIDECAR_SUFFIX, directory: str = ".") -> np.ndarray:
+    """The pose of one sweep, by ``pose_source``: "auto": the group's own ``pose`` dataset wins, a group without one takes the sidecar's;
+    "file": the dataset only; "sidecar": the sidecar (``side``: what load_pose_sidecar returned) only.  A sidecar that is missing or lacks
+    the timestamp is a ValueError naming the command that writes it."""
+    if pose_source == "file" or (pose_source == "auto" and "pose" in group):
+        return group["pose"].read()
+    if side is None or ts not in side:
+        what = "does not exist" if side is None else f"has no entry for sweep {ts}"
+        raise ValueError(f"{scene_id}: no pose for sweep {ts} (pose_source={pose_source!r}): {scene_id}{pose_sidecar} {what}; write it with  "
+                         f"python -m deflow_amd.odometry data_dir={directory}")
+    pose = np.asarray(side[ts])
+    if pose.shape != (4, 4):
+        raise ValueError(f"{scene_id}{pose_sidecar}: pose of shape {pose.shape} for sweep {ts}, [4,4] expected")
+    return pose
+
+
+# ---- command line -----------------------------------------------------------------------------------------------------------------------
+CLI_DEFAULTS: Dict[str, Any] = {"data_dir": None, "scenes": None, "overwrite": False, "ground_source": "auto", "init": "previous",
+                                **SCENE_DEFAULTS, **{k: (list(v) if isinstance(v, tuple) else v) for k, v in DEFAULTS.items()}}
+USAGE = ("usage: python -m deflow_amd.odometry data_dir=<dir> [scenes=a,b] [overwrite=false] [stride=4] [levels=2,1,0.5] [iters=8] "
+         "[planar=false] [min_inliers=50] [ground_source=auto|none] [init=previous|identity] [min_range=3] [max_range=51.2] [cell=1] "
+         "[xy_range=-51.2,-51.2,51.2,51.2]")
+
+
+def _bool(v: str) -> bool:
+    if v.lower() not in ("true", "false", "1", "0"):
+        raise ValueError(v)
+    return v.lower() in ("true", "1")
+
+
+def parse_args(argv: List[str]) -> Dict[str, Any]:
+    """key=value arguments in the style of deflow_amd.train"""
+    cfg = dict(CLI_DEFAULTS)
+    for a in argv:
+        if "=" not in a:
+            raise SystemExit(f"expected key=value, got {a!r}")
+        k, v = a.split("=", 1)
+        k = k.lstrip("+")
+        if k not in CLI_DEFAULTS:
+            raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted(CLI_DEFAULTS))}")
+        try:
+            if k == "data_dir":
+                cfg[k] = v
+            elif k == "scenes":
+                cfg[k] = [s for s in v.split(",") if s]
+            elif k in ("overwrite", "planar"):
+                cfg[k] = _bool(v)
+            elif k == "ground_source":
+                if v not in ("auto", "none"):
+                    raise ValueError(v)
+                cfg[k] = v
+            elif k == "init":
+                if v not in ("previous", "identity"):
+                    raise ValueError(v)
+                cfg[k] = v
+            elif k in ("levels", "xy_range"):
+                cfg[k] = [float(x) for x in v.strip("[]()").split(",")]
+                if (k == "xy_range" and len(cfg[k]) != 4) or not cfg[k] or not all(math.isfinite(x) for x in cfg[k]) or \
+                        (k == "levels" and not all(x > 0 for x in cfg[k])):
+                    raise ValueError(v)
+            elif k in ("stride", "iters", "min_inliers"):
+                cfg[k] = int(v)
+                lo, hi = {"stride": (1, 1024), "iters": (0, 1024), "min_inliers": (0, 2 ** 31 - 1)}[k]
+                if not lo <= cfg[k] <= hi:
+                    raise ValueError(v)
+            else:
+                cfg[k] = float(v)
+                if not math.isfinite(cfg[k]) or cfg[k] < 0 or (k == "cell" and cfg[k] == 0):
+                    raise ValueError(v)
+        except ValueError:
+            raise SystemExit(f"bad value for {k}: {v!r}")
+    if not cfg["data_dir"]:
+        raise SystemExit(USAGE)
+    if not cfg["min_range"] < cfg["max_range"]:
+        raise SystemExit(f"bad value for min_range / max_range: {cfg['min_range']} .. {cfg['max_range']}")
+    return cfg
+
+
+def main(argv=None) -> int:
+    cfg = parse_args(sys.argv[1:] if argv is None else argv)
+    assert torch.cuda.is_available(), "the odometry runs on the HIP engine only"
+    d = cfg["data_dir"]
+    scenes = cfg["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
+    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS)}
+    for sid in scenes:
+        out = os.path.join(d, sid + SIDECAR_SUFFIX)
+        if os.path.exists(out) and not cfg["overwrite"]:
+            print(json.dumps({"scene": sid, "skipped": "sidecar exists (overwrite=true replaces it)"}), flush=True)
+            continue
+        rep: Dict[str, Any] = {}
+        t0 = time.perf_counter()
+        poses = scene_poses(os.path.join(d, sid + ".h5"), ground_source=cfg["ground_source"], init=cfg["init"], report=rep, **params)
+        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": "DESIGN.md 6r (UNPINNED)"})
+        ps = list(poses.values())
+        path = sum(float(np.linalg.norm(b[:3, 3] - a[:3, 3])) for a, b in zip(ps, ps[1:]))
+        n = max(len(rep["inliers"]), 1)
+        print(json.dumps({"scene": sid, "sweeps": len(poses), "failed_pairs": rep["failed"],
+                          "mean_inliers": round(sum(rep["inliers"]) / n, 3), "mean_residual": round(sum(rep["residual"]) / n, 9),
+                          "path_length": round(path, 6), "seconds": round(time.perf_counter() - t0, 3)}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

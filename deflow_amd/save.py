@@ -34,14 +34,17 @@ import torch
 
 from . import pairflow
 from .data import HDF5Dataset
+from .odometry import check_pose_source
 from .train import DEFAULTS, _TARGET_ALIASES
 
 FLOW_SUFFIX = ".flow.npz"
+POSE_SOURCES = ("auto", "file", "sidecar")
 GROUND_SOURCES = ("auto", "file", "sidecar", "online")
 OWN_DEFAULTS: Dict[str, Any] = {"checkpoint": None, "dataset_path": None, "res_name": None, "scenes": None, "ground_source": "auto",
-                                "half": False, "overwrite": False, "inference_dtype": None}
+                                "half": False, "overwrite": False, "inference_dtype": None, "pose_source": "auto"}
 USAGE = ("usage: python -m deflow_amd.save checkpoint=<ckpt> dataset_path=<dir of .h5 files> [res_name=<checkpoint file stem>] [scenes=a,b] "
-         "[batch_size=] [num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [inference_dtype=fp32|bf16]")
+         "[batch_size=] [num_workers=] [ground_source=auto|file|sidecar|online] [half=false] [overwrite=false] [inference_dtype=fp32|bf16] "
+         "[pose_source=auto|file|sidecar]")
 
 
 def _flag(k: str, v: str) -> bool:
@@ -76,6 +79,10 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         elif k == "ground_source":
             if v not in GROUND_SOURCES:
                 raise SystemExit(f"bad value for ground_source: {v!r} ({', '.join(GROUND_SOURCES)})")
+            opt[k] = v
+        elif k == "pose_source":                # where poses are read (HDF5Dataset(pose_source=...)); never written into the file's meta
+            if v not in POSE_SOURCES:
+                raise SystemExit(f"bad value for pose_source: {v!r} ({', '.join(POSE_SOURCES)})")
             opt[k] = v
         elif k == "inference_dtype":
             if v not in ("fp32", "bf16"):
@@ -163,9 +170,13 @@ class ScenePairs(HDF5Dataset):
     ground masks without its index file (and so without the step-back rule for a scene's last sweep).  ``ground_source="online"``: the
     items carry all-False masks; the caller computes them on the GPU."""
 
-    def __init__(self, directory: str, scene_id: str, ground_source: str = "auto", ground_sidecar: str = ".ground.npz"):
+    def __init__(self, directory: str, scene_id: str, ground_source: str = "auto", ground_sidecar: str = ".ground.npz",
+                 pose_source: str = "auto", pose_sidecar: Optional[str] = ".pose.npz"):
         if ground_source not in GROUND_SOURCES:
             raise ValueError(f"ground_source must be one of {', '.join(GROUND_SOURCES)}, got {ground_source!r}")
+        check_pose_source(pose_source, pose_sidecar)
+        self.pose_source, self.pose_sidecar = pose_source, pose_sidecar
+        self._pose_sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
         self.directory, self.ground_source, self.ground_sidecar = directory, ground_source, ground_sidecar
         self.dynamic_key, self.dynamic_sidecar = "", None           # the dynamic flags are not needed here
         self._sidecars: "OrderedDict[str, Optional[dict]]" = OrderedDict()
@@ -276,7 +287,7 @@ def main(argv=None, wrap=None) -> int:
             print(json.dumps({"scene": sid, "skipped": "flow file exists (overwrite=true replaces it)"}), flush=True)
             continue
         t0 = time.perf_counter()
-        pairs = ScenePairs(d, sid, opt["ground_source"])
+        pairs = ScenePairs(d, sid, opt["ground_source"], pose_source=opt["pose_source"])
         flows = save_scene(sweep_flow_for, pairs, int(cfg["batch_size"]), dev, half=opt["half"], online=online,
                            num_workers=int(cfg["num_workers"]), pinned=pinned)
         write_flow(out, flows, meta)

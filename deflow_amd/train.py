@@ -77,6 +77,24 @@ def split_metrics_impl(args: List[str]):
     return impl, rest
 
 
+POSE_SOURCES = ("auto", "file", "sidecar")
+
+
+def split_pose_source(args: List[str]):
+    """-> (pose_source, the other arguments).  ``pose_source=auto|file|sidecar``: where the scene files' sweeps take their poses from
+    (``HDF5Dataset(pose_source=...)``: the group's ``pose``, or ``<scene_id>.pose.npz`` of python -m deflow_amd.odometry).  Says where
+    poses are READ: like ``metrics_impl`` not a hyper-parameter, never saved.  The last one wins, default auto."""
+    src, rest = "auto", []
+    for a in args:
+        if a.lstrip("+").split("=", 1)[0] == "pose_source" and "=" in a:
+            src = a.split("=", 1)[1]
+        else:
+            rest.append(a)
+    if src not in POSE_SOURCES:
+        raise SystemExit(f"pose_source must be one of {', '.join(POSE_SOURCES)}, got {src!r}")
+    return src, rest
+
+
 def split_pseudo_flow(args: List[str]):
     """-> (res_name or None, the other arguments).  ``pseudo_flow=<res_name>``: training pairs whose scene files hold no ``flow`` take it
     from ``<scene_id>.<res_name>.flow.npz`` (``python -m deflow_amd.save``, e.g. with model=icpflow: pseudo labels for
@@ -207,6 +225,7 @@ def save_checkpoint(path: str, model, trainer, cfg, epoch: int, step: int):
 def main(argv=None):
     metrics_impl, args = split_metrics_impl(list(sys.argv[1:] if argv is None else argv))
     pseudo_flow, args = split_pseudo_flow(args)
+    pose_source, args = split_pose_source(args)
     cfg = parse_overrides(args)
     if pseudo_flow and cfg["train_data"] == "synthetic":
         raise SystemExit("pseudo_flow=<res_name> reads <scene_id>.<res_name>.flow.npz beside scene files: name them with train_data= or dataset_path=")
@@ -254,7 +273,7 @@ def main(argv=None):
             if world > 1:
                 dist.barrier()
             path = dst
-        ds = HDF5Dataset(path, flow_sidecar=pseudo_flow if shuffle else None)      # (pseudo labels are for training pairs only)
+        ds = HDF5Dataset(path, flow_sidecar=pseudo_flow if shuffle else None, pose_source=pose_source)      # (pseudo labels are for training pairs only)
         sampler = ShardedSampler(len(ds), rank, world, shuffle=shuffle, seed=int(cfg["seed"]))
         return SceneLoader(ds, B, sampler, device=dev, num_workers=max(0, int(cfg["num_workers"])), drop_last=shuffle), sampler
 

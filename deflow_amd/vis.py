@@ -22,18 +22,18 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .save import GROUND_SOURCES, ScenePairs, _Pinned, _flag, flow_path, read_flow
+from .save import GROUND_SOURCES, POSE_SOURCES, ScenePairs, _Pinned, _flag, flow_path, read_flow
 from .train import DEFAULTS, _TARGET_ALIASES
 
 PANELS = ("est", "gt", "err")
 OWN_DEFAULTS: Dict[str, Any] = {"dataset_path": None, "res_name": None, "flow_source": "file", "checkpoint": None, "scenes": None,
                                 "out_dir": None, "panels": None, "range": 51.2, "res": 0.1, "vmax": 1.0, "vmax_err": 0.5, "radius": 1,
                                 "legend": None, "every": 1, "batch_size": None, "overwrite": False, "ground_source": "auto",
-                                "inference_dtype": None}
+                                "inference_dtype": None, "pose_source": "auto"}
 USAGE = ("usage: python -m deflow_amd.vis dataset_path=<dir of .h5 files> res_name=<name> [flow_source=file|model] [checkpoint=<ckpt>] "
          "[scenes=a,b] [out_dir=<dataset_path>/vis_<res_name>] [panels=est,gt,err] [range=51.2] [res=0.1] [vmax=1.0] [vmax_err=0.5] "
          "[radius=1] [legend=<disc radius in pixels, 0 = none>] [every=1] [batch_size=] [overwrite=false] "
-         "[ground_source=auto|file|sidecar|online]")
+         "[ground_source=auto|file|sidecar|online] [pose_source=auto|file|sidecar]")
 
 
 def _num(k: str, v: str, kind, lo, hi=None):
@@ -87,6 +87,10 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         elif k == "ground_source":
             if v not in GROUND_SOURCES:
                 raise SystemExit(f"bad value for ground_source: {v!r} ({', '.join(GROUND_SOURCES)})")
+            opt[k] = v
+        elif k == "pose_source":
+            if v not in POSE_SOURCES:
+                raise SystemExit(f"bad value for pose_source: {v!r} ({', '.join(POSE_SOURCES)})")
             opt[k] = v
         elif k == "inference_dtype":
             if v not in ("fp32", "bf16"):
@@ -240,7 +244,7 @@ def main(argv=None) -> int:
     pinned = _Pinned()
     for sid in scenes:
         t0 = time.perf_counter()
-        pairs = ScenePairs(d, sid, opt["ground_source"])
+        pairs = ScenePairs(d, sid, opt["ground_source"], pose_source=opt["pose_source"])
         every = [i for i in range(0, len(pairs), opt["every"])]
         todo = [i for i in every if opt["overwrite"] or not os.path.exists(image_path(opt["out_dir"], sid, pairs.data_index[i][1]))]
         if sweep_flow is not None:

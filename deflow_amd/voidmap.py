@@ -210,14 +210,22 @@ def label_sweeps(lidars: Sequence[np.ndarray], poses: Sequence[np.ndarray], *, v
 
 def label_scene(h5_path: str, *, voxel: float = 0.1, range_xy: float = 51.2, z_half: float = 4.0, sensor_offset=SENSOR_OFFSET,
                 hit_margin: int = 2, erode: int = 1, max_range: float = 80.0, device="cuda", grid=None,
-                report: Optional[dict] = None) -> Dict[str, np.ndarray]:
+                report: Optional[dict] = None, pose_source: str = "auto", pose_sidecar: Optional[str] = ".pose.npz") -> Dict[str, np.ndarray]:
     """Flags of every sweep of a preprocessed scene file, sweeps taken in time order: {timestamp: uint8 [N]}, N the rows of that sweep's
-    ``lidar`` (ground rows included: they are cast like every other return)."""
+    ``lidar`` (ground rows included: they are cast like every other return).  pose_source / pose_sidecar: where the sweeps' poses come
+    from, as ``HDF5Dataset`` reads them ("auto": the group's ``pose``, else ``<scene_id>.pose.npz`` of python -m deflow_amd.odometry)."""
     from .h5scene import H5File
+    from .odometry import check_pose_source, load_pose_sidecar, sweep_pose
+    check_pose_source(pose_source, pose_sidecar)
+    directory, scene_id = os.path.dirname(h5_path) or ".", os.path.basename(h5_path)[:-3]
     with H5File(h5_path) as f:
         keys = sorted(f.keys(), key=int)
         lidars = [f[k]["lidar"].read() for k in keys]
-        poses = [f[k]["pose"].read() for k in keys]
+        side = None
+        if pose_source == "sidecar" or any("pose" not in f[k] for k in keys):
+            side = load_pose_sidecar(directory, scene_id, pose_sidecar)
+        poses = [sweep_pose(f[k], side, scene_id=scene_id, ts=k, pose_source=pose_source, pose_sidecar=pose_sidecar, directory=directory)
+                 for k in keys]
     flags = label_sweeps(lidars, poses, voxel=voxel, range_xy=range_xy, z_half=z_half, sensor_offset=sensor_offset, hit_margin=hit_margin,
                          erode=erode, max_range=max_range, device=device, grid=grid, report=report)
     return dict(zip(keys, flags))
@@ -239,6 +247,7 @@ def read_sidecar(path: str) -> Dict[str, np.ndarray]:
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
 CLI_DEFAULTS: Dict[str, Any] = {"data_dir": None, "scenes": None, "overwrite": False, "voxel": 0.1, "range_xy": 51.2, "z_half": 4.0,
                                 "sensor_offset": list(SENSOR_OFFSET), "hit_margin": 2, "erode": 1, "max_range": 80.0}
+POSE_SOURCES = ("auto", "file", "sidecar")      # pose_source=: where poses are read; not a parameter of the map, so not among the defaults
 
 
 def parse_args(argv: List[str]) -> Dict[str, Any]:
@@ -249,8 +258,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             raise SystemExit(f"expected key=value, got {a!r}")
         k, v = a.split("=", 1)
         k = k.lstrip("+")
-        if k not in CLI_DEFAULTS:
-            raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted(CLI_DEFAULTS))}")
+        if k not in CLI_DEFAULTS and k != "pose_source":
+            raise SystemExit(f"unknown key {k!r}; known: {', '.join(sorted((*CLI_DEFAULTS, 'pose_source')))}")
         try:
             if k == "data_dir":
                 cfg[k] = v
@@ -260,6 +269,10 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if v.lower() not in ("true", "false", "1", "0"):
                     raise ValueError(v)
                 cfg[k] = v.lower() in ("true", "1")
+            elif k == "pose_source":
+                if v not in POSE_SOURCES:
+                    raise ValueError(v)
+                cfg[k] = v
             elif k == "sensor_offset":
                 cfg[k] = [float(x) for x in v.strip("[]()").split(",")]
                 if len(cfg[k]) != 3:
@@ -272,7 +285,7 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
             raise SystemExit(f"bad value for {k}: {v!r}")
     if not cfg["data_dir"]:
         raise SystemExit("usage: python -m deflow_amd.voidmap data_dir=<dir> [scenes=a,b] [overwrite=false] [voxel=0.1] [range_xy=51.2] "
-                         "[z_half=4.0] [sensor_offset=1.35,0,1.64] [hit_margin=2] [erode=1] [max_range=80]")
+                         "[z_half=4.0] [sensor_offset=1.35,0,1.64] [hit_margin=2] [erode=1] [max_range=80] [pose_source=auto|file|sidecar]")
     return cfg
 
 
@@ -289,7 +302,8 @@ def main(argv=None) -> int:
             continue
         rep: Dict[str, Any] = {}
         t0 = time.perf_counter()
-        flags = label_scene(os.path.join(d, sid + ".h5"), report=rep, **{**params, "sensor_offset": tuple(params["sensor_offset"])})
+        flags = label_scene(os.path.join(d, sid + ".h5"), report=rep, pose_source=cfg.get("pose_source", "auto"),
+                            **{**params, "sensor_offset": tuple(params["sensor_offset"])})
         write_sidecar(out, flags, {**params, **{k: rep[k] for k in ("grid_min", "dims")}, "definition": "DESIGN.md 6c (UNPINNED)"})
         rows = sum(int(v.shape[0]) for v in flags.values())
         print(json.dumps({"scene": sid, "sweeps": len(flags), "rows": rows,

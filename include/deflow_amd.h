@@ -1139,6 +1139,55 @@ int df_refine_score(const float* x, const float* flow, const int32_t* count, con
 int df_refine_apply(const float* x, const float* flow, const int32_t* count, const int32_t* labels, const float* table,
                     const int32_t* anchor, int B, int Nc, int Kcap, float* flow_out, int32_t* rigid_id, void* stream);
 
+/* ------------------------------------------------------------------ sweep-to-sweep registration (odometry) ----
+ * UNPINNED: this project's own definition, not that of an existing LiDAR odometry; nothing about its accuracy on
+ * real sweeps has been measured.  A robust point-to-point ICP of whole clouds in 6 degrees of freedom that never returns to the host:
+ * T [B,16] f64 (row-major 4 x 4) with dst ~ R src + t maps the source sweep into the target sweep's frame -- with source = sweep k and
+ * target = sweep k + 1 it is the reference's pose_0to1 / ego_motion.  One iteration = df_reg_accumulate, then df_reg_solve.
+ *   rows         BOTH clouds are filed by df_nn_grid_build, each under its own grid: a row takes part by that entry's rule (< count,
+ *                finite, optional label > 0).  The source is filed so that its rows are walked in cell order and the lanes of a wave search
+ *                neighbouring target spans; its grid's range and cell do not enter the result's definition beyond that order.
+ *   subsample    stride in [1, 1024]: with [s, e) the span of sample b in the source's cell order (s = the start of its first cell, e =
+ *                the end of its last), the record at position p is USED when (p - s) % stride == 0.
+ *   row terms    R, t = T rounded to fp32.  q = R s + t in fp32: q.x = fma(R02, s.z, fma(R01, s.y, fma(R00, s.x, t.x))), y and z alike.
+ *                (d2, j) = the nearest participating target row of q: df_chamfer_nn's distance expression, tie rule (lowest row on equal
+ *                distances) and max_dist2 gate -- the same device function.  A used row with d2 <= max_dist2 is an INLIER with the
+ *                Geman-McClure weight w = fp32(u u), u = fp32(k2 / fp32(k2 + d2)), k2 = kernel^2.  Residual r = fp32(q - dst[j]); the
+ *                Jacobian of the left perturbation T <- exp(delta) T, delta = (omega, v): J = [ -[q]x , I ].
+ *   sums         per inlier, each term formed in fp32 and accumulated in float64; partial[b][block][32] f64 =
+ *                  0..20  the upper triangle of H = sum w J^T J, row by row (H00 .. H05, H11 .. H15, ..., H55)
+ *                  21..26 g = sum w J^T r = (sum w q x r, sum w r);  27 sum w;  28 sum fp32(w d2);  29 the inliers;  30, 31: 0.
+ *                Order: a lane holds its one row, the 64 lanes of a wave are added in an xor butterfly (32, 16, ..., 1), the block's 4
+ *                waves in wave order, one slab row per block of 256 cell-ordered positions; df_reg_solve adds the slab rows in ascending
+ *                block order.  No float atomics: two calls are bit-identical, and a sample's result depends neither on B nor on the other
+ *                samples at equal Ns.
+ *   solve        in float64.  planar != 0: rows and columns omega_x, omega_y of H are replaced by identity, their g entries by 0.
+ *                status 2: fewer than min_inliers inliers; 3: a Cholesky pivot of a solved-for row <= 1e-9 x the largest diagonal entry
+ *                of H (or not finite); T is untouched, bit for bit, in both.  Else 0: delta = -H^-1 g through the Cholesky factor and
+ *                T <- exp(delta) T with the closed-form SE(3) exponential: theta = |omega|, R = I + A K + B K^2, t = (I + B K + C K^2) v,
+ *                K = [omega]x, A = sin(theta) / theta, B = 2 sin^2(theta / 2) / theta^2, C = (theta - sin(theta)) / theta^3; for
+ *                theta < 1e-2 the series of A, B, C up to theta^6.  log [B,4] f32 = (inliers, sum w d2 / sum w (0 when sum w = 0),
+ *                |omega|, |v|), the last two 0 unless status 0.
+ * df_reg_ws_bytes(B, Ns): the bytes of partial = 256 B ceil(Ns / 256); DF_E_SHAPE (negative) for shapes the entries refuse.
+ * df_reg_accumulate: src_rng [B*Gs*Gs, 2] i32 and src_sorted [B*Ns, 4] f32: the source's grid; dst_rng [B*G*G, 2], dst_sorted [B*Nd, 4],
+ *   minx, miny, cell, G: the target's.  -> partial, every one of its B ceil(Ns / 256) 32 elements written.  The optional per-row outputs are
+ *   indexed by source ROW, not by cell position: q_out [B,Ns,3] f32, idx_out [B,Ns] i32, d2_out [B,Ns] f32, w_out [B,Ns] f32; a row that is
+ *   not used gets q = 0, idx = -1, d2 = +inf, w = 0, a used row that is no inlier its q and idx = -1, d2 = +inf, w = 0; every element of a
+ *   given output is written.  One thread per cell-ordered source position, 256 per block, grid (ceil(Ns / 256), B).
+ * df_reg_solve: partial [B,nblk,32], nblk = ceil(Ns / 256) -> T in place, log [B,4], status [B] i32; one 64-thread block per sample.  T
+ *   NULL: nothing is solved, log = (inliers, sum w d2 / sum w, 0, 0), status (then nullable) is not written.
+ * B outside 1..65535, Ns < 1, B Ns >= 2^30, Gs or G outside 1..4096, B G^2 >= 2^30, nblk < 1: DF_E_SHAPE.  NULL pointers, stride outside
+ * [1, 1024], a max_dist2 / k2 / cell that is not positive and finite, minx / miny not finite, min_inliers < 0: DF_E_ARG.  src_sorted /
+ * dst_sorted not 16-byte, partial / T not 8-byte aligned: DF_E_ALIGN.  No launch then.  No grid dimension comes from a device value; the
+ * entries never allocate or synchronise and read nothing back. */
+int64_t df_reg_ws_bytes(int B, int Ns);
+int df_reg_accumulate(const int32_t* src_rng, const float* src_sorted, int Gs, const int32_t* dst_rng, const float* dst_sorted, float minx,
+                      float miny, float cell, int G, int B, int Ns, int stride, const double* T, float max_dist2, float k2, double* partial,
+                      float* q_out /*nullable*/, int32_t* idx_out /*nullable*/, float* d2_out /*nullable*/, float* w_out /*nullable*/,
+                      void* stream);
+int df_reg_solve(const double* partial, int B, int nblk, int min_inliers, int planar, double* T /*nullable*/, float* log,
+                 int32_t* status /*nullable*/, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */

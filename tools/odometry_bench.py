@@ -1,0 +1,103 @@
+"""What the sweep-to-sweep registration costs on the GPU, measured: usage  python tools/odometry_bench.py [--batch 16] [--points 80000]
+[--grid 512] [--reps 20] [--out profiles/odometry_bench.json]
+
+At the configs[2] cloud (80 000 rows per cloud, 512 x 512; ~70 000 rows in range: the compact pc0 / pc1 of a real forward, the clouds
+tools/cluster_bench.py times), for B = 1 and B = --batch and stride 4 and 1, with device events after a warm-up (medians of --reps calls):
+
+  * one df_reg_accumulate at T = identity and the first level's gate (max_dist 2.0), next to the yardstick timed on the same grid in the
+    same run: df_chamfer_nn pc0 -> pc1 with the same gate -- the same search without the sums (and at every row: stride 1 is the like
+    for like comparison);
+  * one df_reg_solve;
+  * a whole default ``odometry.register`` (two grid builds, 24 accumulate + solve pairs, the final accumulate).
+
+A measuring tool, not a bench.py leg; needs the GPU (no fallback)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import deflow_amd
+from deflow_amd import chamfer, odometry
+from deflow_amd._lib import call, ptr, stream
+from deflow_amd.synth import synth_batch
+
+
+def timed(fn, reps):
+    """median of `reps` event-timed calls after three warm-up calls"""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return sorted(out)[len(out) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--points", type=int, default=80000)
+    ap.add_argument("--grid", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "odometry_bench.json"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "tools/odometry_bench.py measures on the GPU"
+    dev = torch.device("cuda")
+    H = a.grid
+    half = 0.1 * H
+    rng = [-half, -half, -3, half, half, 3]
+    grid_range = (rng[0], rng[1], rng[3], rng[4])
+    torch.manual_seed(0)
+    m = deflow_amd.DeFlow(voxel_size=[0.2, 0.2, 6], point_cloud_range=rng, grid_feature_size=[H, H]).to(dev).train()
+    with torch.no_grad():
+        st = m.forward_padded(synth_batch(a.batch, a.points, seed=20240116, grid_hw=(H, H), device=dev))
+    all0, all1 = st["p0"].points_c.contiguous(), st["p1"].points_c.contiguous()
+    cnt0, cnt1 = st["p0"].counts.contiguous(), st["p1"].counts.contiguous()
+    del m, st
+    cell, max_dist = odometry.DEFAULTS["cell"], odometry.LEVELS[0]
+    report = {"device": torch.cuda.get_device_name(0), "cell_m": cell, "max_dist_m": max_dist, "levels": list(odometry.LEVELS),
+              "iters": odometry.DEFAULTS["iters"], "reps": a.reps, "cases": []}
+    for B in sorted({1, a.batch}):
+        pc0, pc1, c0, c1 = all0[:B].contiguous(), all1[:B].contiguous(), cnt0[:B].contiguous(), cnt1[:B].contiguous()
+        Ns, Nd = pc0.shape[1], pc1.shape[1]
+        minx, miny, G = chamfer._grid(B, grid_range, cell)
+        s_rng, s_rows = odometry._file(pc0, c0, None, B, Ns, minx, miny, cell, G)
+        d_rng, d_rows = odometry._file(pc1, c1, None, B, Nd, minx, miny, cell, G)
+        d2 = torch.empty(B, Ns, dtype=torch.float32, device=dev)
+        idx = torch.empty(B, Ns, dtype=torch.int32, device=dev)
+        t_search = timed(lambda: call("df_chamfer_nn", ptr(pc0), ptr(c0), None, B, Ns, ptr(d_rng), ptr(d_rows), minx, miny, cell, G,
+                                      max_dist ** 2, ptr(d2), ptr(idx), None, stream()), a.reps)
+        nblk = (Ns + 255) // 256
+        partial = torch.empty(call("df_reg_ws_bytes", B, Ns) // 8, dtype=torch.float64, device=dev)
+        T = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1)
+        log = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        for stride in (4, 1):
+            t_acc = timed(lambda: call("df_reg_accumulate", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), minx, miny, cell, G, B, Ns,
+                                       stride, ptr(T), max_dist ** 2, (max_dist / 3) ** 2, ptr(partial), None, None, None, None, stream()),
+                          a.reps)
+            t_solve = timed(lambda: call("df_reg_solve", ptr(partial), B, nblk, 50, 0, None, ptr(log), None, stream()), a.reps)
+            t_reg = timed(lambda: odometry.register(pc0, c0, pc1, c1, xy_range=grid_range, stride=stride), a.reps)
+            _, info = odometry.register(pc0, c0, pc1, c1, xy_range=grid_range, stride=stride)
+            case = {"batch": B, "rows": Ns, "valid_rows": c0.tolist()[:4], "stride": stride, "chamfer_nn_same_gate_ms": round(t_search, 4),
+                    "reg_accumulate_ms": round(t_acc, 4), "accumulate_over_chamfer_nn": round(t_acc / t_search, 3),
+                    "reg_solve_ms": round(t_solve, 4), "register_default_ms": round(t_reg, 3), "inliers_at_identity": log[:4, 0].tolist(),
+                    "status": info["status"].tolist()[:4], "final_log_sample0": info["log"][0, -1].tolist()}
+            report["cases"].append(case)
+            print(json.dumps(case), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(report, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
