@@ -9,12 +9,14 @@ DESIGN.md "chamfer nearest neighbour"), and the scatter half of the backward is 
 CUDA tensors only, like the rest of the library: there is no CPU fallback."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from ._lib import call, ptr, stream
+from .args import labels, tensor, workspace
 
 # The grid: cells of CELL metres over GRID_RANGE (xmin, ymin, xmax, ymax); rows outside go to the clamped border cells, so the range
 # only affects speed, never the result.  CELL: see DESIGN.md (0.5 m: the 3 x 3 cells around a query guarantee a 0.5 m radius, which
@@ -32,19 +34,37 @@ def _grid(B: int, grid_range: Sequence[float], cell: float) -> Tuple[float, floa
     return xmin, ymin, G
 
 
-def _check(name: str, t: torch.Tensor, shape, dtype):
-    if not t.is_cuda:
-        raise TypeError(f"chamfer_nn: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"chamfer_nn: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+_check = functools.partial(tensor, "chamfer_nn")
 
 
-def _labels(name: str, lab: Optional[torch.Tensor], shape) -> Optional[torch.Tensor]:
-    if lab is None:
-        return None
-    if not lab.is_cuda or tuple(lab.shape) != tuple(shape) or lab.dtype.is_floating_point:
-        raise ValueError(f"chamfer_nn: {name} must be an integer CUDA tensor of shape {tuple(shape)}")
-    return lab.to(torch.int32).contiguous()
+class RowGrid:
+    """The xy search grid of ``B`` samples, sized once: ``file`` puts a cloud's rows under its cells (df_nn_grid_build), ``nn`` searches a
+    filed cloud (df_chamfer_nn).  A static cloud is filed once and searched as often as needed.  Checks nothing but the grid: the callers
+    have checked their tensors."""
+
+    def __init__(self, B: int, grid_range: Sequence[float], cell: float, device):
+        self.minx, self.miny, self.G = _grid(B, grid_range, cell)
+        self.B, self.cell, self.dev = int(B), float(cell), device
+
+    def file(self, points: torch.Tensor, count: torch.Tensor, label: Optional[torch.Tensor] = None):
+        """points [B,N,3] f32, count [B] i32, label [B,N] i32 or None -> (cell_rng [B G G, 2] i32, rows [B N, 4] f32)"""
+        B, N, G = self.B, int(points.shape[1]), self.G
+        cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=self.dev)
+        rows = torch.empty(B * N, 4, dtype=torch.float32, device=self.dev)
+        ws = workspace("df_nn_grid_ws_bytes", (B, N, G), self.dev, f"RowGrid: df_nn_grid_ws_bytes refused B = {B}, N = {N}, G = {G}")
+        call("df_nn_grid_build", ptr(points), ptr(count), ptr(label), B, N, self.minx, self.miny, self.cell, G, ptr(cell_rng), ptr(rows),
+             ptr(ws), stream())
+        return cell_rng, rows
+
+    def nn(self, query: torch.Tensor, qcount: torch.Tensor, qlabel: Optional[torch.Tensor], filed, max_dist2: float,
+           far_count: Optional[torch.Tensor] = None):
+        """query [B,Nq,3] f32, qcount [B] i32, qlabel [B,Nq] i32 or None, filed: what ``file`` returned -> d2 [B,Nq] f32, idx [B,Nq] i32"""
+        B, Nq = self.B, int(query.shape[1])
+        d2 = torch.empty(B, Nq, dtype=torch.float32, device=self.dev)
+        idx = torch.empty(B, Nq, dtype=torch.int32, device=self.dev)
+        call("df_chamfer_nn", ptr(query), ptr(qcount), ptr(qlabel), B, Nq, ptr(filed[0]), ptr(filed[1]), self.minx, self.miny, self.cell,
+             self.G, float(max_dist2), ptr(d2), ptr(idx), ptr(far_count), stream())
+        return d2, idx
 
 
 def chamfer_nn(query: torch.Tensor, qcount: torch.Tensor, ref: torch.Tensor, rcount: torch.Tensor,
@@ -57,32 +77,23 @@ def chamfer_nn(query: torch.Tensor, qcount: torch.Tensor, ref: torch.Tensor, rco
     index on equal distances); d2 = +inf, idx = -1 where that distance exceeds max_dist2, no ref row takes part or the query row does
     not.  No host synchronisation, no gradient (ChamferDis / losses.seflow_loss build theirs on top).
     far_count: optional i32[1] the search adds the number of queries to that had to look past the 3 x 3 cells around their own."""
-    if query.dim() != 3 or ref.dim() != 3 or query.shape[2] != 3 or ref.shape[2] != 3 or query.shape[0] != ref.shape[0]:
-        raise ValueError(f"chamfer_nn: query [B,Nq,3] and ref [B,Nr,3] expected, got {tuple(query.shape)} and {tuple(ref.shape)}")
-    B, Nq, _ = query.shape
-    Nr = ref.shape[1]
+    qs, rs = tuple(getattr(query, "shape", ())), tuple(getattr(ref, "shape", ()))
+    if len(qs) != 3 or len(rs) != 3 or qs[2] != 3 or rs[2] != 3 or qs[0] != rs[0]:
+        raise ValueError(f"chamfer_nn: query [B,Nq,3] and ref [B,Nr,3] expected, got {qs} and {rs}")
+    B, Nq, Nr = qs[0], qs[1], rs[1]
     if B == 0 or Nq == 0 or Nr == 0:
         raise ValueError("chamfer_nn: empty batch or zero padded rows")
     if not (max_dist2 >= 0):
         raise ValueError(f"chamfer_nn: max_dist2 must be >= 0 (inf allowed), got {max_dist2}")
-    _check("query", query, (B, Nq, 3), torch.float32)
-    _check("ref", ref, (B, Nr, 3), torch.float32)
-    _check("qcount", qcount, (B,), torch.int32)
-    _check("rcount", rcount, (B,), torch.int32)
+    _check("query", query, torch.float32, (B, Nq, 3))
+    _check("ref", ref, torch.float32, (B, Nr, 3))
+    _check("qcount", qcount, torch.int32, (B,))
+    _check("rcount", rcount, torch.int32, (B,))
     query, ref = query.detach().contiguous(), ref.detach().contiguous()
-    ql, rl = _labels("qlabel", qlabel, (B, Nq)), _labels("rlabel", rlabel, (B, Nr))
-    minx, miny, G = _grid(B, grid_range, cell)
-    dev = query.device
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    rows = torch.empty(B * Nr, 4, dtype=torch.float32, device=dev)
-    ws = torch.empty(call("df_nn_grid_ws_bytes", B, Nr, G), dtype=torch.uint8, device=dev)
-    call("df_nn_grid_build", ptr(ref), ptr(rcount), ptr(rl), B, Nr, minx, miny, float(cell), G, ptr(cell_rng), ptr(rows), ptr(ws),
-         stream())
-    d2 = torch.empty(B, Nq, dtype=torch.float32, device=dev)
-    idx = torch.empty(B, Nq, dtype=torch.int32, device=dev)
-    call("df_chamfer_nn", ptr(query), ptr(qcount), ptr(ql), B, Nq, ptr(cell_rng), ptr(rows), minx, miny, float(cell), G,
-         float(max_dist2), ptr(d2), ptr(idx), ptr(far_count), stream())
-    return d2, idx
+    ql = labels("chamfer_nn", "qlabel", qlabel, (B, Nq), f"must be an integer CUDA tensor of shape {(B, Nq)}")
+    rl = labels("chamfer_nn", "rlabel", rlabel, (B, Nr), f"must be an integer CUDA tensor of shape {(B, Nr)}")
+    grid = RowGrid(B, grid_range, cell, query.device)
+    return grid.nn(query, qcount, ql, grid.file(ref, rcount, rl), max_dist2, far_count)
 
 
 def chamfer_bwd(query: torch.Tensor, ref: torch.Tensor, idx: torch.Tensor, g: torch.Tensor, dquery: Optional[torch.Tensor],

@@ -11,13 +11,15 @@ hold one, otherwise the void map of ``voidmap.py`` (UNPINN
 CUDA tensors only, like the rest of the library: there is no CPU fallback.  Nothing here reads a device value back."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from ._lib import call, ptr, stream
-from .chamfer import GRID_RANGE, _grid
+from .args import tensor, workspace
+from .chamfer import GRID_RANGE, RowGrid
 
 # cell = max(CELL_SLACK * eps, extent / 4096): with cell >= eps the 3 x 3 cells around a row hold every row within eps.  The slack covers
 # the rounding of the cell coordinates (< 1e-3 cell at G <= 4096, the bound csrc/chamfer.hip's search uses): two rows eps apart in x never
@@ -25,19 +27,14 @@ from .chamfer import GRID_RANGE, _grid
 CELL_SLACK = 1.0025
 
 
-def _check(name: str, t: torch.Tensor, shape, dtype):
-    if not t.is_cuda:
-        raise TypeError(f"dbscan: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"dbscan: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+_check = functools.partial(tensor, "dbscan")
 
 
 def _flags(name: str, f: Optional[torch.Tensor], shape) -> Optional[torch.Tensor]:
     """a per-row flag (bool or integer, non-zero = set) as the i32 0 / 1 tensor the kernels read"""
     if f is None:
         return None
-    if not f.is_cuda:
-        raise TypeError(f"dbscan: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    _check(name, f)
     if tuple(f.shape) != tuple(shape) or f.dtype.is_floating_point:
         raise ValueError(f"dbscan: {name} must be a bool or integer CUDA tensor of shape {tuple(shape)}")
     return (f != 0).to(torch.int32).contiguous()
@@ -45,9 +42,10 @@ def _flags(name: str, f: Optional[torch.Tensor], shape) -> Optional[torch.Tensor
 
 def _run(points: torch.Tensor, count: torch.Tensor, mask, dynamic, eps: float, min_points: int, min_cluster_size: int,
          min_dynamic_frac: float, grid_range, status: Optional[torch.Tensor]):
-    if points.dim() != 3 or points.shape[2] != 3:
-        raise ValueError(f"dbscan: points [B,N,3] expected, got {tuple(points.shape)}")
-    B, N, _ = points.shape
+    shape = tuple(getattr(points, "shape", ()))
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"dbscan: points [B,N,3] expected, got {shape}")
+    B, N, _ = shape
     if B == 0 or N == 0:
         raise ValueError("dbscan: empty batch or zero padded rows")
     if not (eps > 0 and math.isfinite(eps)):
@@ -56,25 +54,23 @@ def _run(points: torch.Tensor, count: torch.Tensor, mask, dynamic, eps: float, m
         raise ValueError(f"dbscan: min_points and min_cluster_size must be >= 1, got {min_points} and {min_cluster_size}")
     if not (min_dynamic_frac >= 0 and math.isfinite(min_dynamic_frac)):
         raise ValueError(f"dbscan: min_dynamic_frac must be a finite fraction >= 0, got {min_dynamic_frac}")
-    _check("points", points, (B, N, 3), torch.float32)
-    _check("count", count, (B,), torch.int32)
+    _check("points", points, torch.float32, (B, N, 3))
+    _check("count", count, torch.int32, (B,))
     if status is not None:
-        _check("status", status, (1,), torch.int32)
+        _check("status", status, torch.int32, (1,))
     points = points.detach().contiguous()
     m, d = _flags("mask", mask, (B, N)), _flags("dynamic", dynamic, (B, N))
     rg = GRID_RANGE if grid_range is None else grid_range
     xmin, ymin, xmax, ymax = (float(v) for v in rg)
     cell = max(CELL_SLACK * float(eps), max(xmax - xmin, ymax - ymin) / 4096.0)
-    minx, miny, G = _grid(B, rg, cell)
     dev = points.device
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    rows = torch.empty(B * N, 4, dtype=torch.float32, device=dev)
-    gws = torch.empty(call("df_nn_grid_ws_bytes", B, N, G), dtype=torch.uint8, device=dev)
-    ws = torch.empty(call("df_dbscan_ws_bytes", B, N), dtype=torch.uint8, device=dev)
+    grid = RowGrid(B, rg, cell, dev)
+    minx, miny, G = grid.minx, grid.miny, grid.G
+    cell_rng, rows = grid.file(points, count, m)
+    ws = workspace("df_dbscan_ws_bytes", (B, N), dev, f"dbscan: df_dbscan_ws_bytes refused B = {B}, N = {N}")
     labels = torch.empty(B, N, dtype=torch.int32, device=dev)
     n_clusters = torch.empty(B, dtype=torch.int32, device=dev)
     s = stream()
-    call("df_nn_grid_build", ptr(points), ptr(count), ptr(m), B, N, minx, miny, cell, G, ptr(cell_rng), ptr(rows), ptr(gws), s)
     call("df_dbscan_core", ptr(cell_rng), ptr(rows), B, N, minx, miny, cell, G, float(eps), int(min_points), ptr(ws), s)
     call("df_dbscan_link", ptr(cell_rng), B, N, minx, miny, cell, G, float(eps), ptr(status), ptr(ws), s)
     call("df_dbscan_finish", ptr(cell_rng), ptr(d), B, N, minx, miny, cell, G, float(eps), int(min_cluster_size), float(min_dynamic_frac),
@@ -105,8 +101,7 @@ def dynamic_cluster_labels(points: torch.Tensor, count: torch.Tensor, dynamic: t
     -> labels [B,N] i32, n_clusters [B] i32, status i32[1] (see dbscan; left on the device)."""
     if dynamic is None:
         raise ValueError("dynamic_cluster_labels: the per-row dynamic flag is required (dbscan clusters without one)")
-    if not points.is_cuda:
-        raise TypeError("dbscan: points must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    _check("points", points)
     status = torch.zeros(1, dtype=torch.int32, device=points.device)
     labels, n_clusters = _run(points, count, None, dynamic, eps, min_points, min_cluster_size, min_dynamic_frac, grid_range, status)
     return labels, n_clusters, status

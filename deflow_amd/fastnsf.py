@@ -18,8 +18,8 @@ import torch
 
 from . import pairflow
 from ._lib import call, ptr, stream
+from .args import tensor as _tensor, workspace
 from .nsfp import MAX_DEPTH, init_params, mlp_backward, mlp_forward, param_stride
-from .pairflow import _tensor
 from .pairopt import Loop, OptimisedPairModel, mean_and_weight, pair_clouds, rows
 
 R_MAX = 255
@@ -80,11 +80,9 @@ def dt_build(ref: torch.Tensor, count: torch.Tensor, *, origin: Sequence[float],
     _tensor("dt_build", "count", count, torch.int32, (B,), ref.device)
     _grid_args("dt_build", origin, cell, dims, radius)
     GX, GY, GZ = dims
-    need = int(call("df_dt_ws_bytes", B, GX, GY, GZ, radius))
-    if need < 0:
-        raise ValueError(f"dt_build: dims: df_dt_ws_bytes refused B = {B}, dims = {tuple(dims)}, radius = {radius}")
+    ws = workspace("df_dt_ws_bytes", (B, GX, GY, GZ, radius), ref.device,
+                   f"dt_build: dims: df_dt_ws_bytes refused B = {B}, dims = {tuple(dims)}, radius = {radius}")
     dt2 = torch.empty(B, GZ, GY, GX, dtype=torch.uint16, device=ref.device)
-    ws = torch.empty(need, dtype=torch.uint8, device=ref.device)
     call("df_dt_build", ptr(ref.detach().contiguous()), ptr(count.contiguous()), B, N, origin[0], origin[1], origin[2], cell, GX, GY, GZ,
          radius, ptr(dt2), ptr(ws), stream())
     return dt2

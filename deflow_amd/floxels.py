@@ -19,8 +19,8 @@ import torch
 
 from . import pairflow
 from ._lib import call, ptr, stream
+from .args import tensor as _tensor, workspace
 from .fastnsf import R_MAX, DataTerm, dt_grid, f32
-from .pairflow import _tensor
 from .pairopt import Loop, OptimisedPairModel, pair_clouds, rows, sample_sum
 
 # every default of section 6n; all of them are arguments of floxels_optimize and Floxels, and `floxels_<name>=` keys of the commands
@@ -90,16 +90,14 @@ def vox_plan(x: torch.Tensor, count: torch.Tensor, *, origin: Sequence[float], v
         raise ValueError(f"vox_plan: voxel must be positive and finite, got {voxel!r}")
     VX, VY, VZ = _dims("vox_plan", dims, B, N)
     NV, NC = VX * VY * VZ, (VX - 1) * (VY - 1) * (VZ - 1)
-    need = int(call("df_vox_plan_ws_bytes", B, N, VX, VY, VZ))
-    if need < 0:
-        raise ValueError(f"vox_plan: dims: df_vox_plan_ws_bytes refused B = {B}, N = {N}, dims = {tuple(dims)}")
+    ws = workspace("df_vox_plan_ws_bytes", (B, N, VX, VY, VZ), dev,
+                   f"vox_plan: dims: df_vox_plan_ws_bytes refused B = {B}, N = {N}, dims = {tuple(dims)}")
     cell = torch.empty(B, N, dtype=torch.int32, device=dev)
     frac = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
     idx_sorted = torch.empty(B * N, dtype=torch.int32, device=dev)
     cell_rng = torch.empty(B * NC, 2, dtype=torch.int32, device=dev)
     active = torch.empty(B, NV, dtype=torch.uint8, device=dev)
     pairs = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     call("df_vox_plan", ptr(x.detach().contiguous()), ptr(count.contiguous()), B, N, origin[0], origin[1], origin[2], float(voxel), VX, VY, VZ,
          ptr(cell), ptr(frac), ptr(idx_sorted), ptr(cell_rng), ptr(active), ptr(pairs), ptr(ws), stream())
     return {"cell": cell, "frac": frac, "idx_sorted": idx_sorted, "cell_rng": cell_rng, "active": active, "pairs": pairs,
@@ -182,8 +180,6 @@ def check_params(p: Dict[str, object]) -> Dict[str, object]:
     pairflow.whole_cells(fn, out, R_MAX)
     pairflow.flag(fn, out, "graph")
     return out
-
-
 
 
 def _grids(fn: str, grid_range, p: Dict[str, object]):

@@ -13,6 +13,7 @@ missed); a return no higher than ``tol`` above its cell's ground height is groun
 ``<scene_id>.ground.npz`` beside every scene, which ``HDF5Dataset`` picks up when the file has no ``ground_mask``."""
 from __future__ import annotations
 
+import functools
 import json
 import math
 import os
@@ -24,6 +25,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
+from .args import tensor
 
 SIDECAR_SUFFIX = ".ground.npz"
 EMPTY = 2 ** 31 - 1
@@ -38,13 +40,7 @@ def _quant(v: float, lo: float, k) -> np.float32:
         return np.float32(np.float32(np.float32(v) - np.float32(lo)) * np.float32(k))
 
 
-def _check(name: str, t: torch.Tensor, shape, dtype, device):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"GroundSegmenter: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.device != device:
-        raise ValueError(f"GroundSegmenter: {name} is on {t.device}, the segmenter is on {device}")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"GroundSegmenter: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+_check = functools.partial(tensor, "GroundSegmenter", other="the segmenter is")
 
 
 class GroundSegmenter:
@@ -143,13 +139,12 @@ class GroundSegmenter:
     def segment(self, points: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
         """One sweep per sample: points [B,N,3] f32 with count [B] i32 valid leading rows -> bool [B,N], True = ground.  Afterwards
         ``cell_min``, ``height`` and ``observed`` hold this sweep's maps."""
-        if not isinstance(points, torch.Tensor) or not points.is_cuda:
-            raise TypeError("GroundSegmenter: points must be a CUDA tensor (deflow_amd has no CPU fallback)")
+        _check("points", points)
         if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] != self.batch or points.shape[1] < 1:
             raise ValueError(f"GroundSegmenter: points [{self.batch},N,3] with N >= 1 expected, got {tuple(points.shape)}")
         B, N, _ = points.shape
-        _check("points", points, (B, N, 3), torch.float32, self.device)
-        _check("count", count, (B,), torch.int32, self.device)
+        _check("points", points, torch.float32, (B, N, 3), self.device)
+        _check("count", count, torch.int32, (B,), self.device)
         points, count = points.detach().contiguous(), count.contiguous()
         mask = torch.empty(B, N, dtype=torch.uint8, device=self.device)
         s = stream()

@@ -18,9 +18,10 @@ import torch
 
 from . import fastnsf, pairflow
 from ._lib import call, ptr, stream
+from .args import integer, merged, nonneg, positive, tensor as _tensor
 from .fastnsf import FastNsf, dt_grid, optimize_net
-from .pairflow import _tensor
 from .pairopt import pair_clouds, rows, sample_sum
+from .rigid import segments
 
 P_MAX = 16               # pairs per row (csrc/iso.hip: ISO_PMAX)
 
@@ -41,13 +42,13 @@ def params_from_command(given: Dict[str, str]) -> Dict[str, object]:
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
     fn = "mbnsf_optimize"
-    out = pairflow.merged(fn, DEFAULTS, p)
+    out = merged(fn, DEFAULTS, p)
     out.update(fastnsf.check_params({k: out[k] for k in fastnsf.DEFAULTS}, fn=fn))
-    pairflow.nonneg(fn, out, "rigid_weight", finite=True)
-    pairflow.positive(fn, out, "rigid_delta", finite=True)
-    pairflow.positive(fn, out, "eps", finite=True)
+    nonneg(fn, out, "rigid_weight", finite=True)
+    positive(fn, out, "rigid_delta", finite=True)
+    positive(fn, out, "eps", finite=True)
     for k, hi in (("rigid_pairs", P_MAX), ("min_points", 1 << 30), ("min_cluster_size", 1 << 30), ("max_cluster_points", 1 << 30)):
-        pairflow.integer(fn, out, k, 1, hi, finite=True)
+        integer(fn, out, k, 1, hi, finite=True)
     return out
 
 
@@ -88,23 +89,12 @@ def iso_plan(x: torch.Tensor, count: torch.Tensor, labels: torch.Tensor, *, pair
     else:
         _tensor("iso_plan", "status", status, torch.int32, (1,), dev)
     x, count = x.detach().contiguous(), count.contiguous()
-    counted = torch.arange(N, device=dev)[None] < count.clamp(0, N)[:, None]
-    ext = torch.zeros(B, N + 1, dtype=torch.int32, device=dev)          # the labels, then one column of zeros: df_rigid_segments' N1 = 1
-    lab = torch.where(counted, labels, torch.zeros_like(labels)).contiguous()
-    ext[:, :N] = lab
-    need = int(call("df_rigid_segments_ws_bytes", B, N, 1, K))
-    if need < 0:
-        raise ValueError(f"iso_plan: x: df_rigid_segments_ws_bytes refused B = {B}, N = {N}, kcap = {K}")
-    ws = torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
-    seg_off = torch.empty(B, 2 * K + 1, dtype=torch.int32, device=dev)
-    seg_rows = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
+    lab, seg_off, seg_rows = segments("iso_plan", "x", labels, count, K, status)
     nbr = torch.empty(B, N, 2 * pairs, dtype=torch.int32, device=dev)
     r0 = torch.empty(B, N, 2 * pairs, dtype=torch.float32, device=dev)
     n_pairs = torch.empty(B, dtype=torch.int32, device=dev)
-    s = stream()
-    call("df_rigid_segments", ptr(ext), B, N, 1, K, ptr(seg_off), ptr(seg_rows), ptr(status), ptr(ws), s)
     call("df_iso_plan", ptr(x), ptr(count), ptr(lab), ptr(seg_off), ptr(seg_rows), B, N, K, pairs, max_cluster_points, ptr(nbr), ptr(r0),
-         ptr(n_pairs), s)
+         ptr(n_pairs), stream())
     return nbr, r0, n_pairs
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
+from .args import tensor, ws_bytes
 from .metrics import BUCKET_WIDTH, META_CLASSES, N_BUCKETS, N_CATEGORIES, OfficialMetrics
 
 SUMMARY_KEYS = ("EPE", "AccS", "AccR", "n", "EPE_FD", "EPE_FS", "EPE_BS", "EPE_3way")
@@ -30,11 +31,7 @@ def rows_per_block() -> int:
 
 
 def _tensor(name: str, t, device) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"DeviceMetrics: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.device != device:
-        raise ValueError(f"DeviceMetrics: {name} is on {t.device}, the accumulator is on {device}")
-    return t
+    return tensor("DeviceMetrics", name, t, device=device, other="the accumulator is")
 
 
 def _rows3(name: str, t, B: int, N: int, device) -> torch.Tensor:
@@ -81,9 +78,8 @@ class DeviceMetrics:
     # ---- feeding ------------------------------------------------------------------------------------------------------------------------
     def reserve(self, B: int, N: int) -> None:
         """make the workspace large enough for [B, N] batches (update() does it itself, but never inside a stream capture)"""
-        need = int(call("df_metrics_ws_bytes", int(B), int(N)))
-        if need < 0:
-            raise ValueError(f"DeviceMetrics: 1 <= B <= 65535, N >= 1 and B * N < 2^31 expected, got B = {B}, N = {N}")
+        need = ws_bytes("df_metrics_ws_bytes", (int(B), int(N)),
+                        f"DeviceMetrics: 1 <= B <= 65535, N >= 1 and B * N < 2^31 expected, got B = {B}, N = {N}")
         if self._ws is None or self._ws.numel() * 8 < need:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("DeviceMetrics: the workspace would have to grow inside a stream capture; call reserve(B, N) or one "

@@ -18,7 +18,8 @@ import torch
 
 from . import pairflow
 from ._lib import call, ptr, stream
-from .chamfer import CELL, GRID_RANGE, _grid, chamfer_bwd
+from .args import tensor, workspace
+from .chamfer import CELL, GRID_RANGE, RowGrid, chamfer_bwd
 from .pairopt import BETAS, EPS, Loop, OptimisedPairModel, mean_and_weight, pair_clouds  # noqa: F401  (nsfp.BETAS / EPS stay importable)
 
 WIDTH = 128
@@ -87,7 +88,7 @@ def check_params(p: Dict[str, object]) -> Dict[str, object]:
 
 
 # ---- the MLP -------------------------------------------------------------------------------------------------------------------------
-_tensor = functools.partial(pairflow._tensor, other="x is")     # (a device mismatch is reported against x)
+_tensor = functools.partial(tensor, other="x is")     # (a device mismatch is reported against x)
 
 
 def _mlp_args(fn: str, x, count, params, depth) -> Tuple[int, int, int]:
@@ -136,10 +137,7 @@ def mlp_backward(x: torch.Tensor, count: torch.Tensor, params: torch.Tensor, dep
         if tuple(dparams.stride()) != tuple(params.stride()) or dparams.data_ptr() % 16:
             raise ValueError(f"mlp_backward: dparams must have the strides of params {tuple(params.stride())} and be 16-byte aligned, got "
                              f"{tuple(dparams.stride())}")
-    need = int(call("df_mlp_ws_bytes", B, N, depth))
-    if need < 0:
-        raise ValueError(f"mlp_backward: x: df_mlp_ws_bytes refused B = {B}, N = {N}, depth = {depth}")
-    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+    ws = workspace("df_mlp_ws_bytes", (B, N, depth), x.device, f"mlp_backward: x: df_mlp_ws_bytes refused B = {B}, N = {N}, depth = {depth}")
     dx = torch.empty_like(x) if need_dx else None
     call("df_mlp_bwd", ptr(x), ptr(count.contiguous()), ptr(params), stride, ptr(acts), ptr(dy), B, N, depth, ptr(dparams), ptr(dx),
          ptr(ws), stream())
@@ -164,32 +162,6 @@ class FlowMLPFn(torch.autograd.Function):
         return dx, None, (dparams if ctx.needs_input_grad[2] else None), None
 
 
-# ---- the searches ----------------------------------------------------------------------------------------------------------------------
-class _Search:
-    """df_nn_grid_build / df_chamfer_nn with the grid of a static cloud kept between iterations"""
-
-    def __init__(self, B: int, grid_range: Sequence[float], cell: float, max_dist2: float, device):
-        self.B, self.cell, self.max_dist2, self.dev = B, float(cell), float(max_dist2), device
-        self.minx, self.miny, self.G = _grid(B, grid_range, cell)
-
-    def build(self, ref: torch.Tensor, rcount: torch.Tensor, rlabel: torch.Tensor):
-        B, Nr = self.B, ref.shape[1]
-        cell_rng = torch.empty(B * self.G * self.G, 2, dtype=torch.int32, device=self.dev)
-        rows = torch.empty(B * Nr, 4, dtype=torch.float32, device=self.dev)
-        ws = torch.empty(call("df_nn_grid_ws_bytes", B, Nr, self.G), dtype=torch.uint8, device=self.dev)
-        call("df_nn_grid_build", ptr(ref), ptr(rcount), ptr(rlabel), B, Nr, self.minx, self.miny, self.cell, self.G, ptr(cell_rng),
-             ptr(rows), ptr(ws), stream())
-        return cell_rng, rows
-
-    def nn(self, query: torch.Tensor, qcount: torch.Tensor, qlabel: torch.Tensor, grid):
-        B, Nq = self.B, query.shape[1]
-        d2 = torch.empty(B, Nq, dtype=torch.float32, device=self.dev)
-        idx = torch.empty(B, Nq, dtype=torch.int32, device=self.dev)
-        call("df_chamfer_nn", ptr(query), ptr(qcount), ptr(qlabel), B, Nq, ptr(grid[0]), ptr(grid[1]), self.minx, self.miny, self.cell,
-             self.G, self.max_dist2, ptr(d2), ptr(idx), None, stream())
-        return d2, idx
-
-
 def nsfp_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *,
                   grid_range: Optional[Sequence[float]] = None, init: Optional[torch.Tensor] = None, **params):
     """pc0s [B,N0,3] f32 (first sweep, in the second sweep's frame) with count0 [B] i32 valid leading rows; pc1 [B,N1,3], count1 alike.
@@ -210,8 +182,8 @@ def nsfp_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, c
     with torch.no_grad():
         arena = start.to(pair.dev)[None].repeat(B, 1, 1).contiguous()       # [B][2][S]
         loop = Loop(arena, x0, p)
-        search = _Search(B, GRID_RANGE if grid_range is None else grid_range, CELL, p["trunc_d2"], pair.dev)
-        grid_p1, grid_p0 = search.build(x1, n1, l1), search.build(x0, n0, l0)
+        search, t2 = RowGrid(B, GRID_RANGE if grid_range is None else grid_range, CELL, pair.dev), p["trunc_d2"]
+        grid_p1, grid_p0 = search.file(x1, n1, l1), search.file(x0, n0, l0)
         fpar, gpar = arena[:, 0], arena[:, 1]
         last = {"nn": None}
 
@@ -221,10 +193,10 @@ def nsfp_optimize(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tensor, c
             W = x0 + F
             G, acts_g = mlp_forward(W, n0, gpar, depth)
             C = W - G
-            d_w1, i_w1 = search.nn(W, n0, l0, grid_p1)
-            d_1w, i_1w = search.nn(x1, n1, l1, search.build(W, n0, l0))
-            d_c0, i_c0 = search.nn(C, n0, l0, grid_p0)
-            d_0c, i_0c = search.nn(x0, n0, l0, search.build(C, n0, l0))
+            d_w1, i_w1 = search.nn(W, n0, l0, grid_p1, t2)
+            d_1w, i_1w = search.nn(x1, n1, l1, search.file(W, n0, l0), t2)
+            d_c0, i_c0 = search.nn(C, n0, l0, grid_p0, t2)
+            d_0c, i_0c = search.nn(x0, n0, l0, search.file(C, n0, l0), t2)
             (a, ga), (b, gb), (c, gc), (d, gd) = (mean_and_weight(v) for v in (d_w1, d_1w, d_c0, d_0c))
             loss = (a + b) + (c + d)
             dW, dC = torch.zeros_like(W), torch.zeros_like(C)

@@ -14,6 +14,7 @@ value back); ``register_sweeps`` / ``scene_poses`` run it over the consecutive s
 pick up (``pose_source``) when the file has no ``pose``."""
 from __future__ import annotations
 
+import functools
 import json
 import math
 import os
@@ -25,7 +26,8 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
-from .chamfer import GRID_RANGE, _grid
+from .args import labels, tensor
+from .chamfer import GRID_RANGE, RowGrid
 
 SIDECAR_SUFFIX = ".pose.npz"
 POSE_SOURCES = ("auto", "file", "sidecar")
@@ -36,21 +38,7 @@ DEFAULTS: Dict[str, Any] = {"xy_range": GRID_RANGE, "cell": 1.0, "stride": 4, "l
 SCENE_DEFAULTS: Dict[str, Any] = {"min_range": 3.0, "max_range": 51.2}
 
 
-def _tensor(name: str, t, dtype, shape, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"register: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"register: {name} is on {t.device}, src on {device}")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"register: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-
-
-def _mask(name: str, m, shape, device) -> Optional[torch.Tensor]:
-    if m is None:
-        return None
-    if not isinstance(m, torch.Tensor) or not m.is_cuda or m.device != device or tuple(m.shape) != tuple(shape) or m.dtype.is_floating_point:
-        raise ValueError(f"register: {name} must be an integer or bool CUDA tensor of shape {tuple(shape)} on {device}")
-    return m.to(torch.int32).contiguous()
+_tensor = functools.partial(tensor, "register", other="src")
 
 
 def schedule(levels, iters) -> List[Tuple[float, int]]:
@@ -69,16 +57,6 @@ def schedule(levels, iters) -> List[Tuple[float, int]]:
     if not out:
         raise ValueError("register: levels must name at least one level")
     return out
-
-
-def _file(points, count, mask, B, N, minx, miny, cell, G):
-    """df_nn_grid_build of one cloud -> (cell_rng, rows)"""
-    dev = points.device
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    rows = torch.empty(B * N, 4, dtype=torch.float32, device=dev)
-    ws = torch.empty(call("df_nn_grid_ws_bytes", B, N, G), dtype=torch.uint8, device=dev)
-    call("df_nn_grid_build", ptr(points), ptr(count), ptr(mask), B, N, minx, miny, float(cell), G, ptr(cell_rng), ptr(rows), ptr(ws), stream())
-    return cell_rng, rows
 
 
 def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_d: torch.Tensor, *, init: Optional[torch.Tensor] = None,
@@ -111,7 +89,7 @@ def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_
         raise ValueError(f"register: min_inliers must be an integer >= 0, got {min_inliers!r}")
     plan = schedule(levels, iters)
     try:
-        minx, miny, G = _grid(B, xy_range, cell)
+        grid = RowGrid(B, xy_range, cell, dev)
     except (TypeError, ValueError):
         raise ValueError(f"register: bad grid (xy_range {tuple(xy_range)}, cell {cell})") from None
     if init is None:
@@ -123,10 +101,11 @@ def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_
         T = init.detach().to(torch.float64).contiguous().clone()
     src, dst = src.detach().contiguous(), dst.detach().contiguous()
     count_s, count_d = count_s.contiguous(), count_d.contiguous()
-    ms, md = _mask("mask_s", mask_s, (B, Ns), dev), _mask("mask_d", mask_d, (B, Nd), dev)
+    ms = labels("register", "mask_s", mask_s, (B, Ns), f"must be an integer or bool CUDA tensor of shape {(B, Ns)} on {dev}", dev)
+    md = labels("register", "mask_d", mask_d, (B, Nd), f"must be an integer or bool CUDA tensor of shape {(B, Nd)} on {dev}", dev)
 
-    s_rng, s_rows = _file(src, count_s, ms, B, Ns, minx, miny, cell, G)
-    d_rng, d_rows = _file(dst, count_d, md, B, Nd, minx, miny, cell, G)
+    (s_rng, s_rows), (d_rng, d_rows) = grid.file(src, count_s, ms), grid.file(dst, count_d, md)
+    minx, miny, G = grid.minx, grid.miny, grid.G
     nblk = (Ns + 255) // 256
     slab = call("df_reg_ws_bytes", B, Ns)
     if slab <= 0:

@@ -9,12 +9,12 @@ from __future__ import annotations
 
 import ast
 import importlib
-import math
 from typing import Dict, Iterable, NamedTuple, Optional, Tuple
 
 import torch
 
 from ._lib import call, ptr, stream
+from .args import flag, integer, merged, nonneg, positive  # noqa: F401
 
 
 class Entry(NamedTuple):
@@ -120,77 +120,13 @@ def usage(e: Entry) -> str:
             f"[overwrite=false] [voxel_size=] [point_cloud_range=] {own}" + ("\n" + e.memory if e.memory else ""))
 
 
-# ---- the parameter checks of the models' check_params ----------------------------------------------------------------------------------
-# fn: the function the message names; out: the parameter dict, checked and converted in place.  finite=True (mbnsf, floxels): a value that
-# is no finite number is reported as such, whatever else the key asks for.
-def merged(fn: str, defaults: Dict[str, object], p: Dict[str, object]) -> Dict[str, object]:
-    out = dict(defaults)
-    for k, v in p.items():
-        if k not in defaults:
-            raise ValueError(f"{fn}: unknown parameter {k!r}; known: {', '.join(sorted(defaults))}")
-        out[k] = v
-    return out
-
-
-def _number(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, float))
-
-
-def _finite(fn: str, k: str, v) -> None:
-    if not _number(v) or not math.isfinite(v):
-        raise ValueError(f"{fn}: {k} must be a finite number, got {v!r}")
-
-
-def integer(fn: str, out: dict, k: str, lo: int, hi: int, finite: bool = False) -> None:
-    v = out[k]
-    if finite:
-        _finite(fn, k, v)
-    if not _number(v) or int(v) != v or not lo <= int(v) <= hi:
-        raise ValueError(f"{fn}: {k} must be an integer in [{lo}, {hi}], got {v!r}")
-    out[k] = int(v)
-
-
-def positive(fn: str, out: dict, k: str, finite: bool = False) -> None:
-    v = out[k]
-    if finite:
-        _finite(fn, k, v)
-    if not _number(v) or not (math.isfinite(v) and v > 0):
-        raise ValueError(f"{fn}: {k} must be positive and finite, got {v!r}")
-    out[k] = float(v)
-
-
-def nonneg(fn: str, out: dict, k: str, finite: bool = False) -> None:
-    v = out[k]
-    if finite:
-        _finite(fn, k, v)
-    if not _number(v) or not (math.isfinite(v) and v >= 0):
-        raise ValueError(f"{fn}: {k} must be finite and >= 0, got {v!r}")
-    out[k] = float(v)
-
-
-def flag(fn: str, out: dict, k: str) -> None:
-    if not isinstance(out[k], bool):
-        raise ValueError(f"{fn}: {k} must be True or False, got {out[k]!r}")
-
-
+# ---- the parameter checks of the models' check_params are deflow_amd.args' (imported above: pairflow.integer and the rest resolve) ----------
 def whole_cells(fn: str, out: dict, r_max: int) -> None:
     """trunc is 1 to r_max cells (the distance transform's radius, deflow_amd.fastnsf)"""
     R = int(round(out["trunc"] / out["cell"]))
     if not 1 <= R <= r_max or abs(R * out["cell"] - out["trunc"]) > 1e-6 * out["trunc"]:
         raise ValueError(f"{fn}: trunc must be a whole number of cells, 1 to {r_max} of them, got trunc = {out['trunc']}, "
                          f"cell = {out['cell']}")
-
-
-def _tensor(fn: str, name: str, t, dtype, shape=None, device=None, other: str = "not"):
-    """a CUDA tensor of that dtype (and shape, and device) or an error naming the argument; other: how the message names the device
-    it compares with"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"{fn}: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"{fn}: {name} is on {t.device}, {other} on {device}")
-    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{fn}: {name} must be {dtype}" + (f" of shape {tuple(shape)}" if shape is not None else "") +
-                         f", got {t.dtype} {tuple(t.shape)}")
 
 
 # ---- the models' base ------------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ Only ``Loop.update`` and the graph capture need the GPU: the snapshot / freeze /
 arena is on, and tests/test_pairopt_cpu.py runs it on the host."""
 from __future__ import annotations
 
+import functools
 import math
 from types import SimpleNamespace
 from typing import Callable, Dict, Tuple
@@ -15,20 +16,13 @@ from typing import Callable, Dict, Tuple
 import torch
 
 from ._lib import call, ptr, stream
-from .pairflow import PairFlowModel, _tensor
+from .args import cloud, tensor as _tensor
+from .pairflow import PairFlowModel
 
 BETAS, EPS = (0.9, 0.999), 1e-8
 
 
-def rows(fn: str, name: str, t) -> Tuple[int, int]:
-    """(B, N) of a CUDA float32 cloud [B,N,3], or an error of ``fn`` naming the argument"""
-    _tensor(fn, name, t, torch.float32)
-    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{fn}: {name} must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got {tuple(t.shape)}")
-    B, N = int(t.shape[0]), int(t.shape[1])
-    if B > 65535 or 3 * B * N >= 2 ** 31:
-        raise ValueError(f"{fn}: {name}: 1 <= B <= 65535 and 3 * B * N < 2^31 expected, got B = {B}, N = {N}")
-    return B, N
+rows = functools.partial(cloud, rows_limit=3)    # (B, N) of a CUDA float32 cloud [B,N,3], or an error of ``fn`` naming the argument
 
 
 def pair_clouds(fn: str, pc0s, count0, pc1, count1, second: bool = False) -> SimpleNamespace:

@@ -16,14 +16,17 @@ arguments> [refine_*=]`` prints the same tables for the refined flow.
 CUDA tensors only, like the rest of the library: there is no CPU fallback.  Nothing here reads a device value back."""
 from __future__ import annotations
 
+import functools
 import sys
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import pairflow
+from . import pairflow, rigid
 from ._lib import call, ptr, stream
-from .pairflow import _tensor
+from .args import cloud, flag, integer, merged, nonneg, positive
+from .args import tensor as _tensor
+from .chamfer import CELL, GRID_RANGE, RowGrid
 
 STATUS_NAMES = {0: "empty", 1: "snapped", 2: "too few rows", 3: "too large", 4: "inlier fraction", 5: "yaw / displacement", 6: "static",
                 7: "worse against the second sweep"}
@@ -46,15 +49,15 @@ USAGE = ("usage: python -m deflow_amd.refine save|eval <that command's arguments
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
     fn = "rigid_refine"
-    out = pairflow.merged(fn, DEFAULTS, p)
-    pairflow.integer(fn, out, "iters", 0, MAX_ITERS, finite=True)
+    out = merged(fn, DEFAULTS, p)
+    integer(fn, out, "iters", 0, MAX_ITERS, finite=True)
     for k in ("min_points", "min_cluster_size", "min_rows", "max_cluster_points"):
-        pairflow.integer(fn, out, k, 1, 1 << 30, finite=True)
+        integer(fn, out, k, 1, 1 << 30, finite=True)
     for k in ("eps", "delta", "inlier_dist", "check_trunc"):
-        pairflow.positive(fn, out, k, finite=True)
+        positive(fn, out, k, finite=True)
     for k in ("min_inlier_frac", "max_yaw", "max_disp", "static_disp", "static_yaw", "check_tol"):
-        pairflow.nonneg(fn, out, k, finite=True)
-    pairflow.flag(fn, out, "check")
+        nonneg(fn, out, k, finite=True)
+    flag(fn, out, "check")
     return out
 
 
@@ -68,15 +71,7 @@ def kcap(Nc: int, min_cluster_size: int) -> int:
     return max(int(Nc) // int(min_cluster_size), 1)
 
 
-def _rows(name: str, t) -> Tuple[int, int]:
-    fn = "rigid_refine"
-    _tensor(fn, name, t, torch.float32)
-    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{fn}: {name} must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got {tuple(t.shape)}")
-    B, N = int(t.shape[0]), int(t.shape[1])
-    if B > 65535 or 3 * B * N >= 2 ** 31:
-        raise ValueError(f"{fn}: {name}: 1 <= B <= 65535 and 3 * B * N < 2^31 expected, got B = {B}, N = {N}")
-    return B, N
+_rows = functools.partial(cloud, "rigid_refine", rows_limit=3)
 
 
 def _slots(name: str, K, Nc: int) -> int:
@@ -87,7 +82,7 @@ def _slots(name: str, K, Nc: int) -> int:
 
 def segments(labels: torch.Tensor, count: torch.Tensor, K: int, status: Optional[torch.Tensor] = None):
     """labels [B,Nc] i32, count [B] i32 -> (labels with the rows behind the count set to 0, seg_off [B, 2K + 1] i32, seg_rows [B, Nc + 1]
-    i32): df_rigid_segments with N0 = Nc, N1 = 1 on the labels followed by one zero column, as ``mbnsf.iso_plan`` gets its lists."""
+    i32): ``rigid.segments``, with the arguments checked."""
     fn = "rigid_refine"
     _tensor(fn, "labels", labels, torch.int32)
     if labels.dim() != 2:
@@ -96,20 +91,7 @@ def segments(labels: torch.Tensor, count: torch.Tensor, K: int, status: Optional
     dev = labels.device
     _tensor(fn, "count", count, torch.int32, (B,), dev)
     _slots("kcap", K, Nc)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    counted = torch.arange(Nc, device=dev)[None] < count.clamp(0, Nc)[:, None]
-    lab = torch.where(counted, labels, torch.zeros_like(labels)).contiguous()
-    ext = torch.zeros(B, Nc + 1, dtype=torch.int32, device=dev)
-    ext[:, :Nc] = lab
-    need = int(call("df_rigid_segments_ws_bytes", B, Nc, 1, K))
-    if need < 0:
-        raise ValueError(f"{fn}: labels: df_rigid_segments_ws_bytes refused B = {B}, Nc = {Nc}, kcap = {K}")
-    ws = torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
-    seg_off = torch.empty(B, 2 * K + 1, dtype=torch.int32, device=dev)
-    seg_rows = torch.empty(B, Nc + 1, dtype=torch.int32, device=dev)
-    call("df_rigid_segments", ptr(ext), B, Nc, 1, K, ptr(seg_off), ptr(seg_rows), ptr(status), ptr(ws), stream())
-    return lab, seg_off, seg_rows
+    return rigid.segments(fn, "labels", labels, count, K, status)
 
 
 def _lists(fn: str, B: int, Nc: int, K: int, dev, seg_off, seg_rows):
@@ -190,22 +172,9 @@ def refine_apply(x: torch.Tensor, count: torch.Tensor, flow: torch.Tensor, label
 def _nn_d2(queries: Sequence[torch.Tensor], count: torch.Tensor, ref: torch.Tensor, rcount: torch.Tensor, max_dist2: float,
            grid_range: Optional[Sequence[float]]):
     """squared distance of every row of each query cloud to its nearest row of ``ref``: ONE df_nn_grid_build, one df_chamfer_nn per query"""
-    from .chamfer import CELL, GRID_RANGE, _grid
-    B, Nq, Nr = int(ref.shape[0]), int(queries[0].shape[1]), int(ref.shape[1])
-    dev = ref.device
-    minx, miny, G = _grid(B, GRID_RANGE if grid_range is None else grid_range, CELL)
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    rows = torch.empty(B * Nr, 4, dtype=torch.float32, device=dev)
-    ws = torch.empty(call("df_nn_grid_ws_bytes", B, Nr, G), dtype=torch.uint8, device=dev)
-    call("df_nn_grid_build", ptr(ref), ptr(rcount), None, B, Nr, minx, miny, float(CELL), G, ptr(cell_rng), ptr(rows), ptr(ws), stream())
-    out = []
-    for q in queries:
-        d2 = torch.empty(B, Nq, dtype=torch.float32, device=dev)
-        idx = torch.empty(B, Nq, dtype=torch.int32, device=dev)
-        call("df_chamfer_nn", ptr(q), ptr(count), None, B, Nq, ptr(cell_rng), ptr(rows), minx, miny, float(CELL), G, float(max_dist2), ptr(d2),
-             ptr(idx), None, stream())
-        out.append(d2)
-    return out
+    grid = RowGrid(int(ref.shape[0]), GRID_RANGE if grid_range is None else grid_range, CELL, ref.device)
+    filed = grid.file(ref, rcount)
+    return [grid.nn(q, count, None, filed, max_dist2)[0] for q in queries]
 
 
 def rigid_refine(x: torch.Tensor, count: torch.Tensor, flow: torch.Tensor, pc1: torch.Tensor, count1: torch.Tensor, *,

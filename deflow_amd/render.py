@@ -8,35 +8,21 @@ UNPINNED): what ``python -m deflow_amd.vis`` draws with.
 CUDA tensors only: there is no CPU fallback (tests/helpers/render_ref.py restates the definition in numpy).  Nothing is read back."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import Sequence, Tuple
 
 import torch
 
 from ._lib import call, ptr, stream
+from .args import cloud, tensor
 
 MAX_SIDE = 4096
 MAX_RADIUS = 4
 
 
-def _check(name: str, t, shape, dtype, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"render: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"render: {name} is on {t.device}, points is on {device}")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"render: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-
-
-def _rows(name: str, t) -> Tuple[int, int]:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"render: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"render: {name} must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got {t.dtype} {tuple(t.shape)}")
-    B, N = int(t.shape[0]), int(t.shape[1])
-    if B > 65535 or B * N >= 2 ** 31:
-        raise ValueError(f"render: {name}: B <= 65535 and B * N < 2^31 expected, got B = {B}, N = {N}")
-    return B, N
+_check = functools.partial(tensor, "render", other="points is")
+_rows = functools.partial(cloud, "render", rows_limit=1)
 
 
 def _number(name: str, v, positive: bool) -> float:
@@ -75,9 +61,9 @@ def render_rows(points: torch.Tensor, count: torch.Tensor, vec: torch.Tensor, cl
     allocator and is zeroed on the current stream: the op can be captured in a graph.  Two calls are bit-identical."""
     B, N = _rows("points", points)
     dev = points.device
-    _check("vec", vec, (B, N, 3), torch.float32, dev)
-    _check("cls", cls, (B, N), torch.uint8, dev)
-    _check("count", count, (B,), torch.int32, dev)
+    _check("vec", vec, torch.float32, (B, N, 3), dev)
+    _check("cls", cls, torch.uint8, (B, N), dev)
+    _check("count", count, torch.int32, (B,), dev)
     if not isinstance(view, (tuple, list)) or len(view) != 3:
         raise ValueError(f"render: view must be (xmin, ymin, inv_res), got {view!r}")
     xmin, ymin = _number("view[0] (xmin)", view[0], False), _number("view[1] (ymin)", view[1], False)
@@ -99,9 +85,9 @@ def flow_vectors(raw: torch.Tensor, count_raw: torch.Tensor, flow: torch.Tensor,
     padding); ``render_rows`` skips them."""
     B, N = _rows("raw", raw)
     dev = raw.device
-    _check("count_raw", count_raw, (B,), torch.int32, dev)
-    _check("flow", flow, (B, N, 3), torch.float32, dev)
-    _check("T", T, (B, 4, 4), torch.float32, dev)
+    _check("count_raw", count_raw, torch.int32, (B,), dev)
+    _check("flow", flow, torch.float32, (B, N, 3), dev)
+    _check("T", T, torch.float32, (B, 4, 4), dev)
     raw, T = raw.detach().contiguous(), T.contiguous()
     moved = torch.empty_like(raw)
     pose_flow = torch.empty_like(raw)

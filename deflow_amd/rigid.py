@@ -10,6 +10,7 @@ point pairs (integer counters: exact), refines yaw + translation by a fixed numb
 CUDA tensors only, like the rest of the library: there is no CPU fallback.  Nothing here reads a device value back."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import Dict, Optional, Sequence
 
@@ -17,6 +18,7 @@ import torch
 
 from . import pairflow
 from ._lib import call, ptr, stream
+from .args import cloud, integer, merged, nonneg, positive, tensor, workspace
 from .pairflow import PairFlowModel  # noqa: F401  (rigid.PairFlowModel stays importable)
 
 STATUS_NAMES = {0: "empty", 1: "registered", 2: "one-sided", 3: "too large", 4: "inlier fraction", 5: "no vote / yaw / displacement"}
@@ -46,47 +48,45 @@ def vote_radius(max_disp: float, vote_bin: float) -> int:
 
 def check_params(p: Dict[str, object]) -> Dict[str, object]:
     """validated copy of a parameter dict (ValueError naming the argument); launches nothing"""
-    out = pairflow.merged("rigid_cluster_flow", DEFAULTS, p)
-    for k in ("min_points", "min_cluster_size", "min_side", "max_cluster_points", "vote_cap", "icp_cap"):
-        if isinstance(out[k], bool) or int(out[k]) != out[k] or int(out[k]) < 1:
-            raise ValueError(f"rigid_cluster_flow: {k} must be an integer >= 1, got {out[k]!r}")
-        out[k] = int(out[k])
+    fn = "rigid_cluster_flow"
+    out = merged(fn, DEFAULTS, p)
+    for k in ("min_points", "min_cluster_size", "min_side", "max_cluster_points"):
+        integer(fn, out, k, 1, 1 << 30)
     for k in ("vote_cap", "icp_cap"):
-        if out[k] > 1 << 20:
-            raise ValueError(f"rigid_cluster_flow: {k} must be at most 2^20, got {out[k]}")
-    if isinstance(out["icp_iters"], bool) or int(out["icp_iters"]) != out["icp_iters"] or not 0 <= int(out["icp_iters"]) <= 1024:
-        raise ValueError(f"rigid_cluster_flow: icp_iters must be an integer in [0, 1024], got {out['icp_iters']!r}")
-    out["icp_iters"] = int(out["icp_iters"])
+        integer(fn, out, k, 1, 1 << 20)
+    integer(fn, out, "icp_iters", 0, 1024)
     for k in ("eps", "vote_bin", "icp_max_dist"):
-        if not (math.isfinite(float(out[k])) and float(out[k]) > 0):
-            raise ValueError(f"rigid_cluster_flow: {k} must be positive and finite, got {out[k]!r}")
-        out[k] = float(out[k])
+        positive(fn, out, k)
     for k in ("max_disp", "max_yaw", "min_inlier_frac"):
-        if not (math.isfinite(float(out[k])) and float(out[k]) >= 0):
-            raise ValueError(f"rigid_cluster_flow: {k} must be finite and >= 0, got {out[k]!r}")
-        out[k] = float(out[k])
+        nonneg(fn, out, k)
     if vote_radius(out["max_disp"], out["vote_bin"]) > R_MAX:
         raise ValueError(f"rigid_cluster_flow: max_disp / vote_bin must be at most {R_MAX} bins, got max_disp = {out['max_disp']}, "
                          f"vote_bin = {out['vote_bin']}")
     return out
 
 
-def _check(name: str, t, shape, dtype, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"rigid_cluster_flow: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"rigid_cluster_flow: {name} is on {t.device}, pc0s is on {device}")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"rigid_cluster_flow: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+_check = functools.partial(tensor, "rigid_cluster_flow", other="pc0s is")
 
 
-def _cloud(name: str, t) -> int:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"rigid_cluster_flow: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"rigid_cluster_flow: {name} must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got "
-                         f"{t.dtype} {tuple(t.shape)}")
-    return int(t.shape[1])
+def segments(fn: str, name: str, labels: torch.Tensor, count: torch.Tensor, K: int, status: Optional[torch.Tensor] = None):
+    """The ordered row lists of ONE cloud's clusters: labels [B,N] i32 (checked by the caller; 0: no cluster, 1..K), count [B] i32 ->
+    (labels with the rows behind the count set to 0, seg_off [B, 2K + 1] i32, seg_rows [B, N + 1] i32): df_rigid_segments with N0 = N,
+    N1 = 1 on the labels followed by one zero column.  status: i32[1] that is added to for a label outside [0, K].  fn / name: the
+    function and the argument a refusal names."""
+    B, N = int(labels.shape[0]), int(labels.shape[1])
+    dev = labels.device
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    counted = torch.arange(N, device=dev)[None] < count.clamp(0, N)[:, None]
+    lab = torch.where(counted, labels, torch.zeros_like(labels)).contiguous()
+    ext = torch.zeros(B, N + 1, dtype=torch.int32, device=dev)
+    ext[:, :N] = lab
+    ws = workspace("df_rigid_segments_ws_bytes", (B, N, 1, K), dev,
+                   f"{fn}: {name}: df_rigid_segments_ws_bytes refused B = {B}, N = {N}, kcap = {K}")
+    seg_off = torch.empty(B, 2 * K + 1, dtype=torch.int32, device=dev)
+    seg_rows = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
+    call("df_rigid_segments", ptr(ext), B, N, 1, K, ptr(seg_off), ptr(seg_rows), ptr(status), ptr(ws), stream())
+    return lab, seg_off, seg_rows
 
 
 def kcap(N0: int, N1: int, min_cluster_size: int) -> int:
@@ -122,14 +122,14 @@ def rigid_cluster_flow(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tens
     histogram [B,Kcap,2R+1,2R+1] i32 as a sixth value.  Kcap = max((N0+N1) // min_cluster_size, 1).
     labels: the joint labels [B,N0+N1] i32 when the caller has them already (else cluster.dbscan computes them); grid_range as in dbscan.
     No host synchronisation; workspaces come from torch's allocator; two calls are bit-identical."""
-    N0, N1 = _cloud("pc0s", pc0s), _cloud("pc1", pc1)
-    B, dev = int(pc0s.shape[0]), pc0s.device
+    (B, N0), (_, N1) = cloud("rigid_cluster_flow", "pc0s", pc0s), cloud("rigid_cluster_flow", "pc1", pc1)
+    dev = pc0s.device
     if pc1.shape[0] != B:
         raise ValueError(f"rigid_cluster_flow: pc1 must have the batch size of pc0s ({B}), got {tuple(pc1.shape)}")
     if pc1.device != dev:
         raise ValueError(f"rigid_cluster_flow: pc1 is on {pc1.device}, pc0s is on {dev}")
-    _check("count0", count0, (B,), torch.int32, dev)
-    _check("count1", count1, (B,), torch.int32, dev)
+    _check("count0", count0, torch.int32, (B,), dev)
+    _check("count1", count1, torch.int32, (B,), dev)
     p = check_params({"eps": eps, "min_points": min_points, "min_cluster_size": min_cluster_size, "min_side": min_side,
                       "max_cluster_points": max_cluster_points, "vote_cap": vote_cap, "vote_bin": vote_bin, "max_disp": max_disp,
                       "icp_cap": icp_cap, "icp_iters": icp_iters, "icp_max_dist": icp_max_dist, "min_inlier_frac": min_inlier_frac,
@@ -140,7 +140,7 @@ def rigid_cluster_flow(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tens
     K = kcap(N0, N1, p["min_cluster_size"])
     R = vote_radius(p["max_disp"], p["vote_bin"])
     if labels is not None:
-        _check("labels", labels, (B, N), torch.int32, dev)
+        _check("labels", labels, torch.int32, (B, N), dev)
     pc0s, pc1 = pc0s.detach().contiguous(), pc1.detach().contiguous()
     count0, count1 = count0.contiguous(), count1.contiguous()
     status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -149,12 +149,7 @@ def rigid_cluster_flow(pc0s: torch.Tensor, count0: torch.Tensor, pc1: torch.Tens
                               min_cluster_size=p["min_cluster_size"], grid_range=grid_range, status=status)
     labels = labels.contiguous()
 
-    def ws(entry, *a):
-        need = int(call(entry, *a))
-        if need < 0:
-            raise ValueError(f"rigid_cluster_flow: {entry} refused B = {B}, N0 = {N0}, N1 = {N1}")
-        return torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
-
+    ws = lambda entry, *a: workspace(entry, a, dev, f"rigid_cluster_flow: {entry} refused B = {B}, N0 = {N0}, N1 = {N1}")
     seg_ws, icp_ws = ws("df_rigid_segments_ws_bytes", B, N0, N1, K), ws("df_rigid_icp_ws_bytes", B, N0, N1)
     seg_off = torch.empty(B, 2 * K + 1, dtype=torch.int32, device=dev)
     seg_rows = torch.empty(B, N, dtype=torch.int32, device=dev)

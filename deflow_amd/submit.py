@@ -14,6 +14,7 @@ only (``eval_mask``), as fp16, in Arrow's column layout with the boolean column 
 CUDA tensors only: there is no CPU fallback (tests/helpers/submit_ref.py restates the body layout in numpy)."""
 from __future__ import annotations
 
+import functools
 import os
 import zipfile
 from typing import Dict, List, Optional, Tuple
@@ -22,6 +23,7 @@ import torch
 
 from . import sweeps
 from ._lib import call, ptr, stream
+from .args import cloud, tensor
 from .data import HDF5Dataset
 from .feather import COLUMNS
 
@@ -36,15 +38,7 @@ def body_stride(N: int) -> int:
     return S
 
 
-def _cuda(name: str, t, shape, dtypes, device=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"submit: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"submit: {name} is on {t.device}, flow_est is on {device}")
-    if t.dtype not in dtypes or tuple(t.shape) != tuple(shape):
-        want = " or ".join(str(d) for d in dtypes)
-        raise ValueError(f"submit: {name} must be {want} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    return t.contiguous()
+_cuda = functools.partial(tensor, "submit", other="flow_est is")
 
 
 def pack_rows(flow_est: torch.Tensor, dynamic: torch.Tensor, eval_mask: torch.Tensor, count_raw: torch.Tensor, version: int):
@@ -54,17 +48,12 @@ def pack_rows(flow_est: torch.Tensor, dynamic: torch.Tensor, eval_mask: torch.Te
     behind them are not written.  Reads nothing back; two calls are bit-identical."""
     if version not in COLUMNS:
         raise ValueError(f"submit: version must be 1 or 2, got {version!r}")
-    if not isinstance(flow_est, torch.Tensor) or not flow_est.is_cuda:
-        raise TypeError("submit: flow_est must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if flow_est.dtype != torch.float32 or flow_est.dim() != 3 or flow_est.shape[2] != 3 or flow_est.shape[0] < 1 or flow_est.shape[1] < 1:
-        raise ValueError("submit: flow_est must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got "
-                         f"{flow_est.dtype} {tuple(flow_est.shape)}")
-    B, N = int(flow_est.shape[0]), int(flow_est.shape[1])
+    B, N = cloud("submit", "flow_est", flow_est)
     dev = flow_est.device
     flow_est = flow_est.detach().contiguous()
-    dynamic = _cuda("dynamic", dynamic, (B, N), (torch.uint8, torch.bool), dev)
-    eval_mask = _cuda("eval_mask", eval_mask, (B, N), (torch.bool, torch.uint8), dev)
-    count_raw = _cuda("count_raw", count_raw, (B,), (torch.int32,), dev)
+    dynamic = _cuda("dynamic", dynamic, (torch.uint8, torch.bool), (B, N), dev).contiguous()
+    eval_mask = _cuda("eval_mask", eval_mask, (torch.bool, torch.uint8), (B, N), dev).contiguous()
+    count_raw = _cuda("count_raw", count_raw, torch.int32, (B,), dev).contiguous()
     if dynamic.dtype == torch.bool:
         dynamic = dynamic.view(torch.uint8)
     S = body_stride(N)

@@ -13,11 +13,13 @@
 CUDA tensors only: there is no CPU fallback (tests/helpers/sweep_flow_ref.py restates the definition in numpy)."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+import functools
+from typing import Dict, List, Optional
 
 import torch
 
 from ._lib import call, ptr, stream
+from .args import cloud, tensor, workspace
 
 
 def rows_per_block() -> int:
@@ -25,42 +27,18 @@ def rows_per_block() -> int:
     return int(call("df_sweep_rows_per_block"))
 
 
-def _check(name: str, t, shape, dtype, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"sweeps: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"sweeps: {name} is on {t.device}, raw is on {device}")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"sweeps: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-
-
-def _raw(raw) -> Tuple[int, int]:
-    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
-        raise TypeError("sweeps: raw must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if raw.dtype != torch.float32 or raw.dim() != 3 or raw.shape[2] != 3 or raw.shape[0] < 1 or raw.shape[1] < 1:
-        raise ValueError(f"sweeps: raw must be torch.float32 of shape (B, N, 3) with B >= 1 and N >= 1, got {raw.dtype} {tuple(raw.shape)}")
-    return int(raw.shape[0]), int(raw.shape[1])
+_check = functools.partial(tensor, "sweeps", other="raw is")
+_raw = functools.partial(cloud, "sweeps", "raw")
 
 
 def _mask(name: str, t, shape, device) -> torch.Tensor:
     """bool or uint8 [B,N] -> u8 (non-zero = set)"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"sweeps: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if t.device != device:
-        raise ValueError(f"sweeps: {name} is on {t.device}, raw is on {device}")
-    if t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"sweeps: {name} must be torch.bool or torch.uint8 of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    t = t.contiguous()
+    t = _check(name, t, (torch.bool, torch.uint8), shape, device).contiguous()
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
 def _workspace(entry: str, B: int, N: int, device) -> torch.Tensor:
-    """the entry's scratch, from torch's caching allocator like the outputs: safe across streams, and under a stream capture it comes
-    from the graph's own pool"""
-    need = int(call(entry + "_ws_bytes", B, N))
-    if need < 0:
-        raise ValueError(f"sweeps: 1 <= B <= 65535, N >= 1 and B * N < 2^31 expected, got B = {B}, N = {N}")
-    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
+    return workspace(entry + "_ws_bytes", (B, N), device, f"sweeps: 1 <= B <= 65535, N >= 1 and B * N < 2^31 expected, got B = {B}, N = {N}")
 
 
 def compact_rows(raw: torch.Tensor, count_raw: torch.Tensor, drop: torch.Tensor):
@@ -70,7 +48,7 @@ def compact_rows(raw: torch.Tensor, count_raw: torch.Tensor, drop: torch.Tensor)
     dropped and padded rows; kept [B] i32.  Reads nothing back."""
     B, N = _raw(raw)
     dev = raw.device
-    _check("count_raw", count_raw, (B,), torch.int32, dev)
+    _check("count_raw", count_raw, torch.int32, (B,), dev)
     drop = _mask("drop", drop, (B, N), dev)
     raw, count_raw = raw.detach().contiguous(), count_raw.contiguous()
     ws = _workspace("df_sweep_compact", B, N, dev)
@@ -89,17 +67,16 @@ def compose_flow(raw: torch.Tensor, count_raw: torch.Tensor, T: torch.Tensor, po
     back; two calls are bit-identical."""
     B, N = _raw(raw)
     dev = raw.device
-    _check("count_raw", count_raw, (B,), torch.int32, dev)
-    _check("T", T, (B, 4, 4), torch.float32, dev)
-    _check("pos_of", pos_of, (B, N), torch.int32, dev)
-    if not isinstance(flow, torch.Tensor) or not flow.is_cuda:
-        raise TypeError("sweeps: flow must be a CUDA tensor (deflow_amd has no CPU fallback)")
+    _check("count_raw", count_raw, torch.int32, (B,), dev)
+    _check("T", T, torch.float32, (B, 4, 4), dev)
+    _check("pos_of", pos_of, torch.int32, (B, N), dev)
+    _check("flow", flow)
     if flow.dim() != 3 or flow.shape[0] != B or flow.shape[1] < 1 or flow.shape[2] != 3:
         raise ValueError(f"sweeps: flow must be torch.float32 of shape ({B}, Nc, 3) with Nc >= 1, got {flow.dtype} {tuple(flow.shape)}")
     Nc = int(flow.shape[1])
-    _check("flow", flow, (B, Nc, 3), torch.float32, dev)
-    _check("idx_c", idx_c, (B, Nc), torch.int64, dev)
-    _check("counts", counts, (B,), torch.int32, dev)
+    _check("flow", flow, torch.float32, (B, Nc, 3), dev)
+    _check("idx_c", idx_c, torch.int64, (B, Nc), dev)
+    _check("counts", counts, torch.int32, (B,), dev)
     raw, flow = raw.detach().contiguous(), flow.detach().contiguous()
     count_raw, T, pos_of, idx_c, counts = count_raw.contiguous(), T.contiguous(), pos_of.contiguous(), idx_c.contiguous(), counts.contiguous()
     ws = _workspace("df_flow_compose", B, N, dev)

@@ -12,6 +12,7 @@ scene file with it, and ``python -m deflow_amd.voidmap data_dir=<dir>`` writes `
 ``HDF5Dataset`` picks up."""
 from __future__ import annotations
 
+import functools
 import json
 import math
 import os
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
+from .args import tensor
 
 SUB = 256                          # sub-voxel units per voxel
 SIDECAR_SUFFIX = ".dufo.npz"
@@ -36,13 +38,7 @@ def ray_limit(max_range: float, voxel: float) -> int:
     return int(round(float(max_range) / float(voxel) * SUB))
 
 
-def _check(name: str, t: torch.Tensor, shape, dtype, device=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"VoidMap: {name} must be a CUDA tensor (deflow_amd has no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"VoidMap: {name} is on {t.device}, the map is on {device}")
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"VoidMap: {name} must be {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+_check = functools.partial(tensor, "VoidMap", other="the map is")
 
 
 class VoidMap:
@@ -105,13 +101,12 @@ class VoidMap:
         return (*self.grid_min, self.k, *self.dims)
 
     def _points(self, points, count):
-        if not isinstance(points, torch.Tensor) or not points.is_cuda:
-            raise TypeError("VoidMap: points must be a CUDA tensor (deflow_amd has no CPU fallback)")
+        _check("points", points)
         if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] != self.batch or points.shape[1] < 1:
             raise ValueError(f"VoidMap: points [{self.batch},N,3] with N >= 1 expected, got {tuple(points.shape)}")
         B, N, _ = points.shape
-        _check("points", points, (B, N, 3), torch.float32, self.device)
-        _check("count", count, (B,), torch.int32, self.device)
+        _check("points", points, torch.float32, (B, N, 3), self.device)
+        _check("count", count, torch.int32, (B,), self.device)
         return points.detach().contiguous(), count.contiguous(), B, N
 
     def integrate(self, points: torch.Tensor, count: torch.Tensor, origin: torch.Tensor, status: Optional[torch.Tensor] = None,
@@ -121,11 +116,11 @@ class VoidMap:
         status: optional i32[1], increased when a ray reaches the walk's bound (never, on a valid map); attempts: optional i64[1],
         increased by the number of free-bit sets the rays asked for; always_atomic drops the test before the atomic (measuring only)."""
         points, count, B, N = self._points(points, count)
-        _check("origin", origin, (B, 3), torch.float32, self.device)
+        _check("origin", origin, torch.float32, (B, 3), self.device)
         if status is not None:
-            _check("status", status, (1,), torch.int32, self.device)
+            _check("status", status, torch.int32, (1,), self.device)
         if attempts is not None:
-            _check("attempts", attempts, (1,), torch.int64, self.device)
+            _check("attempts", attempts, torch.int64, (1,), self.device)
         s = stream()
         args = (ptr(points), ptr(count), ptr(origin.contiguous()), B, N, *self._grid_args(), self.hit_margin, self.R, ptr(self._f),
                 ptr(self._o), ptr(status))

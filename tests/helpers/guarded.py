@@ -183,8 +183,8 @@ def install(monkeypatch, fill: int) -> Guard:
     """put a Guard's ``call`` and ``ptr`` in place of the names every op module imported from deflow_amd._lib"""
     import importlib
     from deflow_amd import _lib
-    for m in ("augment", "chamfer", "cluster", "decoder", "fastnsf", "floxels", "ground", "mbnsf", "metrics_device", "nsfp", "pairflow",
-              "pairopt", "refine", "render", "rigid", "submit", "sweeps", "voidmap"):
+    for m in ("args", "augment", "chamfer", "cluster", "decoder", "fastnsf", "floxels", "ground", "mbnsf", "metrics_device", "nsfp", "odometry",
+              "pairflow", "pairopt", "refine", "render", "rigid", "submit", "sweeps", "voidmap"):
         importlib.import_module("deflow_amd." + m)
     g = Guard(fill, _lib.call)
     hit = 0
@@ -195,5 +195,5 @@ def install(monkeypatch, fill: int) -> Guard:
             monkeypatch.setattr(mod, "call", g.call)
             monkeypatch.setattr(mod, "ptr", g.ptr)
             hit += 1
-    assert hit >= 18, hit
+    assert hit >= 20, hit
     return g

@@ -468,6 +468,33 @@ def test_refine(dev, monkeypatch):
     assert int(out["status"]) == 0 and int((out["table"][0, :, 6] > 0).sum()) >= 1 and int((out["rigid_id"][2] != 0).sum()) == 0
 
 
+# ---- the shared checks and the row grid the wrappers above are written on (not guarded: the scenarios above are) ---------------------------
+def test_args_tensor_and_row_grid(dev):
+    from deflow_amd import args, chamfer
+    g = torch.Generator().manual_seed(31)
+    x = (4.0 * torch.rand(2, 5, 3, generator=g) - 2.0).to(dev)
+    cnt = torch.tensor([5, 3], dtype=torch.int32, device=dev)
+    assert args.tensor("op", "x", x, torch.float32, (2, 5, 3), dev, "y is") is x and args.cloud("op", "x", x, 3) == (2, 5)
+    with pytest.raises(ValueError, match=r"op: x must be torch.int32 of shape \(2, 5, 3\), got torch.float32 \(2, 5, 3\)"):
+        args.tensor("op", "x", x, torch.int32, (2, 5, 3))
+    with pytest.raises(ValueError, match=r"op: x must be torch.bool or torch.uint8 of shape \(2, 5\), got torch.float32 \(2, 5, 3\)"):
+        args.tensor("op", "x", x, (torch.bool, torch.uint8), (2, 5))
+    with pytest.raises(ValueError, match=r"op: cnt must be torch.float32 of shape \(B, N, 3\) with B >= 1 and N >= 1, got torch.int32 \(2,\)"):
+        args.cloud("op", "cnt", cnt)
+    if torch.cuda.device_count() > 1:
+        other = torch.device("cuda", (dev.index + 1) % torch.cuda.device_count())
+        with pytest.raises(ValueError, match=f"op: x is on {dev}, y is on {other}"):
+            args.tensor("op", "x", x, torch.float32, (2, 5, 3), other, "y is")
+    # file + nn are chamfer_nn, bit for bit (one sample with rows behind its count, a gate that cuts some pairs)
+    ref = (4.0 * torch.rand(2, 5, 3, generator=g) - 2.0).to(dev)
+    rng, cell, gate = (-2.0, -2.0, 2.0, 2.0), 1.0, 2.5
+    grid = chamfer.RowGrid(2, rng, cell, dev)
+    d2, idx = grid.nn(x, cnt, None, grid.file(ref, cnt), gate)
+    want_d2, want_idx = chamfer.chamfer_nn(x, cnt, ref, cnt, max_dist2=gate, grid_range=rng, cell=cell)
+    assert guarded.same_bits(d2, want_d2) and guarded.same_bits(idx, want_idx)
+    assert int((idx[0] >= 0).sum()) >= 1 and bool((idx[1, 3:] == -1).all())
+
+
 # ---- the table covers what ran ------------------------------------------------------------------------------------------------------------
 def test_the_scenarios_cover_the_table_and_the_cpu_modules_workspace_cases():
     """the scenarios' entry lists are the whole table; and what the guarded runs of this process asked the df_*_ws_bytes functions is

@@ -72,11 +72,12 @@ def bits(t):
 # ---- test 1: one accumulate -------------------------------------------------------------------------------------------------------------
 def accumulate(src, cs, dst, cd, T, stride, max_dist):
     """the two grids as ``register`` files them, then ONE df_reg_accumulate with the per-row outputs on"""
-    from deflow_amd import odometry
     from deflow_amd._lib import call, ptr, stream
-    b, ns, nd, dev = src.shape[0], src.shape[1], dst.shape[1], src.device
-    s_rng, s_rows = odometry._file(src, cs, None, b, ns, RANGE[0], RANGE[1], CELL, G)
-    d_rng, d_rows = odometry._file(dst, cd, None, b, nd, RANGE[0], RANGE[1], CELL, G)
+    from deflow_amd.chamfer import RowGrid
+    b, ns, dev = src.shape[0], src.shape[1], src.device
+    grid = RowGrid(b, GRID["xy_range"], CELL, dev)
+    assert (grid.minx, grid.miny, grid.G) == (RANGE[0], RANGE[1], G)
+    (s_rng, s_rows), (d_rng, d_rows) = grid.file(src, cs), grid.file(dst, cd)
     nblk = (ns + 255) // 256
     assert call("df_reg_ws_bytes", b, ns) == b * nblk * 256
     partial = torch.full((b, nblk, 32), float("nan"), dtype=torch.float64, device=dev)
@@ -308,7 +309,7 @@ REG_TABLE = {            # the sizes of the header's registration section, local
 
 
 def test_guarded_entries_write_nothing_outside_their_buffers(dev, monkeypatch):
-    from deflow_amd import _lib, odometry
+    from deflow_amd import _lib, args, chamfer, odometry
     protos = abi_sizes.header_prototypes()
     for name in ("df_reg_accumulate", "df_reg_solve"):               # the local table against the header's prototypes
         assert [p.name for p in protos[name]][:-1] == list(REG_TABLE[name].params)
@@ -326,8 +327,9 @@ def test_guarded_entries_write_nothing_outside_their_buffers(dev, monkeypatch):
         for fill in (0xA5, 0x7F):
             with monkeypatch.context() as m:
                 g = guarded.Guard(fill, _lib.call, table=REG_TABLE)
-                m.setattr(odometry, "call", g.call)
-                m.setattr(odometry, "ptr", g.ptr)
+                for mod in (odometry, chamfer, args):       # register's own entries, the grid build, the workspace query
+                    m.setattr(mod, "call", g.call)
+                    m.setattr(mod, "ptr", g.ptr)
                 outs.append(scenario(stride))
             assert g.seen.count("df_reg_accumulate") == 3 and g.seen.count("df_reg_solve") == 3 and g.seen.count("df_nn_grid_build") == 2
         for a, b, c in zip(*outs):

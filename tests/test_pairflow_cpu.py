@@ -192,7 +192,7 @@ MESSAGES = {
                 ({"min_delta": float("inf")}, "floxels_optimize: min_delta must be a finite number, got inf"),
                 ({"depth": 1}, "floxels_optimize: unknown parameter 'depth'; known: cell, check_every, graph, iters, lr, min_delta, patience, "
                                "smooth_weight, trunc, voxel")],
-    "icpflow": [({"min_points": 0}, "rigid_cluster_flow: min_points must be an integer >= 1, got 0"),
+    "icpflow": [({"min_points": 0}, "rigid_cluster_flow: min_points must be an integer in [1, 1073741824], got 0"),
                 ({"eps": 0}, "rigid_cluster_flow: eps must be positive and finite, got 0"),
                 ({"bins": 1}, "rigid_cluster_flow: unknown parameter 'bins'; known: eps, icp_cap, icp_iters, icp_max_dist, max_cluster_points, "
                               "max_disp, max_yaw, min_cluster_size, min_inlier_frac, min_points, min_side, vote_bin, vote_cap")],

@@ -85,32 +85,26 @@ def main():
               "eps": eps, "min_points": a.min_points, "device": torch.cuda.get_device_name(0)}
 
     # ---- the yardstick: the whole-cloud chamfer search and its grid build ------------------------------------------------------------
-    minx, miny, G = chamfer._grid(B, grid_range, chamfer.CELL)
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    rows = torch.empty(B * pc1.shape[1], 4, dtype=torch.float32, device=dev)
-    ws = torch.empty(call("df_nn_grid_ws_bytes", B, pc1.shape[1], G), dtype=torch.uint8, device=dev)
-    d2 = torch.empty(B, Nc, dtype=torch.float32, device=dev)
-    idx = torch.empty(B, Nc, dtype=torch.int32, device=dev)
-    t_ybuild = timed(lambda: call("df_nn_grid_build", ptr(pc1), ptr(c1), None, B, pc1.shape[1], minx, miny, chamfer.CELL, G, ptr(cell_rng),
-                                  ptr(rows), ptr(ws), stream()), a.reps)
-    t_ysearch = timed(lambda: call("df_chamfer_nn", ptr(pc0), ptr(c0), None, B, Nc, ptr(cell_rng), ptr(rows), minx, miny, chamfer.CELL, G,
-                                   float("inf"), ptr(d2), ptr(idx), None, stream()), a.reps)
+    ygrid = chamfer.RowGrid(B, grid_range, chamfer.CELL, dev)
+    G = ygrid.G
+    filed = ygrid.file(pc1, c1)
+    t_ybuild = timed(lambda: ygrid.file(pc1, c1), a.reps)
+    t_ysearch = timed(lambda: ygrid.nn(pc0, c0, None, filed, float("inf")), a.reps)
     report["yardstick"] = {"chamfer_grid_build_ms": round(t_ybuild, 4), "chamfer_nn_pc0_to_pc1_ms": round(t_ysearch, 4),
                            "cell_m": chamfer.CELL, "grid_cells_per_side": G}
     print(json.dumps(report["yardstick"]), flush=True)
-    del cell_rng, rows, ws
+    del filed
 
     # ---- the stages ----------------------------------------------------------------------------------------------------------------
     cell = max(cluster.CELL_SLACK * eps, 2 * half / 4096.0)
-    minx, miny, G = chamfer._grid(B, grid_range, cell)
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    rows = torch.empty(B * Nc, 4, dtype=torch.float32, device=dev)
-    gws = torch.empty(call("df_nn_grid_ws_bytes", B, Nc, G), dtype=torch.uint8, device=dev)
+    grid = chamfer.RowGrid(B, grid_range, cell, dev)
+    minx, miny, G = grid.minx, grid.miny, grid.G
+    cell_rng, rows = grid.file(pc0, c0)
     ws = torch.empty(call("df_dbscan_ws_bytes", B, Nc), dtype=torch.uint8, device=dev)
     labels = torch.empty(B, Nc, dtype=torch.int32, device=dev)
     ncl = torch.empty(B, dtype=torch.int32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    build = lambda: call("df_nn_grid_build", ptr(pc0), ptr(c0), None, B, Nc, minx, miny, cell, G, ptr(cell_rng), ptr(rows), ptr(gws), stream())
+    build = lambda: grid.file(pc0, c0)
     core = lambda: call("df_dbscan_core", ptr(cell_rng), ptr(rows), B, Nc, minx, miny, cell, G, eps, a.min_points, ptr(ws), stream())
     link = lambda: call("df_dbscan_link", ptr(cell_rng), B, Nc, minx, miny, cell, G, eps, ptr(status), ptr(ws), stream())
     fin = lambda: call("df_dbscan_finish", ptr(cell_rng), ptr(f0), B, Nc, minx, miny, cell, G, eps, 20, 0.3, ptr(labels), ptr(ncl),

@@ -72,11 +72,8 @@ def stages(B, n, reps, g, dev, hbm):
                           ptr(seg._height), ptr(seg._observed), stream())
     masks = lambda: call("df_ground_mask", ptr(pts), ptr(cnt), B, n, *rows, ptr(seg._height), seg.TOL, ptr(mask), stream())
     # the yardstick: the chamfer search's grid build over the same rows (the grid chamfer.py would choose for this cloud)
-    minx, miny, G = chamfer._grid(B, chamfer.GRID_RANGE, chamfer.CELL)
-    cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-    srows = torch.empty(B * n, 4, dtype=torch.float32, device=dev)
-    ws = torch.empty(int(call("df_nn_grid_ws_bytes", B, n, G)), dtype=torch.uint8, device=dev)
-    build = lambda: call("df_nn_grid_build", ptr(pts), ptr(cnt), None, B, n, minx, miny, chamfer.CELL, G, ptr(cell_rng), ptr(srows), ptr(ws), stream())
+    grid = chamfer.RowGrid(B, chamfer.GRID_RANGE, chamfer.CELL, dev)
+    build = lambda: grid.file(pts, cnt)
     t = {"cells_ms": timed(cells, reps), "height_ms": timed(height, reps), "mask_ms": timed(masks, reps), "nn_grid_build_ms": timed(build, reps),
          "zmin_fill_ms": timed(lambda: seg._zmin.fill_(ground.EMPTY), reps)}
     whole = timed(lambda: seg.segment(pts, cnt), reps)

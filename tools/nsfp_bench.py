@@ -16,7 +16,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from deflow_amd import nsfp, pairopt  # noqa: E402
+from deflow_amd import chamfer, nsfp, pairopt  # noqa: E402
 from deflow_amd._lib import call, ptr, stream  # noqa: E402
 from deflow_amd.chamfer import chamfer_bwd  # noqa: E402
 
@@ -70,17 +70,17 @@ def main():
     dy = torch.randn_like(y)
     W = p0 + y
     lab = torch.ones(1, N, dtype=torch.int32, device=dev)
-    search = nsfp._Search(1, nsfp.GRID_RANGE, nsfp.CELL, 4.0, dev)
-    grid1 = search.build(p1, cnt, lab)
-    d2, idx = search.nn(W, cnt, lab, grid1)
+    search = chamfer.RowGrid(1, chamfer.GRID_RANGE, chamfer.CELL, dev)
+    grid1 = search.file(p1, cnt, lab)
+    d2, idx = search.nn(W, cnt, lab, grid1, 4.0)
     g = pairopt.mean_and_weight(d2)[1]
     buf = torch.zeros_like(W)
     grads, m, v = torch.zeros_like(arena), torch.zeros_like(arena), torch.zeros_like(arena)
     step = torch.ones(1, dtype=torch.int32, device=dev)
     ms_fwd = median_ms(lambda: nsfp.mlp_forward(p0, cnt, par, depth))
     ms_bwd = median_ms(lambda: nsfp.mlp_backward(p0, cnt, par, depth, acts, dy, need_dx=True))
-    ms_nn = median_ms(lambda: search.nn(W, cnt, lab, grid1))
-    ms_build = median_ms(lambda: search.build(W, cnt, lab))
+    ms_nn = median_ms(lambda: search.nn(W, cnt, lab, grid1, 4.0))
+    ms_build = median_ms(lambda: search.file(W, cnt, lab))
     ms_red = median_ms(lambda: pairopt.mean_and_weight(d2))
     ms_cq = median_ms(lambda: chamfer_bwd(W, p1, idx, g, buf, None))
     ms_cr = median_ms(lambda: chamfer_bwd(W, p1, idx, g, None, buf))

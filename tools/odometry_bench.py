@@ -68,13 +68,10 @@ def main():
     for B in sorted({1, a.batch}):
         pc0, pc1, c0, c1 = all0[:B].contiguous(), all1[:B].contiguous(), cnt0[:B].contiguous(), cnt1[:B].contiguous()
         Ns, Nd = pc0.shape[1], pc1.shape[1]
-        minx, miny, G = chamfer._grid(B, grid_range, cell)
-        s_rng, s_rows = odometry._file(pc0, c0, None, B, Ns, minx, miny, cell, G)
-        d_rng, d_rows = odometry._file(pc1, c1, None, B, Nd, minx, miny, cell, G)
-        d2 = torch.empty(B, Ns, dtype=torch.float32, device=dev)
-        idx = torch.empty(B, Ns, dtype=torch.int32, device=dev)
-        t_search = timed(lambda: call("df_chamfer_nn", ptr(pc0), ptr(c0), None, B, Ns, ptr(d_rng), ptr(d_rows), minx, miny, cell, G,
-                                      max_dist ** 2, ptr(d2), ptr(idx), None, stream()), a.reps)
+        grid = chamfer.RowGrid(B, grid_range, cell, dev)
+        minx, miny, G = grid.minx, grid.miny, grid.G
+        (s_rng, s_rows), (d_rng, d_rows) = grid.file(pc0, c0), grid.file(pc1, c1)
+        t_search = timed(lambda: grid.nn(pc0, c0, None, (d_rng, d_rows), max_dist ** 2), a.reps)
         nblk = (Ns + 255) // 256
         partial = torch.empty(call("df_reg_ws_bytes", B, Ns) // 8, dtype=torch.float64, device=dev)
         T = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1)

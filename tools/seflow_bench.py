@@ -22,7 +22,6 @@ import torch
 
 import deflow_amd
 from deflow_amd import chamfer
-from deflow_amd._lib import call, ptr, stream
 from deflow_amd.optim import Trainer
 from deflow_amd.synth import synth_batch, synth_cluster_labels
 
@@ -80,7 +79,7 @@ def main():
     p = torch.where(valid0[..., None], pc0 + st["flow"], torch.full_like(pc0, float("nan"))).contiguous()
     n0, n1 = c0.double(), c1.double()
     d0, d1 = (l0 > 0).sum(1).double(), (l1 > 0).sum(1).double()
-    minx, miny, G = chamfer._grid(B, (rng[0], rng[1], rng[3], rng[4]), chamfer.CELL)
+    grid = chamfer.RowGrid(B, (rng[0], rng[1], rng[3], rng[4]), chamfer.CELL, dev)
     T = 4.0
     searches = [  # name, query, qcount, qlabel, ref, rcount, rlabel, max_dist2, participating rows per sample (query, ref)
         ("p->pc1", p, c0, None, pc1, c1, None, T, n0, n1), ("pc1->p", pc1, c1, None, p, c0, None, T, n1, n0),
@@ -89,23 +88,14 @@ def main():
         ("pc1->pc0 raw, unbounded", pc1, c1, None, pc0, c0, None, float("inf"), n1, n0)]
     report = {"shape": {"batch": B, "points_per_cloud": N, "grid": [H, H], "valid_rows_pc0": c0.tolist(), "valid_rows_pc1": c1.tolist(),
                         "dynamic_rows_pc0": (l0 > 0).sum(1).tolist(), "dynamic_rows_pc1": (l1 > 0).sum(1).tolist()},
-              "grid_cells_per_side": G, "cell_m": chamfer.CELL, "device": torch.cuda.get_device_name(0), "searches": []}
+              "grid_cells_per_side": grid.G, "cell_m": chamfer.CELL, "device": torch.cuda.get_device_name(0), "searches": []}
     keep = {}
     for name, q, qc, ql, r, rc, rl, md, nq, nr in searches:
-        Nq, Nr = q.shape[1], r.shape[1]
-        cell_rng = torch.empty(B * G * G, 2, dtype=torch.int32, device=dev)
-        rows = torch.empty(B * Nr, 4, dtype=torch.float32, device=dev)
-        ws = torch.empty(call("df_nn_grid_ws_bytes", B, Nr, G), dtype=torch.uint8, device=dev)
-        d2 = torch.empty(B, Nq, dtype=torch.float32, device=dev)
-        idx = torch.empty(B, Nq, dtype=torch.int32, device=dev)
         far = torch.zeros(1, dtype=torch.int32, device=dev)
-        build = lambda: call("df_nn_grid_build", ptr(r), ptr(rc), ptr(rl), B, Nr, minx, miny, chamfer.CELL, G, ptr(cell_rng), ptr(rows),
-                             ptr(ws), stream())
-        search = lambda fc=None: call("df_chamfer_nn", ptr(q), ptr(qc), ptr(ql), B, Nq, ptr(cell_rng), ptr(rows), minx, miny, chamfer.CELL,
-                                      G, md, ptr(d2), ptr(idx), ptr(fc), stream())
-        t_build = timed(build, a.reps)
-        t_search = timed(search, a.reps)
-        search(far)
+        filed = grid.file(r, rc, rl)
+        t_build = timed(lambda: grid.file(r, rc, rl), a.reps)
+        t_search = timed(lambda: grid.nn(q, qc, ql, filed, md), a.reps)
+        _, idx = grid.nn(q, qc, ql, filed, md, far)
         torch.cuda.synchronize()
         floor_ms = float((nq * nr).sum()) * 4 / FMA_PER_S * 1e3
         row = {"search": name, "grid_build_ms": round(t_build, 4), "search_ms": round(t_search, 4),
