@@ -129,6 +129,10 @@ _SIGS = {
     "df_upsample2x_bwd": [DfImg, DfImg, I, P],
     "df_upsample2x_bwd_h2": [DfImg, DfImg, I, P, P],
     "df_u5u1_decompose": [P, P, P, P, P, I, I, I, I, P, P, P, P, P],
+    "df_cat_pack_up": [DfImg, DfImg, DfImg, I, P, P],
+    "df_u3u4_border_fix": [DfImg, P, P, P],
+    "df_u3u4_border_sums": [DfImg, P, P, P, P, P],
+    "df_u3u4_decompose": [P, P, P, P, P, I, I, P, P, P, P, P],
     "df_gru_decoder_fwd": [DfImg, DfImg, P, P, P, I, I, I, DfGruWeights, P, P, P],
     "df_gru_decoder_fwd_mp": [DfImg, DfImg, P, P, P, I, I, I, DfGruWeights, P, P, I, P],
     "df_gru_decoder_bwd_mp": [P, P, P, I, I, I, DfGruWeights, DfGruWeightsT, P, P, P, P, P, P, I, P],

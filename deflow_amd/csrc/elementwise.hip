@@ -152,18 +152,84 @@ __device__ __forceinline__ void df_small_gemm8(const float* __restrict__ A, int6
 #pragma unroll
   for (int r = 0; r < 8; ++r) acc[r] = 0.0;
   if (j >= J) return;
+#pragma unroll 4          // (loads of four k steps in flight; the FMAs keep their order)
   for (int k = 0; k < K; ++k) {
     const double b = (double)Bm[(int64_t)k * J + j];
 #pragma unroll
     for (int r = 0; r < 8; ++r) acc[r] = __builtin_fma((double)A[(row0 + r) * rs + k * ks], b, acc[r]);
   }
 }
+// ---- the second kind of composed layer (DF_FUSE_U3U4): an UpsampleSkip block's 1x1 skip convolution u3 (W3 [lat][lat], b3; no padding)
+// is read by the second half of the input channels of the block's first 3x3 (W4 [O][taps][2 lat] = [W4a | W4b], b4; zero padding 1)
+// alone, with nothing in between: the pair is ONE 3x3 layer of W4's shape that reads [up(t) | b] instead of [up(t) | u3(b)],
+//   We[o][tap][:lat] = W4a[o][tap][:]      We[o][tap][lat + i] = sum_c W4b[o][tap][c] W3[c][i]
+//   beta[o][tap] = sum_c W4b[o][tap][c] b3[c]      be[o] = b4[o] + sum_tap beta[o][tap]
+// exactly in the interior; at a border pixel the taps that fall on the padding carry no b3 term, so the single bias be over-counts there
+// by the sum of their beta (taken off again by u3u4_border_fix_kernel).  Source record: w_off = W4, b_off = b4, wt_off = W3, w2_off = b3,
+// wt2_off = the `norms` slot of max |We|, cout = O, taps, cin = 2 lat, split = lat, pad = 1.  beta lies behind be in `out`; the layer's
+// bias norm (norms[L][2]) also covers |b4| + sum_tap |beta|, which bounds the bias side of the output before AND after the border fix.
+__device__ __forceinline__ void u3u4_compose_layer(const float* __restrict__ params, const df_wprep_layer& t, const df_wprep_layer& src,
+                                                   float* __restrict__ out, unsigned* __restrict__ norms, int L) {
+  __shared__ double sbeta[16][9];
+  const int O = t.cout, taps = t.taps, lat = src.split, I2 = t.cin, R = O * taps;
+  const float* __restrict__ w4 = params + src.w_off;
+  const float* __restrict__ w3 = params + src.wt_off;
+  const float* __restrict__ b3 = params + src.w2_off;
+  float* __restrict__ beta = out + t.b_off + (O + 63) / 64 * 64;
+  const int nj = (lat + 255) >> 8, ntile = nj * (R >> 3), nbias = (O + 15) >> 4;
+  for (int g = blockIdx.x; g < ntile + nbias; g += gridDim.x) {
+    if (g >= ntile) {              // beta and the bias of 16 output channels: thread (o, tap)
+      const int o = (g - ntile) * 16 + ((int)threadIdx.x >> 4), tap = (int)threadIdx.x & 15;
+      __syncthreads();
+      if (o < O && tap < taps && tap < 9) {
+        double a = 0.0;
+        const float* row = w4 + ((int64_t)o * taps + tap) * I2 + lat;
+        for (int c = 0; c < lat; ++c) a = __builtin_fma((double)row[c], (double)b3[c], a);
+        sbeta[threadIdx.x >> 4][tap] = a;
+        beta[(int64_t)o * taps + tap] = (float)a;
+      }
+      __syncthreads();
+      if (o < O && tap == 0) {
+        double s = (double)params[src.b_off + o], m = fabs(s);
+        for (int k = 0; k < taps; ++k) {
+          s += sbeta[threadIdx.x >> 4][k];
+          m += fabs(sbeta[threadIdx.x >> 4][k]);
+        }
+        out[t.b_off + o] = (float)s;
+        df_atomic_amax(norms + 3 * L + 2, (float)m * 1.000001f);
+      }
+      continue;
+    }
+    const int rt = g / nj, j = (g - rt * nj) * 256 + (int)threadIdx.x;
+    double acc[8];
+    df_small_gemm8(w4 + lat, I2, 1, w3, lat, lat, rt * 8, j, acc);
+    float m = 0.f;
+    if (j < lat) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int64_t row = (int64_t)(rt * 8 + r) * I2;
+        const float v = (float)acc[r], u = w4[row + j];
+        out[t.w_off + row + lat + j] = v;
+        out[t.w_off + row + j] = u;
+        m = fmaxf(m, fmaxf(fabsf(v), fabsf(u)));
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) df_atomic_amax(norms + src.wt2_off, m);
+  }
+}
+
 __global__ __launch_bounds__(256) void weight_compose_kernel(const float* __restrict__ params, const df_wprep_layer* __restrict__ tab, int nlayers,
                                                              float* __restrict__ out, unsigned* __restrict__ norms) {
   for (int L = 0; L < nlayers; ++L) {
     const df_wprep_layer t = tab[L];
     if (t.pad <= 0) continue;
     const df_wprep_layer src = tab[t.pad];
+    if (src.pad == 1) {            // the second kind: a block's 1x1 skip convolution folded into its first 3x3 (below)
+      u3u4_compose_layer(params, t, src, out, norms, L);
+      continue;
+    }
     const int O = t.cout, J = t.taps * t.cin, C = src.cout;
     const float* __restrict__ w5 = params + src.w_off;
     const float* __restrict__ w1 = params + src.wt_off;
@@ -971,6 +1037,215 @@ __global__ __launch_bounds__(256) void upsample2x_bwd8_kernel(df_img dy, df_img 
   }
 }
 
+// ---- companions of the layer composed of an UpsampleSkip block's skip convolution and its first 3x3 (u3u4_compose_layer) -----------
+// Whole pixels of the layer's pre-split input: channels [0, lat) = bilinear x2 of t (upsample2x8_kernel<2>'s expression and rounding: the
+// same planes), channels [lat, 2 lat) = b (h2_pack_kernel's rounding).  Eight channels of each half per thread, 16-byte plane stores.
+__global__ __launch_bounds__(256) void cat_pack_up_kernel(df_img x, df_img bsrc, df_img y, int align_corners, int64_t total8,
+                                                          const float* __restrict__ y_bound) {
+  const float ys = df_h2_scale(*y_bound);
+  const int lat = x.c, C8 = lat >> 3;
+  const int c8s = df_pow2_shift(C8), yws = df_pow2_shift(y.w), yhs = df_pow2_shift(y.h);
+  const float* __restrict__ xp = reinterpret_cast<const float*>(x.ptr);
+  const float* __restrict__ bp = reinterpret_cast<const float*>(bsrc.ptr);
+  auto split8 = [&](const f32x4 o0, const f32x4 o1, int64_t idx) {
+    f16x8e_t hi, lo;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float t0 = o0[k] * ys, t1 = o1[k] * ys;
+      hi[k] = (_Float16)t0;
+      lo[k] = (_Float16)((t0 - (float)hi[k]) * 2048.f);
+      hi[4 + k] = (_Float16)t1;
+      lo[4 + k] = (_Float16)((t1 - (float)hi[4 + k]) * 2048.f);
+    }
+    char* q = reinterpret_cast<char*>(y.ptr) + (idx & ~31ll) * 4 + (idx & 31) * 2;
+    *reinterpret_cast<f16x8e_t*>(q) = hi;
+    *reinterpret_cast<f16x8e_t*>(q + 64) = lo;
+  };
+  // thread = eight channels c .. c + 7 of BOTH halves of one pixel: ten 16-byte loads in flight, four 16-byte plane stores, no divergence
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = df_udiv(i, C8, c8s);
+    const int c = (int)(i - m * C8) * 8;
+    const int64_t mw = df_udiv(m, y.w, yws);
+    const int X = (int)(m - mw * y.w);
+    const int n = (int)df_udiv(mw, y.h, yhs), Y = (int)(mw - (int64_t)n * y.h);
+    const Lerp ly = lerp_src(Y, x.h, y.h, align_corners), lx = lerp_src(X, x.w, y.w, align_corners);
+    const float* b = xp + df_img_base(x, n) + c;
+    const float* p00 = b + ((int64_t)ly.i0 * x.w + lx.i0) * x.ld;
+    const float* p01 = b + ((int64_t)ly.i0 * x.w + lx.i1) * x.ld;
+    const float* p10 = b + ((int64_t)ly.i1 * x.w + lx.i0) * x.ld;
+    const float* p11 = b + ((int64_t)ly.i1 * x.w + lx.i1) * x.ld;
+    const float* q = bp + df_img_base(bsrc, n) + ((int64_t)Y * y.w + X) * bsrc.ld + c;
+    const f32x4 a00 = ld4(p00), a01 = ld4(p01), a10 = ld4(p10), a11 = ld4(p11);
+    const f32x4 b00 = ld4(p00 + 4), b01 = ld4(p01 + 4), b10 = ld4(p10 + 4), b11 = ld4(p11 + 4);
+    const f32x4 s0 = ld4(q), s1 = ld4(q + 4);
+    const f32x4 o0 = ly.l0 * (lx.l0 * a00 + lx.l1 * a01) + ly.l1 * (lx.l0 * a10 + lx.l1 * a11);
+    const f32x4 o1 = ly.l0 * (lx.l0 * b00 + lx.l1 * b01) + ly.l1 * (lx.l0 * b10 + lx.l1 * b11);
+    const int64_t idx = df_img_base(y, n) + ((int64_t)Y * y.w + X) * y.ld + c;
+    split8(o0, o1, idx);
+    split8(s0, s1, idx + lat);
+  }
+}
+
+// border pixel q of an H x W image (H, W >= 2), q < 2 W + 2 (H - 2): row 0, row H - 1, then the two columns' inner pixels
+__device__ __forceinline__ void u3u4_border_pixel(int q, int H, int W, int& Y, int& X) {
+  if (q < W) { Y = 0; X = q; }
+  else if (q < 2 * W) { Y = H - 1; X = q - W; }
+  else { Y = 1 + ((q - 2 * W) >> 1); X = ((q - 2 * W) & 1) ? W - 1 : 0; }
+}
+// y[border pixel][o] -= sum over the taps (ky, kx) that fall on the padding there of beta[o][tap]: unpack, subtract, re-split with y's scale
+__global__ __launch_bounds__(256) void u3u4_border_fix_kernel(df_img y, const float* __restrict__ bound, const float* __restrict__ beta,
+                                                              int64_t total4) {
+  const float s = df_h2_scale(*bound), inv_s = 1.f / s;
+  const int C4 = y.c >> 2, nb = 2 * y.w + 2 * (y.h - 2);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = i / C4;
+    const int c = (int)(i - m * C4) * 4;
+    const int n = (int)(m / nb);
+    int Y, X;
+    u3u4_border_pixel((int)(m - (int64_t)n * nb), y.h, y.w, Y, X);
+    f32x4 sub = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int yy = Y + tap / 3 - 1, xx = X + tap % 3 - 1;
+      if (yy < 0 || yy >= y.h || xx < 0 || xx >= y.w) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sub[k] += beta[(c + k) * 9 + tap];
+      }
+    }
+    const int64_t idx = df_img_base(y, n) + ((int64_t)Y * y.w + X) * y.ld + c;
+    const f32x4 v = ld_h2x4(y.ptr, idx, inv_s);
+    st_h2x4(y.ptr, idx, v - sub, s);
+  }
+}
+
+// part[q][n][o]: sums of dy over border line q of image n (q = 0 row 0, 1 row H - 1, 2 column 0, 3 column W - 1) and the corner values
+// (q = 4 .. 7: (0,0), (0,W-1), (H-1,0), (H-1,W-1)).  Workgroup (q, n): thread (lane, channel quad) sums every L-th pixel of the line in
+// double, lane 0's threads add the L partial sums in lane order: a fixed order, no atomics
+__global__ __launch_bounds__(256) void u3u4_border_sums_kernel(df_img dy, const float* __restrict__ bound, double* __restrict__ part) {
+  __shared__ double red[1024];
+  const float inv_s = 1.f / df_h2_scale(*bound);
+  const int side = blockIdx.x, n = blockIdx.y, Q = dy.c >> 2, L = 256 / Q;
+  const int quad = (int)threadIdx.x % Q, lane = (int)threadIdx.x / Q, c = quad * 4;
+  const int len = side < 2 ? dy.w : dy.h;
+  const int64_t base = df_img_base(dy, n);
+  auto pix = [&](int p) -> int64_t {
+    const int Y = side == 0 ? 0 : side == 1 ? dy.h - 1 : p, X = side < 2 ? p : side == 2 ? 0 : dy.w - 1;
+    return base + ((int64_t)Y * dy.w + X) * dy.ld + c;
+  };
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int p = lane; p < len; p += L) {
+    const f32x4 v = ld_h2x4(dy.ptr, pix(p), inv_s);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] += (double)v[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) red[lane * dy.c + c + k] = a[k];
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      double s = 0.0;
+      for (int l = 0; l < L; ++l) s += red[l * dy.c + c + k];
+      part[((int64_t)side * dy.n + n) * dy.c + c + k] = s;
+    }
+    if (side < 2) {
+      const f32x4 v0 = ld_h2x4(dy.ptr, pix(0), inv_s), v1 = ld_h2x4(dy.ptr, pix(dy.w - 1), inv_s);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        part[((int64_t)(4 + 2 * side) * dy.n + n) * dy.c + c + k] = (double)v0[k];
+        part[((int64_t)(5 + 2 * side) * dy.n + n) * dy.c + c + k] = (double)v1[k];
+      }
+    }
+  }
+}
+
+// T[o][tap] = sum of dy[o] over the pixels p whose tap lands inside the image = the column sum dbe[o], less the border row / column the tap
+// excludes, plus their common corner (taken off twice).  One thread per (o, tap); the images' partial sums in image order
+__global__ __launch_bounds__(256) void u3u4_tapsums_kernel(const float* __restrict__ dbe, const double* __restrict__ part, int N, int O,
+                                                           double* __restrict__ T) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= O * 9) return;
+  const int o = r / 9, tap = r - 9 * o, ky = tap / 3, kx = tap - 3 * ky;
+  auto P = [&](int q) {
+    double a = 0.0;
+    for (int n = 0; n < N; ++n) a += part[((int64_t)q * N + n) * O + o];
+    return a;
+  };
+  double s = (double)dbe[o];
+  if (ky == 0) s -= P(0);
+  if (ky == 2) s -= P(1);
+  if (kx == 0) s -= P(2);
+  if (kx == 2) s -= P(3);
+  if (ky != 1 && kx != 1) s += P(4 + (ky == 2 ? 2 : 0) + (kx == 2 ? 1 : 0));
+  T[r] = s;
+}
+// The five parameter gradients behind the composed layer (df_u3u4_decompose), rows r = (o, tap) of dWe [O 9][2 lat]:
+//   blocks [0, na): 8 rows x 256 columns c   dW4[r][lat + c] = sum_i dWe[r][lat + i] W3t[i][c] + b3[c] T[r];  dW4[r][c] = dWe[r][c]
+//   blocks [na, na + nb): 16 x 16 outputs    dW3[c][i] = sum_r W4[r][lat + c] dWe[r][lat + i]       (LDS tiles of 64 rows)
+//   blocks [na + nb, na + nb + nc): 16 c     db3[c] = sum_r W4[r][lat + c] T[r]  (16 interleaved partial sums, added in order);  db4[o] = T[o][centre]
+// every sum in a fixed index order in double: bit-reproducible
+__global__ __launch_bounds__(256) void u3u4_decompose_kernel(const float* __restrict__ w3t, const float* __restrict__ w4, const float* __restrict__ b3,
+                                                             const float* __restrict__ dwe, const double* __restrict__ T, int O, int lat,
+                                                             float* __restrict__ dw4, float* __restrict__ db4, float* __restrict__ dw3,
+                                                             float* __restrict__ db3) {
+  __shared__ float As[64][17], Bs[64][17];
+  __shared__ double Cs[16][17];
+  const int R = O * 9, I2 = 2 * lat;
+  const int nj = (lat + 255) >> 8, na = nj * (R >> 3), nb = (lat >> 4) * (lat >> 4), nc = lat >> 4;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (g < na) {
+    const int rt = g / nj, j = (g - rt * nj) * 256 + tid;
+    double acc[8];
+    df_small_gemm8(dwe + lat, I2, 1, w3t, lat, lat, rt * 8, j, acc);
+    if (j < lat) {
+      const double bj = (double)b3[j];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int64_t row = (int64_t)(rt * 8 + r) * I2;
+        dw4[row + lat + j] = (float)__builtin_fma(bj, T[rt * 8 + r], acc[r]);
+        dw4[row + j] = dwe[row + j];
+      }
+    }
+  } else if (g < na + nb) {
+    const int b = g - na, c0 = (b / (lat >> 4)) * 16, i0 = (b % (lat >> 4)) * 16;
+    const int ty = tid >> 4, tx = tid & 15;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < R; k0 += 64) {
+      float av[4], bv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + ty + 16 * u;
+        av[u] = k < R ? w4[(int64_t)k * I2 + lat + c0 + tx] : 0.f;
+        bv[u] = k < R ? dwe[(int64_t)k * I2 + lat + i0 + tx] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        As[ty + 16 * u][tx] = av[u];
+        Bs[ty + 16 * u][tx] = bv[u];
+      }
+      __syncthreads();
+#pragma unroll 8
+      for (int k = 0; k < 64; ++k) acc = __builtin_fma((double)As[k][ty], (double)Bs[k][tx], acc);
+    }
+    dw3[(int64_t)(c0 + ty) * lat + i0 + tx] = (float)acc;
+  } else {
+    const int b = g - na - nb, ty = tid >> 4, tx = tid & 15, c = b * 16 + tx;
+    double a = 0.0;
+#pragma unroll 4
+    for (int r = ty; r < R; r += 16) a = __builtin_fma((double)w4[(int64_t)r * I2 + lat + c], T[r], a);
+    Cs[ty][tx] = a;
+    __syncthreads();
+    if (ty == 0) {
+      double sum = 0.0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sum += Cs[k][tx];
+      db3[c] = (float)sum;
+    }
+    for (int o = b * 256 + tid; o < O; o += nc * 256) db4[o] = (float)T[o * 9 + 4];
+  }
+}
+
 // any16: the entry point has a bfloat16 form (bf16 rows are accessed 8 bytes = 4 elements at a time)
 bool img_ok(const df_img& d, bool any16 = false) {
   return d.ptr && df_aligned16(d.ptr) && d.n > 0 && d.h > 0 && d.w > 0 && d.c > 0 && (d.c % 4) == 0 && d.grp_size > 0 &&
@@ -1237,7 +1512,7 @@ extern "C" int df_weight_prep(const float* params, const void* table, int nlayer
   DF_REQUIRE(params && table && nlayers > 0 && total_blocks > 0 && w_amax && out && norms, DF_E_ARG);
   // composed layers first (records with pad > 0; the launch finds them in the table: a table without any costs an empty pass)
   if (fuse_u5u1_on()) {
-    hipLaunchKernelGGL(weight_compose_kernel, dim3(256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params,
+    hipLaunchKernelGGL(weight_compose_kernel, dim3(1024), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params,
                        reinterpret_cast<const df_wprep_layer*>(table), nlayers, out, reinterpret_cast<unsigned*>(norms));
     DF_CHECK_LAUNCH();
   }
@@ -1258,6 +1533,49 @@ extern "C" int df_u5u1_decompose(const float* w1, const float* w5, const float* 
   const int grid = ((J + 255) / 256) * (C / 8) + (O / 16) * (C / 16) + 1;
   hipLaunchKernelGGL(u5u1_decompose_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w1, w5, b5, dwe, dbe, O, C, J, dw5,
                      db5, dw1, db1);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+// ---- the layer composed of an UpsampleSkip block's skip convolution and its first 3x3 (kernel comments above; include/deflow_amd.h) ----
+extern "C" int df_cat_pack_up(df_img t, df_img b, df_img cat, int align_corners, const float* cat_bound, void* stream) {
+  DF_REQUIRE(img_ok(t) && img_ok(b) && h2_ok(cat) && cat_bound, DF_E_ARG);
+  DF_REQUIRE(t.n == cat.n && b.n == cat.n && cat.h == 2 * t.h && cat.w == 2 * t.w && b.h == cat.h && b.w == cat.w && b.c == t.c &&
+                 cat.c == 2 * t.c && (t.c % 8) == 0, DF_E_SHAPE);
+  const int64_t total8 = (int64_t)cat.n * cat.h * cat.w * (t.c / 8);
+  hipLaunchKernelGGL(cat_pack_up_kernel, dim3(grid_for(total8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), t, b, cat, align_corners,
+                     total8, cat_bound);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+extern "C" int df_u3u4_border_fix(df_img y, const float* y_bound, const float* beta, void* stream) {
+  DF_REQUIRE(h2_ok(y) && y_bound && beta, DF_E_ARG);
+  DF_REQUIRE(y.h >= 2 && y.w >= 2, DF_E_SHAPE);
+  const int64_t total4 = (int64_t)y.n * (2 * y.w + 2 * (y.h - 2)) * (y.c / 4);
+  hipLaunchKernelGGL(u3u4_border_fix_kernel, dim3(grid_for(total4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, y_bound, beta, total4);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+extern "C" int df_u3u4_border_sums(df_img dy, const float* dy_bound, const float* dbe, double* part, double* T, void* stream) {
+  DF_REQUIRE(h2_ok(dy) && dy_bound && dbe && part && T && (((uintptr_t)part) & 7) == 0 && (((uintptr_t)T) & 7) == 0, DF_E_ARG);
+  DF_REQUIRE(dy.h >= 2 && dy.w >= 2 && dy.c <= 1024 && (256 % (dy.c / 4)) == 0, DF_E_SHAPE);
+  hipLaunchKernelGGL(u3u4_border_sums_kernel, dim3(4, dy.n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, dy_bound, part);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(u3u4_tapsums_kernel, dim3((dy.c * 9 + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dbe, part, dy.n,
+                     dy.c, T);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+extern "C" int df_u3u4_decompose(const float* w3t, const float* w4, const float* b3, const float* dwe, const double* T, int O, int lat,
+                                 float* dw4, float* db4, float* dw3, float* db3, void* stream) {
+  DF_REQUIRE(w3t && w4 && b3 && dwe && T && (((uintptr_t)T) & 7) == 0 && dw4 && db4 && dw3 && db3, DF_E_ARG);
+  DF_REQUIRE(O > 0 && (O % 8) == 0 && lat > 0 && (lat % 16) == 0, DF_E_SHAPE);
+  const int grid = ((lat + 255) / 256) * (O * 9 / 8) + (lat / 16) * (lat / 16) + lat / 16;
+  hipLaunchKernelGGL(u3u4_decompose_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w3t, w4, b3, dwe, T, O, lat, dw4,
+                     db4, dw3, db3);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }

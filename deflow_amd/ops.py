@@ -332,6 +332,12 @@ def fuse_u5u1_on() -> bool:
     return os.environ.get("DF_FUSE_U5U1", "1") != "0"
 
 
+def fuse_u3u4_on() -> bool:
+    """DF_FUSE_U3U4=0 (or DF_FUSE_U5U1=0: no composed layers at all): every UpsampleSkip block runs its 1x1 skip convolution as a layer
+    instead of folded into the block's first 3x3 (unet._upsample_skip)"""
+    return fuse_u5u1_on() and os.environ.get("DF_FUSE_U3U4", "1") != "0"
+
+
 class WeightPrep:
     """Every convolution layer's per-step weight forms from ONE launch (df_weight_prep; round 4): transposed weights, [hi | lo] fp16
     planes of the weights and of their transpose (every layer: the 3x3 stride-1 kernels and, since the round's second session, the
@@ -339,15 +345,19 @@ class WeightPrep:
     ops.WPREP; ops.weight_transpose / _split_h2 / rows_l1max answer from it when the tensor they are asked about is one of its
     layers, and fall back to their own launches otherwise (plain autograd users, the decoder head's GEMM weights)."""
 
-    def __init__(self, convs, w_amax: torch.Tensor, compose=()):
+    def __init__(self, convs, w_amax: torch.Tensor, compose=(), compose_skip=()):
         """compose: (conv5, conv1) pairs -- a 3x3 layer and the 1x1 layer that is its only reader, with nothing in between (an UpsampleSkip
         block's last convolution and the next block's first): the prep then also holds the ONE 3x3 layer  conv1 o conv5  as an ordinary
         layer (weights We [O,kh,kw,I] and bias be in its own storage: self.composed), made by the compose launch inside df_weight_prep.
-        DF_FUSE_U5U1=0: none."""
+        DF_FUSE_U5U1=0: none.
+        compose_skip: (conv3, conv4) pairs -- an UpsampleSkip block's 1x1 skip convolution and the block's first 3x3, whose second half of
+        input channels is its only reader: the prep then also holds the ONE 3x3 layer of conv4's shape that reads [up(t) | b] instead of
+        [up(t) | conv3(b)] (self.composed_skip: We, be and the per-tap bias terms beta the border correction needs).  DF_FUSE_U3U4=0: none."""
         import numpy as np
         self.convs = [m for m in convs if m.weight.dim() == 4]
         self.compose = [(m5, m1) for m5, m1 in compose] if fuse_u5u1_on() else []
-        srcs = [m for pair in self.compose for m in pair]
+        self.compose_skip = [(m3, m4) for m3, m4 in compose_skip] if fuse_u3u4_on() else []
+        srcs = [m for pair in self.compose + self.compose_skip for m in pair]
         assert all(m.bias is not None for m in srcs)
         dev = (self.convs + srcs)[0].weight.device
         ws = [ohwi(m.weight) for m in self.convs]
@@ -356,9 +366,9 @@ class WeightPrep:
         ptrs = [w.data_ptr() for w in ws] + [m.bias.data_ptr() for m in self.convs if m.bias is not None]
         ptrs += [m.weight.data_ptr() for m in srcs] + [m.bias.data_ptr() for m in srcs]
         self.base = min(ptrs)
-        nc = len(self.compose)
-        nl = len(ws) + nc           # ordinary records (the composed layers among them); their source records follow
-        rec = np.zeros(nl + nc, dtype=[("w_off", "<i8"), ("b_off", "<i8"), ("wt_off", "<i8"), ("w2_off", "<i8"), ("wt2_off", "<i8"),
+        nc, ns = len(self.compose), len(self.compose_skip)
+        nl = len(ws) + nc + ns      # ordinary records (the composed layers among them); their source records follow
+        rec = np.zeros(nl + nc + ns, dtype=[("w_off", "<i8"), ("b_off", "<i8"), ("wt_off", "<i8"), ("w2_off", "<i8"), ("wt2_off", "<i8"),
                                        ("cout", "<i4"), ("taps", "<i4"), ("cin", "<i4"), ("split", "<i4"), ("blk0", "<i4"), ("pad", "<i4")])
         off, blk = 0, 0
         self.layer = {}
@@ -386,20 +396,39 @@ class WeightPrep:
             comp.append((i, we_off, be_off, off, n, (co, kh, kw, ci)))
             off += 3 * n
             blk += co + ci
+        for k, (m3, m4) in enumerate(self.compose_skip):
+            i = len(ws) + nc + k
+            co, kh, kw, ci = ohwi(m4.weight).shape
+            lat = m3.weight.shape[0]
+            assert (tuple(m3.weight.shape) == (lat, lat, 1, 1) and ci == 2 * lat and (kh, kw) == (3, 3) and co % 16 == 0 and lat % 16 == 0
+                    and m4.stride == (1, 1) and m4.padding == (1, 1) and m3.stride == (1, 1))
+            n = co * kh * kw * ci
+            we_off, be_off = off, off + n
+            off += n + (co + 63) // 64 * 64 + (co * 9 + 63) // 64 * 64          # We, be, beta [O][9]
+            rec[i] = (we_off, be_off, off, off + n, off + 2 * n, co, 9, ci, 1, blk, nl + nc + k)
+            rec[nl + nc + k] = ((m4.weight.data_ptr() - self.base) // 4, (m4.bias.data_ptr() - self.base) // 4, (m3.weight.data_ptr() - self.base) // 4,
+                                (m3.bias.data_ptr() - self.base) // 4, 3 * nl + nc + k, co, 9, ci, lat, 2 ** 31 - 1, 1)
+            comp.append((i, we_off, be_off, off, n, (co, kh, kw, ci)))
+            off += 3 * n
+            blk += co + ci
         self.total_blocks, self.nl = blk, nl
         self.table = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
         self.out = torch.empty(off, dtype=torch.float32, device=dev)
-        self._norms = torch.zeros(3 * nl + nc, dtype=torch.float32, device=dev)     # [nl][3], then the composed layers' max |We|
+        self._norms = torch.zeros(3 * nl + nc + ns, dtype=torch.float32, device=dev)     # [nl][3], then the composed layers' max |We|
         self.norms = self._norms[:3 * nl].view(nl, 3)
         self.w_amax = w_amax
         self.by_wt = {}                 # data_ptr of a transposed view -> (layer, plane offset) for _split_h2 of the transpose
         self.bias_of = {m.bias.data_ptr(): self.layer[w.data_ptr()][0] for w, m in zip(ws, self.convs) if m.bias is not None}
         self.comp_of, self.comp_amax = {}, {}
-        for k, ((m5, m1), (i, we_off, be_off, foff, n, shape)) in enumerate(zip(self.compose, comp)):
+        for k, ((ma, mb), (i, we_off, be_off, foff, n, shape)) in enumerate(zip(self.compose + self.compose_skip, comp)):
             we, be = self.out[we_off:we_off + n].view(shape), self.out[be_off:be_off + shape[0]]
             self.layer[we.data_ptr()] = (i, foff, n, shape, 1)
             self.bias_of[be.data_ptr()] = i
-            self.comp_of[(id(m5), id(m1))] = (we, be)
+            if k < nc:
+                self.comp_of[(id(ma), id(mb))] = (we, be)
+            else:
+                b0 = be_off + (shape[0] + 63) // 64 * 64
+                self.comp_of[(id(ma), id(mb))] = (we, be, self.out[b0:b0 + shape[0] * 9].view(shape[0], 9))
             self.comp_amax[i] = self._norms[3 * nl + k:3 * nl + k + 1]
         self._src_ptrs = [(m, m.weight.data_ptr(), m.bias.data_ptr(), tuple(m.weight.shape)) for m in srcs]
         self._anchor = torch.empty(0, dtype=torch.float32, device=dev)
@@ -407,6 +436,10 @@ class WeightPrep:
     def composed(self, m5, m1):
         """(We [O,kh,kw,I], be [O]) of the layer composed of conv5 and conv1 (views of this prep's storage, valid after run()), or None"""
         return self.comp_of.get((id(m5), id(m1)))
+
+    def composed_skip(self, m3, m4):
+        """(We [O,3,3,2 lat], be [O], beta [O,9]) of the layer composed of the skip convolution conv3 and conv4 (views, valid after run()), or None"""
+        return self.comp_of.get((id(m3), id(m4)))
 
     def stale(self) -> bool:
         """True when a conv parameter no longer lives where the table says (model.to(), load_state_dict(assign=True), p.data = ...):
@@ -661,12 +694,19 @@ def _conv_form(x: DfImg, y: DfImg, ks: int, stride: int, mode: int, epi: int, bi
 
 def conv2d(x: DfImg, w_ohwi: torch.Tensor, bias: Optional[torch.Tensor], y: DfImg, ks: int, stride: int = 1,
            mode: int = CONV_FWD, epi: int = EPI_BIAS, scale=None, shift=None, stats=None, accumulate: bool = False,
-           amax_out: Optional[torch.Tensor] = None, bwd_bn=None):
+           amax_out: Optional[torch.Tensor] = None, bwd_bn=None, x_border: Optional[torch.Tensor] = None):
     """amax_out: the slot the output's max |y| is accumulated into (fp16x2 mode; default: a fresh one) -- several producers of one
     buffer (the two halves of a concatenation) share a slot.
+    x_border = beta [C][9]: x (pre-split) is the raw output of a layer composed of a skip convolution and a zero-padded 3x3
+    (WeightPrep.composed_skip), whose single bias over-counts the folded bias at the border pixels: this call, x's first reader, takes
+    the excess off in place before it reads (df_u3u4_border_fix) -- the composed layer's own launch stays a plain convolution.
     bwd_bn = (y_prev, bn_ss_prev, partial): a 3x3 stride-1 DATA gradient whose output is the gradient of a BatchNorm + GELU layer's
     output -- the fp16x2 kernel's epilogue then also leaves that layer's backward partial sums in `partial` (df_conv2d_h2p_dgrad_bn).
     -> True if it did (the caller then skips ops.bn_gelu_bwd's reduce pass); ignored (False) on any other kernel."""
+    if x_border is not None:
+        assert x.elt == 2
+        with timed("u3u4_border_fix", bytes=16.0 * x.n * (x.h + x.w - 2) * x.c, tag=f"border fix {x.c} ch @{x.h}x{x.w} x{x.n}"):
+            call("df_u3u4_border_fix", x, ptr(x._amax), ptr(x_border), stream())
     prof = PROFILER
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -981,7 +1021,10 @@ def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld
     """dw (float memory [Cout][taps][Cin] with row pitch ld_co, starting dw_off elements in) (+)= dy^T x.
     want_bias: also return the bias gradient sum_p dy[p, :] (fused: the kernel already stages every dy tile).
     decompose = (w1, w5, b5, dw5, db5, dw1, db1): the layer is one composed of w5 [C,kh,kw,I], b5 and the 1x1 layer w1 [O,1,1,C]
-    (WeightPrep.composed); dw and the bias sum are then taken apart into the four parameter gradients (df_u5u1_decompose)."""
+    (WeightPrep.composed); dw and the bias sum are then taken apart into the four parameter gradients (df_u5u1_decompose).
+    decompose = ("skip", w3t, w4, b3, dw4, db4, dw3, db3): the layer is one composed of the 1x1 skip convolution w3 (w3t = its transpose
+    [I,1,1,C]), b3 and the zero-padded 3x3 w4 [O,3,3,2 lat] (WeightPrep.composed_skip); dw, the bias sum and the border sums of dy are
+    then taken apart into those parameters' gradients (df_u3u4_border_sums, df_u3u4_decompose)."""
     dev = dw.device
     assert decompose is None or (want_bias and ld_co is None and not accumulate and not dw_off)
     form, query, entry, mid, name = _wgrad_form(x, dy, ks, stride, row_counts)
@@ -1005,20 +1048,31 @@ def conv2d_wgrad(x: DfImg, dy: DfImg, ks: int, stride: int, dw: torch.Tensor, ld
         db = _f32(dy.c, device=dev)
         call("df_conv2d_wgrad_reduce_bias", ptr(ws), splits, dy.c, taps, x.c, dw.data_ptr() + 4 * dw_off,
              taps * x.c if ld_co is None else ld_co, int(accumulate), ptr(bias_ws), ptr(db), stream())
-        _decompose(decompose, dw, db, taps)
+        _decompose(decompose, dw, db, taps, dy)
         return db
     call("df_conv2d_wgrad_reduce", ptr(ws), splits, dy.c, taps, x.c, dw.data_ptr() + 4 * dw_off,
          taps * x.c if ld_co is None else ld_co, int(accumulate), stream())
     if want_bias:
         db = _f32(dy.c, device=dev)
         call("df_colsum_finalize", ptr(bias_ws), splits, dy.c, 1, ptr(db), 0, stream())
-        _decompose(decompose, dw, db, taps)
+        _decompose(decompose, dw, db, taps, dy)
         return db
     return None
 
 
-def _decompose(d: Optional[tuple], dwe: torch.Tensor, dbe: torch.Tensor, taps: int) -> None:
+def _decompose(d: Optional[tuple], dwe: torch.Tensor, dbe: torch.Tensor, taps: int, dy: DfImg) -> None:
     if d is None:
+        return
+    if d[0] == "skip":
+        _, w3t, w4, b3, dw4, db4, dw3, db3 = d
+        O, lat = w4.shape[0], w3t.shape[0]
+        assert taps == 9 and dy.elt == 2 and dy.c == O and w4.shape[-1] == 2 * lat
+        part = torch.empty(8 * dy.n * O + 9 * O, dtype=torch.float64, device=dwe.device)       # border sums per image, then T [O][9]
+        T = part[8 * dy.n * O:]
+        with timed("u3u4_border_sums", bytes=8.0 * dy.n * (dy.h + dy.w) * O, tag=f"border sums {O} ch @{dy.h}x{dy.w} x{dy.n}"):
+            call("df_u3u4_border_sums", dy, ptr(dy._amax), ptr(dbe), ptr(part), ptr(T), stream())
+        with timed("u3u4_decompose", flops=4.0 * O * taps * lat * lat, tag=f"u3u4 decompose 1x1 {lat}->{lat} of 3x3 {2 * lat}->{O}"):
+            call("df_u3u4_decompose", ptr(w3t), ptr(w4), ptr(b3), ptr(dwe), ptr(T), O, lat, ptr(dw4), ptr(db4), ptr(dw3), ptr(db3), stream())
         return
     w1, w5, b5, dw5, db5, dw1, db1 = d
     O, C, I = w1.shape[0], w5.shape[0], w5.shape[-1]
@@ -1026,7 +1080,16 @@ def _decompose(d: Optional[tuple], dwe: torch.Tensor, dbe: torch.Tensor, taps: i
         call("df_u5u1_decompose", ptr(w1), ptr(w5), ptr(b5), ptr(dwe), ptr(dbe), O, C, taps, I, ptr(dw5), ptr(db5), ptr(dw1), ptr(db1), stream())
 
 
-def upsample2x(x: DfImg, y: DfImg, align_corners: bool):
+def upsample2x(x: DfImg, y: DfImg, align_corners: bool, pack: Optional[DfImg] = None):
+    """pack = b (fp32 [N,2h,2w,C]): y is the FIRST half of a pre-split concatenation of 2 C channels whose second half is b itself (the
+    skip convolution runs folded into the 3x3 that reads the concatenation: WeightPrep.composed_skip) -- one kernel writes whole pixels,
+    the bilinear half exactly as df_upsample2x_h2 does and b split with the concatenation's scale (df_cat_pack_up)"""
+    if pack is not None:
+        assert y.elt == 2 and y.ld == 2 * y.c and pack.elt == 0
+        cat = DfImg(y.ptr, y.n, y.h, y.w, 2 * y.c, y.ld, y.grp_size, y.img_stride, y.grp_off, 2, 0)
+        with timed("cat_pack_up", bytes=4.0 * (x.n * x.h * x.w * x.c + 3 * y.n * y.h * y.w * y.c), tag=f"pack + bilinear x2 {2 * y.c} ch @{y.h}x{y.w} x{y.n}"):
+            call("df_cat_pack_up", x, pack, cat, int(align_corners), ptr(y._amax), stream())
+        return
     if y.elt == 2:      # the upsampled half of a pre-split concatenation: scale from the concatenation's bound (>= max |x|)
         call("df_upsample2x_h2", x, y, int(align_corners), ptr(y._amax), stream())
         return

@@ -556,20 +556,22 @@ class Trainer:
             # by the same launch; DF_FUSE_U5U1=0: none.  DF_WPREP=0 keeps them too, in a prep of their own that holds nothing else, so
             # that switch still changes only where the parameters' own forms come from
             pairs = backbone.fuse_pairs() if (ops.fuse_u5u1_on() and hasattr(backbone, "fuse_pairs")) else []
+            # ... and each block's skip convolution folded into the block's first 3x3 (unet.FastFlow3DUNet.fuse_skips; DF_FUSE_U3U4=0: none)
+            skips = backbone.fuse_skips() if (ops.fuse_u3u4_on() and hasattr(backbone, "fuse_skips")) else []
             if backbone is not None and os.environ.get("DF_WPREP", "1") != "0":
                 wp = getattr(self, "_wprep", None)
-                if wp and (wp.stale() or len(wp.compose) != len(pairs)):      # a parameter was re-assigned since the table of raw addresses was built
+                if wp and (wp.stale() or len(wp.compose) != len(pairs) or len(wp.compose_skip) != len(skips)):      # a parameter was re-assigned since the table of raw addresses was built
                     wp = None
                 if wp is None:
                     convs = [m for m in backbone.modules() if isinstance(m, torch.nn.Conv2d)]
-                    wp = self._wprep = ops.WeightPrep(convs, wa, compose=pairs) if convs else False
+                    wp = self._wprep = ops.WeightPrep(convs, wa, compose=pairs, compose_skip=skips) if convs else False
                 if wp:
                     wp.run(wa)
                     ops.WPREP = wp
-            elif pairs:
+            elif pairs or skips:
                 wp = getattr(self, "_wprep_fused", None)
-                if wp is None or wp.stale():
-                    wp = self._wprep_fused = ops.WeightPrep([], wa, compose=pairs)
+                if wp is None or wp.stale() or len(wp.compose) != len(pairs) or len(wp.compose_skip) != len(skips):
+                    wp = self._wprep_fused = ops.WeightPrep([], wa, compose=pairs, compose_skip=skips)
                 wp.run(wa)
                 ops.WPREP = wp
         try:

@@ -267,8 +267,30 @@ class FastFlow3DUNet(nn.Module):
               and call("df_conv2d_wgrad_h2p_ok", d(cin, 2), d(cout, 2), 3, 1) == 1)
         return (m5, m1) + comp if ok else None
 
+    def fuse_skips(self):
+        """(1x1 skip convolution, first 3x3) of the blocks where ops.WeightPrep folds the former into the latter (the second half of the 3x3's
+        input channels is the skip convolution's only reader, nothing in between).  The last block is not among them: its skip gradient is
+        taken at occupied pillars only, by a kernel that applies the skip weights itself (df_pillar_input_grad)"""
+        return [(m.u3, m.u4_u5[0]) for m in (self.decoder_step1, self.decoder_step2)]
+
+    def _composed_skip(self, m: UpsampleSkip):
+        """(We, be, beta) of block m's first 3x3 with its skip convolution folded in, if this step's WeightPrep holds the layer (it has
+        conv4's shape: the caller's pre-split check of that shape covers it); else None (DF_FUSE_U3U4=0, DF_FUSE_U5U1=0, no WeightPrep, the
+        last block)"""
+        if ops.WPREP is None or not ops.h2p_on() or not ops.fuse_u3u4_on():
+            return None
+        return ops.WPREP.composed_skip(m.u3, m.u4_u5[0])
+
+    @staticmethod
+    def _take_border(x: torch.Tensor):
+        """the pending border correction of a composed layer's raw output (beta of ops.WeightPrep.composed_skip), handed to x's FIRST reader"""
+        beta = getattr(x, "_df_border", None)
+        if beta is not None:
+            x._df_border = None
+        return beta
+
     def _conv(self, m: nn.Conv2d, x: torch.Tensor, y: DfImg, ks: int, tape: Optional[list], amax=None):
-        ops.conv2d(img(x), ops.ohwi(m.weight), m.bias.detach(), y, ks, 1, amax_out=amax)
+        ops.conv2d(img(x), ops.ohwi(m.weight), m.bias.detach(), y, ks, 1, amax_out=amax, x_border=self._take_border(x))
         if tape is not None:
             tape.append(("conv", m, x, ks))
 
@@ -296,6 +318,20 @@ class FastFlow3DUNet(nn.Module):
             t = torch.empty(B, h, w, lat, **f32)
             cat_amax = ops.amax_slot(dev) if (ops.h2_active() and not s16) else None
             self._conv(m.u1_u2[0], a, img(t), 1, tape, amax=cat_amax)
+        cs = self._composed_skip(m) if h2d else None
+        if cs is not None:
+            # the skip convolution folded into the block's first 3x3 (ops.WeightPrep.composed_skip): ONE 3x3 layer of u4's shape reads
+            # [up(t) | b]; one streaming kernel writes those whole pixels pre-split (scale: max(max |t|, max |b|), both measured), the layer's
+            # single bias is corrected at the border pixels by the first reader of its output (ops.conv2d x_border)
+            we, be, beta = cs
+            cat = ops.h2_empty((B, 2 * h, 2 * w, 2 * lat), dev, ops.h2_bound(ops.amax_of(img(b), dev), other=cat_amax))
+            ops.upsample2x(img(t), img(cat, lat, 0), self.align_corners, pack=img(b))
+            tape.append(("up", h, w, lat))
+            u4 = ops.h2_empty((B, 2 * h, 2 * w, outc), dev, ops.conv_out_bound(img(cat), we, be, dev))
+            ops.conv2d(img(cat), we, be, img(u4), 3, 1)
+            tape.append(("sconv", m.u3, m.u4_u5[0], cat, we))
+            u4._df_border = beta
+            return self._upsample_skip_tail(m, u4, tape, True)
         if h2d:
             w3 = ops.ohwi(m.u3.weight)
             cat_bound = ops.conv_out_bound(img(b), w3, m.u3.bias.detach(), dev, other=cat_amax)
@@ -322,6 +358,14 @@ class FastFlow3DUNet(nn.Module):
         else:
             u4 = torch.empty(B, 2 * h, 2 * w, outc, **mid)
         self._conv(m.u4_u5[0], cat, img(u4), 3, tape)
+        return self._upsample_skip_tail(m, u4, tape, h2d)
+
+    def _upsample_skip_tail(self, m: UpsampleSkip, u4: torch.Tensor, tape: Optional[list], h2d: bool) -> torch.Tensor:
+        """the block's last 3x3 on u4 [B,H,W,outc] -- alone, or composed with the next block's u1"""
+        B, h, w, outc = u4.shape
+        h, w = h // 2, w // 2
+        dev = u4.device
+        f32 = dict(dtype=torch.float32, device=dev)
         comp = self._composed_next(m, u4) if h2d else None
         if comp is not None:
             # the next block's u1 (1x1, its only reader) folded into this block's last 3x3: ONE 3x3 layer outc -> lat' straight into the next
@@ -329,7 +373,7 @@ class FastFlow3DUNet(nn.Module):
             m5, m1, we, be = comp
             tn = torch.empty(B, 2 * h, 2 * w, we.shape[0], **f32)
             slot = ops.amax_slot(dev)
-            ops.conv2d(img(u4), we, be, img(tn), 3, 1, amax_out=slot)
+            ops.conv2d(img(u4), we, be, img(tn), 3, 1, amax_out=slot, x_border=self._take_border(u4))
             tape.append(("fconv", m5, u4, 3, m1, we))
             tn._df_fused_t = slot
             return tn
@@ -528,28 +572,62 @@ class FastFlow3DUNet(nn.Module):
                     wgrad()
             return du4
 
-        def upsample_skip_bwd(dout: torch.Tensor, db: Optional[DfImg], acc_b: bool, dout_is_du4: bool = False):
+        def skip_conv_bwd(du4: torch.Tensor) -> torch.Tensor:
+            """backward of a block's first 3x3 with the skip convolution folded in (ops.WeightPrep.composed_skip): -> dcat, whose second
+            half IS d(b) (no 1x1 data gradient); the four parameters' gradients come out of the composed layer's weight gradient"""
+            _, m3, m4, x4, we = pop("sconv")
+            dcat = hold(torch.empty(x4.shape, **f32))
+            ops.conv2d(img(du4), ops.weight_transpose(we), None, img(dcat), 3, 1, mode=ops.CONV_DGRAD)
+
+            def wgrad():
+                w3, w4 = ops.ohwi(m3.weight), ops.ohwi(m4.weight)
+                dwe = hold(torch.empty_like(we))
+                dw3, dw4 = torch.empty_like(w3), torch.empty_like(w4)
+                db3, db4 = torch.empty_like(m3.bias.detach()), torch.empty_like(m4.bias.detach())
+                ops.conv2d_wgrad(img(x4), img(du4), 3, 1, dwe, want_bias=True,
+                                 decompose=("skip", hold(ops.weight_transpose(w3)), w4, m3.bias.detach(), dw4, db4, dw3, db3))
+                grads[m3.weight], grads[m3.bias] = dw3.permute(0, 3, 1, 2), db3
+                grads[m4.weight], grads[m4.bias] = dw4.permute(0, 3, 1, 2), db4
+
+            if ops.SIDE is None:
+                wgrad()
+            else:
+                with ops.SIDE.fork():
+                    wgrad()
+            return dcat
+
+        def upsample_skip_bwd(dout: torch.Tensor, db: Optional[DfImg], acc_b: bool, dout_is_du4: bool = False, b_shape=None):
             # reverse of: u1(a)->t ; up(t)->cat[:lat] ; u3(b)->cat[lat:] ; u4(cat) ; u5(u4)
             # (bf16-storage mode: u4 and cat were bfloat16 -> du4 is bfloat16 as well, so both 3x3 weight gradients see bf16
             #  x and dy; dcat stays fp32 for the 1x1 / upsample kernels behind it.  Pre-split mode: the same with h2 images.)
             # dout_is_du4: the block's last 3x3 ran composed with the next block's u1, whose backward (fused_conv_bwd) already produced d(u4)
-            # -> (d(a) [the block's input gradient: the output gradient of the block in front], False), or across a composed boundary
-            #    (d(u4) of the block in front, True)
+            # -> (d(a) [the block's input gradient: the output gradient of the block in front], False, d(b)), or across a composed boundary
+            #    (d(u4) of the block in front, True, d(b));  d(b): only with b_shape (else it went to `db`)
             if dout_is_du4:
                 du4 = dout
             else:
                 _, m5, x5, _ = tape[-1]
                 du4, wt5 = grad_like(x5, dout, m5)
                 plain_conv_bwd(dout, img(du4), False, wt5)
-            _, m4, x4, _ = tape[-1]
-            dcat = hold(torch.empty(x4.shape, **f32))
-            plain_conv_bwd(du4, img(dcat), False)
-            lat = dcat.shape[3] // 2
-            # u3
-            _, m3, xb, ks = pop("conv")
-            self._conv_bwd(m3, img(xb), img(dcat, lat, lat), 1, 1, db, acc_b, grads)
-            if db is None:
-                retained["dskip"] = (dcat, lat)
+            dbt = None      # d(b) of a block asked for with b_shape: a tensor of its own, or the second half of dcat (skip conv folded in)
+            if tape[-1][0] == "sconv":
+                assert b_shape is not None and db is None
+                dcat = skip_conv_bwd(du4)
+                lat = dcat.shape[3] // 2
+                dbt = dcat[..., lat:]
+            else:
+                _, m4, x4, _ = tape[-1]
+                dcat = hold(torch.empty(x4.shape, **f32))
+                plain_conv_bwd(du4, img(dcat), False)
+                lat = dcat.shape[3] // 2
+                # u3
+                _, m3, xb, ks = pop("conv")
+                if b_shape is not None:
+                    dbt = hold(torch.empty(b_shape, **f32))
+                    db = img(dbt)
+                self._conv_bwd(m3, img(xb), img(dcat, lat, lat), 1, 1, db, acc_b, grads)
+                if db is None:
+                    retained["dskip"] = (dcat, lat)
             _, h, w, lat_ = pop("up")
             dci = img(dcat, lat, 0)
             if tape[-1][0] == "fconv":
@@ -557,7 +635,7 @@ class FastFlow3DUNet(nn.Module):
                 # written pre-split by the bilinear backward itself, scaled by the bound below (4.5 max |dcat|)
                 dt = hold(ops.h2_empty((B, h, w, lat), dev, ops.h2_bound(ops.amax_of(dci, dev), slack=4.5)))
                 ops.upsample2x_bwd(dci, img(dt), self.align_corners)
-                return fused_conv_bwd(dt), True
+                return fused_conv_bwd(dt), True, dbt
             dt = hold(torch.empty(B, h, w, lat, **f32))
             ops.upsample2x_bwd(dci, img(dt), self.align_corners)
             if getattr(dci, "_amax", None) is not None:
@@ -575,7 +653,7 @@ class FastFlow3DUNet(nn.Module):
             else:
                 dA = hold(torch.empty(xa.shape, dtype=torch.float32 if a_like is None else a_like.dtype, device=dev))
             self._conv_bwd(m1, img(xa), img(dt), 1, 1, img(dA), False, grads, wt=wt1)
-            return dA, False
+            return dA, False, dbt
 
         # the gradient a block receives at its output (du, dT, dS) is bfloat16 when that block kept its u4 in bfloat16 (bf16-
         # storage mode): its two consumers are then the bf16-tile data- and weight-gradient kernels of the block's second conv
@@ -618,11 +696,11 @@ class FastFlow3DUNet(nn.Module):
             acc_b = True
         # conv entries of a block in tape order: u1, u3, u4, u5 -> from the end: u5 (x = u4), u4, u3, u1
         # (across a composed boundary dT / dS is the d(u4) of the block in front, and that block starts behind its last 3x3)
-        dT, comp32 = upsample_skip_bwd(du, None if sparse_input_grad else img(dbstar), acc_b)   # step3
-        dF = hold(torch.empty(B, H // 2, W // 2, 128, **f32))   # d(fstar)
-        dS, comp21 = upsample_skip_bwd(dT, img(dF), False, comp32)    # step2
-        dL = hold(torch.empty(B, H // 4, W // 4, 256, **f32))   # d(lstar)
-        dR, _ = upsample_skip_bwd(dS, img(dL), False, comp21)         # d(rstar) [B,H/8,W/8,512], fp32: the encoder's BatchNorm backward reads it
+        # (dF / dL: a tensor of its own, or -- the block's skip convolution folded into its first 3x3 -- the second half of the block's dcat,
+        #  a channel slice the encoder's accumulate and read paths take through img_pair with the wider row pitch)
+        dT, comp32, _ = upsample_skip_bwd(du, None if sparse_input_grad else img(dbstar), acc_b)   # step3
+        dS, comp21, dF = upsample_skip_bwd(dT, None, False, comp32, b_shape=(B, H // 2, W // 2, 128))    # step2; dF = d(fstar)
+        dR, _, dL = upsample_skip_bwd(dS, None, False, comp21, b_shape=(B, H // 4, W // 4, 256))         # step1; dL = d(lstar); dR = d(rstar) [B,H/8,W/8,512], fp32: the encoder's BatchNorm backward reads it
         if phase is not None:   # the four decoder steps are complete: their gradients can leave (optim.GradSink)
             phase([p for m in (self.decoder_step1, self.decoder_step2, self.decoder_step3, self.decoder_step4)
                    for p in m.parameters()])

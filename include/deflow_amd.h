@@ -452,6 +452,32 @@ int df_weight_prep(const float* params, const void* table, int nlayers, int tota
  * (O, C % 16 == 0, I % 64 == 0; sums in ascending index order in double, no float atomics: bit-reproducible) */
 int df_u5u1_decompose(const float* w1, const float* w5, const float* b5, const float* dwe, const float* dbe, int O, int C, int taps,
                       int I, float* dw5, float* db5, float* dw1, float* db1, void* stream);
+/* The SECOND kind of composed layer (unless DF_FUSE_U3U4=0 or DF_FUSE_U5U1=0): an UpsampleSkip block's 1x1 skip convolution (W3 [lat][lat],
+ * b3) folded into the block's first 3x3 (W4 [O][taps][2 lat] = [W4a | W4b], b4, zero padding 1), which is its only reader [REF deflow.py:32]:
+ *   We[o][tap][:lat] = W4a[o][tap][:]     We[o][tap][lat + i] = sum_c W4b[o][tap][c] W3[c][i]
+ *   beta[o][tap] = sum_c W4b[o][tap][c] b3[c]     be[o] = b4[o] + sum_tap beta[o][tap]
+ * The layer then reads [up(t) | b] instead of [up(t) | u3(b)].  Its record has pad > 0 like the first kind; the source record tab[pad]
+ * carries pad = 1 and  w_off = W4, b_off = b4, wt_off = W3, w2_off = b3 (elements in `params`), wt2_off = the `norms` slot of max |We|,
+ * cout = O (O % 8 == 0), taps, cin = 2 lat, split = lat.  beta [O][taps] is stored in `out` behind be (at b_off + (O rounded up to 64)),
+ * and norms[layer][2] also covers max_o (|b4[o]| + sum_tap |beta[o][tap]|): the bias side of the layer's a-priori output bound.
+ * At a border pixel the taps outside the image carry no b3 term: df_u3u4_border_fix subtracts  sum_{taps outside} beta[o][tap]  from the
+ * border pixels of the layer's output y (an h2 image of O channels with bound *y_bound; taps = 9). */
+int df_u3u4_border_fix(df_img y, const float* y_bound, const float* beta, void* stream);
+/* whole pixels of that layer's pre-split input cat [N,2h,2w,2 lat] (h2, scale of *cat_bound >= max(max |t|, max |b|)): channels [0, lat) =
+ * bilinear x2 of t [N,h,w,lat] (the planes df_upsample2x_h2 writes, bit for bit), channels [lat, 2 lat) = b [N,2h,2w,lat] (the planes
+ * df_h2_pack writes); t, b fp32 */
+int df_cat_pack_up(df_img t, df_img b, df_img cat, int align_corners, const float* cat_bound, void* stream);
+/* the tap sums of the layer's output gradient dy (h2 image [N,H,W,O], bound *dy_bound; dbe [O] = its column sum over all pixels):
+ *   T[o][tap] = sum_{p : p + tap inside} dy[o][p]  = dbe less the border row / column the tap excludes, plus the corner taken off twice
+ * from the border sums  part[q][n][o] (workspace, 8 N O doubles), q = 0 row 0, 1 row H-1, 2 column 0, 3 column W-1, 4..7 the corners
+ * (0,0), (0,W-1), (H-1,0), (H-1,W-1), per image in double; two small launches, every sum in a fixed order.  T [O][9] doubles */
+int df_u3u4_border_sums(df_img dy, const float* dy_bound, const float* dbe, double* part, double* T, void* stream);
+/* the five parameter gradients from the composed layer's weight gradient dwe [O][9][2 lat] and T:
+ *   dw4[o][tap][:lat] = dwe[o][tap][:lat]      dw4[o][tap][lat + c] = sum_i W3[c][i] dwe[o][tap][lat + i] + b3[c] T[o][tap]
+ *   dw3[c][i] = sum_{o,tap} W4b[o][tap][c] dwe[o][tap][lat + i]      db3[c] = sum_{o,tap} W4b[o][tap][c] T[o][tap]      db4[o] = T[o][centre]
+ * w3t = W3 transposed [i][c] (df_weight_prep's wt).  O % 8 == 0, lat % 16 == 0; sums in a fixed index order in double */
+int df_u3u4_decompose(const float* w3t, const float* w4, const float* b3, const float* dwe, const double* T, int O, int lat, float* dw4,
+                      float* db4, float* dw3, float* db3, void* stream);
 
 /* ------------------------------------------------------- point decoder (A6-A10) --------
  * Replaces ConvGRUDecoder / LinearDecoder forward_single ([REF decoder.py:72-199]): integer
