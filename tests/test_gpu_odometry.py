@@ -70,14 +70,16 @@ def bits(t):
 
 
 # ---- test 1: one accumulate -------------------------------------------------------------------------------------------------------------
-def accumulate(src, cs, dst, cd, T, stride, max_dist):
-    """the two grids as ``register`` files them, then ONE df_reg_accumulate with the per-row outputs on"""
+def accumulate(src, cs, dst, cd, T, stride, max_dist, src_grid=None):
+    """the two grids as ``register`` files them, then ONE df_reg_accumulate with the per-row outputs on.  src_grid: (xy_range, cell) of a
+    grid of its own for the source (the target's stays)"""
     from deflow_amd._lib import call, ptr, stream
     from deflow_amd.chamfer import RowGrid
     b, ns, dev = src.shape[0], src.shape[1], src.device
     grid = RowGrid(b, GRID["xy_range"], CELL, dev)
     assert (grid.minx, grid.miny, grid.G) == (RANGE[0], RANGE[1], G)
-    (s_rng, s_rows), (d_rng, d_rows) = grid.file(src, cs), grid.file(dst, cd)
+    sgrid = grid if src_grid is None else RowGrid(b, src_grid[0], src_grid[1], dev)
+    (s_rng, s_rows), (d_rng, d_rows) = sgrid.file(src, cs), grid.file(dst, cd)
     nblk = (ns + 255) // 256
     assert call("df_reg_ws_bytes", b, ns) == b * nblk * 256
     partial = torch.full((b, nblk, 32), float("nan"), dtype=torch.float64, device=dev)
@@ -85,9 +87,9 @@ def accumulate(src, cs, dst, cd, T, stride, max_dist):
     idx = torch.full((b, ns), 12345, dtype=torch.int32, device=dev)
     d2 = torch.full((b, ns), float("nan"), dtype=torch.float32, device=dev)
     w = torch.full((b, ns), float("nan"), dtype=torch.float32, device=dev)
-    call("df_reg_accumulate", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), RANGE[0], RANGE[1], CELL, G, b, ns, stride, ptr(T),
+    call("df_reg_accumulate", ptr(s_rng), ptr(s_rows), sgrid.G, ptr(d_rng), ptr(d_rows), RANGE[0], RANGE[1], CELL, G, b, ns, stride, ptr(T),
          max_dist ** 2, (max_dist / 3) ** 2, ptr(partial), ptr(q), ptr(idx), ptr(d2), ptr(w), stream())
-    return dict(partial=partial, q=q, idx=idx, d2=d2, w=w, s_rng=s_rng, s_rows=s_rows)
+    return dict(partial=partial, q=q, idx=idx, d2=d2, w=w, s_rng=s_rng, s_rows=s_rows, Gs=sgrid.G)
 
 
 def used_mask(out, b, ns, stride):
@@ -162,14 +164,15 @@ def test_one_accumulate(dev, stride):
 
 
 # ---- test 2, 3: register ----------------------------------------------------------------------------------------------------------------
-def check_register(dev, motion, stride, planar=False, extra=0, init_h=None):
+def check_register(dev, motion, stride, planar=False, extra=0, init_h=None, levels=((1.0, 6),), full=False):
+    """full: -> (T, info, T_true) instead of T"""
     from deflow_amd.odometry import register
     src_h, cs_h, dst_h, cd_h, T_true = make_batch(motion, extra=extra)
     src, cs, dst, cd = to_dev(dev, src_h, cs_h, dst_h, cd_h)
     if init_h is None:
         init_h = np.stack((np.eye(4), ARBITRARY, np.eye(4)))
     init = torch.from_numpy(init_h).to(dev)
-    T, info = register(src, cs, dst, cd, init=init, stride=stride, levels=((1.0, 6),), planar=planar, rows=True, **GRID)
+    T, info = register(src, cs, dst, cd, init=init, stride=stride, levels=levels, planar=planar, rows=True, **GRID)
     assert T.dtype == torch.float64 and T.shape == (B, 4, 4) and info["log"].shape == (B, 7, 4) and info["status"].dtype == torch.int32
     assert info["q"].shape == (B, N + extra, 3) and info["idx"].shape == (B, N + extra)
     T_h, status, log = T.cpu().numpy(), info["status"].cpu().numpy(), info["log"].cpu().numpy()
@@ -182,7 +185,7 @@ def check_register(dev, motion, stride, planar=False, extra=0, init_h=None):
     assert np.all(T_h[:, 3] == [0, 0, 0, 1])
     if extra:                                                        # the rows 30 m above: used, never inliers
         assert np.all(info["idx"][0, N:].cpu().numpy() == -1) and np.all(info["w"][0, N:].cpu().numpy() == 0)
-    return T
+    return (T, info, T_true) if full else T
 
 
 @pytest.mark.parametrize("stride", [1, 3])
@@ -221,6 +224,106 @@ def test_register_argument_errors(dev):
         register(src, cs, dst, cd, mask_s=torch.ones(B, N, device=dev))
     with pytest.raises(TypeError, match="register: dst must be a CUDA tensor"):
         register(src, cs, dst.cpu(), cd)
+
+
+# ---- the turning branch, status 3, several levels ---------------------------------------------------------------------------------------
+def partner_margin(src, count, dst, motion_T):
+    """float64, at identity: (every participating source row's nearest target row is the row it was moved to, the smallest distance by
+    which the second-nearest target is farther).  ``moved`` permutes: the partner is found as the target nearest to the MOVED row."""
+    ok = reg_ref.participating(src, count)
+    s = src[ok].astype(np.float64)
+    d = dst[:count].astype(np.float64)
+    partner = (((s @ motion_T[:3, :3].T + motion_T[:3, 3])[:, None, :] - d[None]) ** 2).sum(axis=2)
+    assert partner.min(axis=1).max() <= 1e-10               # (the fp32 rounding of the moved row)
+    dist = np.sqrt(((s[:, None, :] - d[None]) ** 2).sum(axis=2))
+    order = np.sort(dist, axis=1)
+    return bool(np.all(dist.argmin(axis=1) == partner.argmin(axis=1))), float((order[:, 1] - order[:, 0]).min())
+
+
+@pytest.mark.parametrize("stride", [1, 3])
+def test_register_through_the_closed_form_branch(dev, stride):
+    """MOTION with three times the yaw: the first iteration's |omega| is 0.0121 >= 1e-2, so the closed form of the exponential runs
+    inside the loop.  Conditions on the input: every source row's nearest target at identity is its true partner, the second-nearest at
+    least 0.09 m farther (0.0945 m at 700 rows, 0.296 m at 333).  The float64 helper reaches 1.3e-8 and 1.9e-8 in six iterations."""
+    src_h, cs_h, dst_h, cd_h, T_true = make_batch(reg_ref.MOTION_TURN)
+    for b in (0, 2):
+        true_partner, margin = partner_margin(src_h[b], COUNTS[b], dst_h[b], T_true)
+        print("sample", b, "second-nearest margin", margin)
+        assert true_partner and margin >= 0.09
+    T, info, _ = check_register(dev, reg_ref.MOTION_TURN, stride, full=True)
+    log = info["log"].cpu().numpy()
+    print("stride", stride, "|omega| of iteration 0", log[:, 0, 2].tolist())
+    assert log[0, 0, 2] >= 1e-2 and log[2, 0, 2] >= 1e-2
+
+
+def test_register_reports_a_singular_system(dev):
+    """status 3 through ``register``: every row at the origin (H's rotation block is 0) and a cloud on the x axis (rank 5: H[0][0] = sum
+    w (qy^2 + qz^2) is exactly 0, also from an init that turns about x and shifts along it).  T == init bit for bit, |omega| = |v| = 0 in
+    every log row."""
+    from deflow_amd.odometry import register
+    n = 60
+    pts = np.zeros((2, n, 3), dtype=np.float32)
+    pts[1, :, 0] = -15.0 + 0.5 * np.arange(n)
+    c, s = np.cos(0.3), np.sin(0.3)
+    init_h = np.stack((ARBITRARY.copy(), np.array([[1, 0, 0, 0.125], [0, c, -s, 0], [0, s, c, 0], [0, 0, 0, 1.0]])))
+    init_h[0, :3, 3] = 0.0                                   # a rotation about the origin leaves the rows at the origin
+    src = torch.from_numpy(pts).to(dev)
+    cnt = torch.full((2,), n, dtype=torch.int32, device=dev)
+    T, info = register(src, cnt, src.clone(), cnt, init=torch.from_numpy(init_h).to(dev), stride=1, levels=((1.0, 3),), **GRID)
+    log = info["log"].cpu().numpy()
+    print("status", info["status"].tolist(), "log", log.tolist())
+    assert info["status"].tolist() == [3, 3]
+    assert T.cpu().numpy().tobytes() == init_h.tobytes()
+    assert log.shape == (2, 4, 4) and np.all(log[:, :, 0] == n) and np.all(log[:, :, 2:] == 0)
+
+
+@pytest.mark.parametrize("stride", [1, 3])
+def test_register_over_several_levels(dev, stride):
+    """three levels of two iterations: T against the truth, at stride 1 against the float64 restatement with the same levels; the log has
+    one row per iteration and one for the final T; the inlier count does not increase from level to level"""
+    levels = ((2.0, 2), (1.0, 2), (0.5, 2))
+    T, info, T_true = check_register(dev, reg_ref.MOTION, stride, levels=levels, full=True)
+    T_h, log = T.cpu().numpy(), info["log"].cpu().numpy()
+    assert log.shape == (B, 7, 4)
+    for b in (0, 2):
+        per_level = log[b, [1, 3, 5, 6], 0]
+        print("stride", stride, "sample", b, "inliers per level and final", per_level.tolist(), "|T - T_true|max", np.abs(T_h[b] - T_true).max())
+        assert np.all(np.diff(per_level) <= 0) and per_level[-1] > 0
+    if stride == 1:
+        src_h, cs_h, dst_h, cd_h, _ = make_batch(reg_ref.MOTION)
+        for b in (0, 2):
+            T_ref, status = reg_ref.register(src_h[b], cs_h[b], dst_h[b], cd_h[b], levels)
+            err = np.abs(T_h[b] - T_ref).max()
+            print("sample", b, "|T - restatement|max", err)
+            assert status == 0 and err <= TOL
+
+
+# ---- a source grid of its own -----------------------------------------------------------------------------------------------------------
+def test_accumulate_with_a_source_grid_of_its_own(dev):
+    """The source filed under a 6 x 6 grid of 8 m cells over (-24, -24, 24, 24) while the target keeps its 12 x 12 grid of 2.7 m cells:
+    the header lets the source's grid set the ORDER of the rows and nothing else.  Stride 1: q, idx, d2, w bit-identical to the run with
+    one grid; the slab summed over blocks within the summation-order bound 2 n 2^-53 (n = 697: 1.5e-13) in test_one_accumulate's norms."""
+    src_h, cs_h, dst_h, cd_h, _ = make_batch(nan_dst=True)
+    src, cs, dst, cd = to_dev(dev, src_h, cs_h, dst_h, cd_h)
+    T_h = np.stack((reg_ref.se3_exp((0.0005, -0.001, 0.003, 0.08, -0.03, 0.01)), ARBITRARY, np.eye(4)))
+    T = torch.from_numpy(T_h).to(dev).reshape(B, 16).contiguous()
+    one = accumulate(src, cs, dst, cd, T, 1, 1.0)
+    own = accumulate(src, cs, dst, cd, T, 1, 1.0, src_grid=((-24.0, -24.0, 24.0, 24.0), 8.0))
+    assert one["Gs"] == G and own["Gs"] == 6
+    assert not torch.equal(one["s_rows"], own["s_rows"])                 # the order of the rows really differs
+    assert all(bits(one[k]) == bits(own[k]) for k in ("q", "idx", "d2", "w"))
+    Sa, Sb = one["partial"].cpu().numpy().sum(axis=1), own["partial"].cpu().numpy().sum(axis=1)
+    assert np.all(Sb[1] == 0) and np.all(Sa[1] == 0)
+    for b in (0, 2):
+        n = Sa[b, 29]
+        bound = 2 * n * 2.0 ** -53
+        Ha, ga, sw, swr, _ = reg_ref.unpack_slab(Sa[b])
+        Hb, gb, swb, swrb, nb = reg_ref.unpack_slab(Sb[b])
+        dH = (np.abs(Ha - Hb) / np.sqrt(np.outer(np.diag(Ha), np.diag(Ha)))).max()
+        dg = (np.abs(ga - gb) / np.sqrt(np.diag(Ha) * swr)).max()
+        print("sample", b, "n", n, "bound", bound, "dH", dH, "dg", dg, "dsw", abs(swb / sw - 1), "dswr", abs(swrb / swr - 1))
+        assert nb == n and n == int((one["idx"][b] >= 0).sum()) and n == (697, 0, 332)[b]       # (dst row 7 of sample 0 is NaN)
+        assert dH <= bound and dg <= bound and abs(swb / sw - 1) <= bound and abs(swrb / swr - 1) <= bound
 
 
 # ---- test 4: a synthetic scene -------------------------------------------------------------------------------------------------------------

@@ -58,6 +58,104 @@ def test_se3_exp_branches_agree():
     assert np.abs(a - b).max() < 1e-6
 
 
+# ---- the independent reference of df_reg_solve (tests/test_gpu_reg_solve.py) -----------------------------------------------------------
+EXP_THETAS = (0.0, 1e-9, 1e-6, 1e-3, 0.0099, 0.0099999, 0.01, 0.0100001, 0.0101, 0.05, 0.3, 1.2, 3.03, 3.14159)
+EXP_AXES = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (0.6, -0.48, 0.64))
+
+
+def test_slab_pack_round_trip():
+    H, g, sw, swr, n = reg_ref.base_sums()
+    S = reg_ref.pack_slab(H, g, sw, swr, n)
+    assert S.shape == (32,) and S.dtype == np.float64 and S[30] == 0 and S[31] == 0
+    assert S[0] == H[0, 0] and S[5] == H[0, 5] and S[6] == H[1, 1] and S[11] == H[2, 2] and S[20] == H[5, 5]      # row by row
+    assert np.array_equal(S[21:27], g) and (S[27], S[28], S[29]) == (sw, swr, n) and n == 700
+    H2, g2, sw2, swr2, n2 = reg_ref.unpack_slab(S)
+    assert np.array_equal(H2, np.triu(H) + np.triu(H, 1).T) and np.array_equal(g2, g) and (sw2, swr2, n2) == (sw, swr, n)
+    assert np.array_equal(reg_ref.pack_slab(H2, g2, sw2, swr2, n2), S)
+    # split_slab: one row is the row; more rows sum to S within the bits the offsets cost, and the order of the additions shows
+    assert np.array_equal(reg_ref.split_slab(S, 1), S[None])
+    for nblk in (2, 3, 4, 4097):
+        rows = reg_ref.split_slab(S, nblk)
+        assert rows.shape == (nblk, 32) and np.all(rows[:, 30:] == 0)
+        up = reg_ref.sum_rows(rows)
+        assert np.abs(up - S).max() <= 2.0 ** -11 * np.abs(S).max() and np.all(np.abs(up - S) <= 2.0 ** -11 * np.abs(S))
+        if nblk >= 3:
+            assert not np.array_equal(up, reg_ref.sum_rows(rows[::-1]))
+        if nblk >= 4:
+            assert not np.array_equal(up, reg_ref.sum_rows_pairwise(rows))
+    probe = np.array([2.0 ** 53, 1.0, 1.0, -2.0 ** 53])[:, None] * np.ones((1, 32))
+    assert reg_ref.sum_rows(probe)[29] == 0 and reg_ref.sum_rows_pairwise(probe)[29] == 1 and reg_ref.sum_rows(probe[::-1])[29] == 2
+
+
+def test_se3_exp_against_the_matrix_exponential():
+    """The restated closed form / series against torch.linalg.matrix_exp of the 4 x 4 twist on the WHOLE matrix, translation column
+    included, at every theta and axis of the GPU test's table and at the threshold, v = (0.3, -2, 11), and v = 0 at the two thetas where
+    the GPU test has it.  Bound: 64 ulp of max(1, max|T|) = 2^-46 max(1, max|T|) = 1.6e-13 with this v.  Measured: largest difference
+    3.4e-14 (theta = 3.14159).  Where the TWIST's norm is around 1e-2 -- v = 0 and theta = 0.0099 or 0.0101 -- matrix_exp itself is
+    7.7e-14 and 8.6e-14 off (about a coordinate axis, where cos and sin give the exact answer and se3_exp is within 1 ulp at every
+    theta; 1e-18 at 1e-3, 2e-16 at 0.05): with max|T| = 1 the reference would miss its own bound of 1.4e-14 there, so v = 0 is taken
+    at theta = 0 and 0.3.  With |v| = 11 the norm is 11 at every theta and that regime is not entered."""
+    worst = 0.0
+    for th in EXP_THETAS:
+        for ax in EXP_AXES:
+            for vv in ((0.3, -2.0, 11.0),) + (((0.0, 0.0, 0.0),) if th in reg_ref.EXP_V0_THETAS else ()):
+                d = np.concatenate((np.array(ax) * th, vv))
+                A, Bm = reg_ref.se3_exp(d), reg_ref.se3_exp_indep(d)
+                err, bound = np.abs(A - Bm).max(), 2.0 ** -46 * max(1.0, np.abs(Bm).max())
+                worst = max(worst, err)
+                assert err <= bound, (th, ax, vv, err, bound)
+                assert np.array_equal(Bm[3], [0, 0, 0, 1])
+    print("se3_exp against matrix_exp: largest difference", worst)
+    for th in EXP_THETAS:                    # about x the exact answer is known: the restatement is the accurate one of the two
+        T, c, s_ = reg_ref.se3_exp((th, 0, 0, 0, 0, 0)), math.cos(th), math.sin(th)
+        assert np.abs(T[:3, :3] - np.array([[1, 0, 0], [0, c, -s_], [0, s_, c]])).max() <= 2.0 ** -52
+
+
+def test_solve_ref_on_a_planted_step():
+    """solve_hp returns the planted step, solve agrees with it, solve_ref puts the pieces together; the status rules"""
+    H, _, sw, swr, n = reg_ref.base_sums()
+    assert np.linalg.cond(H) <= 1e3
+    delta = np.array([0.02, -0.03, 0.05, 0.3, -2.0, 11.0])
+    S = reg_ref.pack_slab(H, -H @ delta, sw, swr, n)
+    st, x = reg_ref.solve_hp(*reg_ref.unpack_slab(S)[:2], n, 50, False)
+    assert st == 0 and x.dtype == np.longdouble and np.abs(x.astype(np.float64) - delta).max() <= 1e-12
+    st64, x64 = reg_ref.solve(*reg_ref.unpack_slab(S)[:2], n, 50, False)
+    assert st64 == 0 and np.abs(x64 - x.astype(np.float64)).max() <= 1e-12
+    T0 = reg_ref.se3_exp((0.3, -0.2, 0.1, 1.0, 2.0, 3.0))
+    st, T, log = reg_ref.solve_ref(S, 50, False, T0)
+    assert st == 0 and np.abs(T - reg_ref.se3_exp(delta) @ T0).max() <= 2.0 ** -46 * np.abs(T).max()
+    assert log[0] == 700 and log[1] == swr / sw
+    assert abs(log[2] - np.linalg.norm(delta[:3])) <= 1e-13 and abs(log[3] - np.linalg.norm(delta[3:])) <= 1e-11
+    # planar: the 4 x 4 system left after the replacement, whatever g[0], g[1] hold
+    Sp = S.copy()
+    Sp[21:23] = 1e6
+    st, Tp, logp = reg_ref.solve_ref(Sp, 50, True, np.eye(4))
+    Hs, gs = H[2:, 2:], (-H @ delta)[2:]
+    xs = np.linalg.solve(Hs, -gs)
+    assert st == 0 and np.abs(Tp - reg_ref.se3_exp(np.concatenate(([0, 0], xs)))).max() <= 1e-11 and abs(logp[2] - abs(xs[0])) <= 1e-13
+    # statuses: T0 comes back, the last two log entries stay 0
+    for kw, want in ((dict(min_inliers=701), 2), (dict(n=np.nan), 2), (dict(H55=np.inf), 3), (dict(g3=np.inf), 3), (dict(H01=np.nan), 3),
+                     (dict(H00=0.0), 3)):
+        Sb = S.copy()
+        if "n" in kw:
+            Sb[29] = kw["n"]
+        if "H55" in kw:
+            Sb[20] = kw["H55"]
+        if "g3" in kw:
+            Sb[24] = kw["g3"]
+        if "H01" in kw:
+            Sb[1] = kw["H01"]
+        if "H00" in kw:
+            Sb[0] = kw["H00"]
+        st, Tb, lb = reg_ref.solve_ref(Sb, kw.get("min_inliers", 50), False, T0)
+        assert st == want and Tb.tobytes() == T0.tobytes() and np.all(lb[2:] == 0), kw
+        assert reg_ref.solve(*reg_ref.unpack_slab(Sb)[:2], Sb[29], kw.get("min_inliers", 50), False)[0] == want, kw
+    assert reg_ref.solve_ref(np.zeros(32), 0, False, T0)[0] == 3 and reg_ref.solve_ref(np.zeros(32), 1, False, T0)[0] == 2
+    Sz = S.copy()
+    Sz[0] = 0.0                                          # H00 = 0: fatal in 6 DoF, replaced in the planar solve
+    assert reg_ref.solve_ref(Sz, 50, True, T0)[0] == 0
+
+
 # ---- chain and sidecar ------------------------------------------------------------------------------------------------------------------
 def _poses(n, seed=3):
     rng = np.random.default_rng(seed)
