@@ -7,6 +7,10 @@
 //                       (w (|q|^2 I - q q^T): 6, w q: 3, w: 1): those, g's 6, sum w d2 and the inlier count -- 18 values -- go through the
 //                       wave butterfly and the block's LDS in float64, and the 32-wide slab row is laid out from them (a copy or an exact
 //                       negation of a sum, or 0).  One slab row per block, no atomics.
+//   df_reg_accumulate_plane   the same thread mapping, transform and search; the residual is e = n . (q - d) with n the matched target
+//                       row's normal (normals.hip: df_normals), the row of the normal equations a = (q x n, n).  H = sum w a a^T has no
+//                       structure to exploit: its 21 sums, g's 6, sum w, sum w e^2 and the inlier count -- 30 values -- ARE the slab's
+//                       columns 0..29 and go through the same butterfly and LDS order.  df_reg_solve serves both.
 //   df_reg_solve        one 64-thread block per sample: lanes 0..31 add the slab rows in ascending block order, lane 0 solves the 6 x 6
 //                       system by Cholesky in float64 and applies the closed-form SE(3) exponential to T in place.
 #include <math.h>
@@ -127,6 +131,113 @@ __global__ __launch_bounds__(256) void reg_accumulate_kernel(const int32_t* __re
     const int sg = REG_SGN[tid];
     partial[((int64_t)b * gridDim.x + blockIdx.x) * REG_SLAB + tid] = sg > 0 ? s : (sg < 0 ? -s : 0.0);
   }
+}
+
+// ---- point-to-plane: the same mapping, transform and search; the residual is the distance to the matched row's plane -----------------
+constexpr int REG_NRED_PLANE = 30;  // the slab's columns 0..29 themselves: nothing is laid out afterwards
+
+__global__ __launch_bounds__(256) void reg_fill_plane_kernel(int64_t n, float* __restrict__ q_out, int32_t* __restrict__ idx_out,
+                                                             float* __restrict__ d2_out, float* __restrict__ w_out,
+                                                             float* __restrict__ e_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (q_out) {
+    q_out[i * 3] = 0.f;
+    q_out[i * 3 + 1] = 0.f;
+    q_out[i * 3 + 2] = 0.f;
+  }
+  if (idx_out) idx_out[i] = -1;
+  if (d2_out) d2_out[i] = INFINITY;
+  if (w_out) w_out[i] = 0.f;
+  if (e_out) e_out[i] = 0.f;
+}
+
+// Every term is a product (or a sum of products) in which each factor that comes from n changes sign with n and nothing else does: the
+// rounding of a product, of a sum of two such products and of an fma of them is symmetric, so negating the fp32 n negates a and e
+// exactly and leaves w, w a a^T, w a e and w e^2 bit for bit.  (+ 0.0 below: a -0 product enters the sums as +0 whatever n's sign.)
+__global__ __launch_bounds__(256) void reg_accumulate_plane_kernel(const int32_t* __restrict__ src_rng, const f32x4* __restrict__ src_sorted,
+                                                                   int Gs, const int32_t* __restrict__ dst_rng,
+                                                                   const f32x4* __restrict__ dst_sorted, const f32x4* __restrict__ dst_normals,
+                                                                   float minx, float miny, float cell, int G, int Ns, int Nd, int stride,
+                                                                   const double* __restrict__ T, float max_dist2, float k2,
+                                                                   double* __restrict__ partial, float* __restrict__ q_out,
+                                                                   int32_t* __restrict__ idx_out, float* __restrict__ d2_out,
+                                                                   float* __restrict__ w_out, float* __restrict__ e_out) {
+  const int b = blockIdx.y, tid = threadIdx.x, t = blockIdx.x * 256 + tid;
+  const int64_t c0 = (int64_t)b * Gs * Gs;
+  const int s0 = src_rng[2 * c0], s1 = src_rng[2 * (c0 + (int64_t)Gs * Gs - 1) + 1];     // the sample's span in the source's cell order
+  double a[REG_NRED_PLANE];
+#pragma unroll
+  for (int k = 0; k < REG_NRED_PLANE; ++k) a[k] = 0.0;
+  const int64_t p = (int64_t)s0 + t;
+  // (every thread stays for the reductions below: no early return)
+  if (t < Ns && s0 >= 0 && p < (int64_t)s1 && p < (int64_t)gridDim.y * Ns && t % stride == 0) {
+    const f32x4 v = src_sorted[p];
+    const float vw = v.w;
+    const int row = __builtin_bit_cast(int, vw);
+    const double* Tb = T + (int64_t)b * 16;
+    const float qx = fmaf((float)Tb[2], v.z, fmaf((float)Tb[1], v.y, fmaf((float)Tb[0], v.x, (float)Tb[3])));
+    const float qy = fmaf((float)Tb[6], v.z, fmaf((float)Tb[5], v.y, fmaf((float)Tb[4], v.x, (float)Tb[7])));
+    const float qz = fmaf((float)Tb[10], v.z, fmaf((float)Tb[9], v.y, fmaf((float)Tb[8], v.x, (float)Tb[11])));
+    float best = INFINITY;
+    int bi = -1;
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (nn_finite3(qx, qy, qz))
+      nn_ring_search<true>(qx, qy, qz, dst_rng + (int64_t)b * G * G * 2, dst_sorted, minx, miny, cell, G, max_dist2, best, bi, bv);
+    float w = 0.f, e = 0.f;
+    f32x4 n = {0.f, 0.f, 0.f, -1.f};
+    if (best <= max_dist2 && (unsigned)bi < (unsigned)Nd) n = dst_normals[(int64_t)b * Nd + bi];
+    if (n.w >= 0.f) {
+      const float rx = qx - bv.x, ry = qy - bv.y, rz = qz - bv.z;
+      e = n.x * rx + n.y * ry + n.z * rz;
+      const float e2 = e * e;
+      const float u = k2 / (k2 + e2);
+      w = u * u;
+      const float av[6] = {qy * n.z - qz * n.y, qz * n.x - qx * n.z, qx * n.y - qy * n.x, n.x, n.y, n.z};
+      int c = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const float wa = w * av[i];
+#pragma unroll
+        for (int j = i; j < 6; ++j) a[c++] = (double)(wa * av[j]) + 0.0;
+        a[21 + i] = (double)(wa * e) + 0.0;
+      }
+      a[27] = (double)w;
+      a[28] = (double)((w * e) * e);
+      a[29] = 1.0;
+    } else {
+      best = INFINITY;
+      bi = -1;
+    }
+    if ((unsigned)row < (unsigned)Ns) {
+      const int64_t o = (int64_t)b * Ns + row;
+      if (q_out) {
+        q_out[o * 3] = qx;
+        q_out[o * 3 + 1] = qy;
+        q_out[o * 3 + 2] = qz;
+      }
+      if (idx_out) idx_out[o] = bi;
+      if (d2_out) d2_out[o] = best;
+      if (w_out) w_out[o] = w;
+      if (e_out) e_out[o] = e;
+    }
+  }
+  // fixed order: the wave's xor butterfly, then the block's waves in wave order
+#pragma unroll
+  for (int k = 0; k < REG_NRED_PLANE; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+  }
+  __shared__ double red[4][REG_SLAB];
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < REG_NRED_PLANE; ++k) red[tid >> 6][k] = a[k];
+    red[tid >> 6][30] = 0.0;
+    red[tid >> 6][31] = 0.0;
+  }
+  __syncthreads();
+  if (tid < REG_SLAB)
+    partial[((int64_t)b * gridDim.x + blockIdx.x) * REG_SLAB + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
 __global__ __launch_bounds__(64) void reg_solve_kernel(const double* __restrict__ partial, int nblk, int min_inliers, int planar,
@@ -305,6 +416,31 @@ extern "C" int df_reg_accumulate(const int32_t* src_rng, const float* src_sorted
   hipLaunchKernelGGL(reg_accumulate_kernel, dim3((Ns + 255) / 256, B), dim3(256), 0, s, src_rng, reinterpret_cast<const f32x4*>(src_sorted),
                      Gs, dst_rng, reinterpret_cast<const f32x4*>(dst_sorted), minx, miny, cell, G, Ns, stride, T, max_dist2, k2, partial,
                      q_out, idx_out, d2_out, w_out);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+extern "C" int df_reg_accumulate_plane(const int32_t* src_rng, const float* src_sorted, int Gs, const int32_t* dst_rng,
+                                       const float* dst_sorted, const float* dst_normals, float minx, float miny, float cell, int G, int B,
+                                       int Ns, int Nd, int stride, const double* T, float max_dist2, float k2, double* partial, float* q_out,
+                                       int32_t* idx_out, float* d2_out, float* w_out, float* e_out, void* stream) {
+  DF_REQUIRE(src_rng && src_sorted && dst_rng && dst_sorted && dst_normals && T && partial, DF_E_ARG);
+  DF_REQUIRE(nn_rows_ok(B, Ns) && nn_rows_ok(B, Nd) && nn_grid_ok(B, G) && nn_grid_ok(B, Gs) && B <= 65535, DF_E_SHAPE);
+  DF_REQUIRE(isfinite(minx) && isfinite(miny) && reg_pos_finite(cell) && reg_pos_finite(max_dist2) && reg_pos_finite(k2), DF_E_ARG);
+  DF_REQUIRE(stride >= 1 && stride <= 1024, DF_E_ARG);
+  DF_REQUIRE(df_aligned16(src_sorted) && df_aligned16(dst_sorted) && df_aligned16(dst_normals) &&
+                 (((uintptr_t)partial | (uintptr_t)T) & 7u) == 0,
+             DF_E_ALIGN);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (q_out || idx_out || d2_out || w_out || e_out) {
+    const int64_t n = (int64_t)B * Ns;
+    hipLaunchKernelGGL(reg_fill_plane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, q_out, idx_out, d2_out, w_out, e_out);
+    DF_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(reg_accumulate_plane_kernel, dim3((Ns + 255) / 256, B), dim3(256), 0, s, src_rng,
+                     reinterpret_cast<const f32x4*>(src_sorted), Gs, dst_rng, reinterpret_cast<const f32x4*>(dst_sorted),
+                     reinterpret_cast<const f32x4*>(dst_normals), minx, miny, cell, G, Ns, Nd, stride, T, max_dist2, k2, partial, q_out,
+                     idx_out, d2_out, w_out, e_out);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }

@@ -4,7 +4,9 @@ frame with it).
 
 UNPINNED: people with their own recordings are normally sent to an external LiDAR odometry for this.  What runs here is this project's own
 definition -- include/deflow_amd.h and DESIGN.md section 6r -- a scan-to-scan, point-to-point ICP with Geman-McClure weights in 6 degrees
-of freedom: no map, no loop closure, no motion un-distortion, and nothing about its accuracy on real sweeps has been measured.  Scene flow
+of freedom (``residual="point"``, the default) or, with ``residual="plane"``, a point-to-plane ICP against normals of the target that
+``normals`` estimates on the GPU: no map, no loop closure, no motion un-distortion, and nothing about its accuracy on real sweeps has been
+measured.  Scene flow
 needs only the relative transform of consecutive sweeps (the reference's ``ego_motion``), which is what it estimates; the poses are those
 transforms chained.
 
@@ -26,15 +28,18 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
-from .args import labels, tensor
+from .args import cloud, integer, labels, positive, tensor
 from .chamfer import GRID_RANGE, RowGrid
 
 SIDECAR_SUFFIX = ".pose.npz"
 POSE_SOURCES = ("auto", "file", "sidecar")
 # this project's own choices, unmeasured: gate distances of the levels (kernel = max_dist / 3), iterations per level, the grids' cell
 LEVELS = (2.0, 1.0, 0.5)
+RESIDUALS = ("point", "plane")
+# residual: which default is better on real sweeps is unmeasured, so the point residual stays.  normal_*: choices, not measurements --
+# the neighbourhood's radius (<= cell), the fewest rows a normal is fitted to, the largest curvature lambda0 / trace of a valid normal
 DEFAULTS: Dict[str, Any] = {"xy_range": GRID_RANGE, "cell": 1.0, "stride": 4, "levels": LEVELS, "iters": 8, "min_inliers": 50,
-                            "planar": False}
+                            "planar": False, "residual": "point", "normal_radius": 1.0, "normal_min_pts": 5, "normal_max_curv": 0.05}
 SCENE_DEFAULTS: Dict[str, Any] = {"min_range": 3.0, "max_range": 51.2}
 
 
@@ -59,17 +64,73 @@ def schedule(levels, iters) -> List[Tuple[float, int]]:
     return out
 
 
+def _normal_params(fn: str, names: Tuple[str, str, str], radius, min_pts, max_curv) -> Tuple[float, int, float]:
+    """df_normals' limits on (radius, min_pts, max_curv), under the names ``fn`` knows them by (the radius is held against the grid's
+    cell by _radius_fits, once the grid is known)"""
+    kr, km, kc = names
+    p = {kr: radius, km: min_pts, kc: max_curv}
+    positive(fn, p, kr)
+    integer(fn, p, km, 3, 2 ** 31 - 1)
+    positive(fn, p, kc)
+    if p[kc] > 1.0 / 3.0:
+        raise ValueError(f"{fn}: {kc} must lie in (0, 1/3], got {p[kc]!r}")
+    return p[kr], p[km], p[kc]
+
+
+def _radius_fits(fn: str, name: str, radius: float, cell: float) -> None:
+    if radius > cell:
+        raise ValueError(f"{fn}: {name} = {radius!r} is larger than the grid's cell = {cell!r}: the neighbours of a row are looked for in "
+                         "the 3 x 3 cells around its own only")
+
+
+def _filed_normals(grid: RowGrid, filed, N: int, radius: float, min_pts: int, max_curv: float, want_m: bool):
+    """df_normals on a cloud that ``grid.file`` filed -> (normals [B,N,4] f32, m [B,N] i32 or None)"""
+    out = torch.empty(grid.B, N, 4, dtype=torch.float32, device=grid.dev)
+    m = torch.empty(grid.B, N, dtype=torch.int32, device=grid.dev) if want_m else None
+    call("df_normals", ptr(filed[0]), ptr(filed[1]), grid.minx, grid.miny, grid.cell, grid.G, grid.B, N, radius, min_pts, max_curv,
+         ptr(out), ptr(m), stream())
+    return out, m
+
+
+def normals(points: torch.Tensor, count: torch.Tensor, *, mask: Optional[torch.Tensor] = None, xy_range: Sequence[float], cell: float,
+            radius: float, min_pts: int, max_curv: float):
+    """Surface normals of points [B,N,3] f32 with count [B] i32 valid leading rows and an optional integer / bool mask [B,N] (rows take
+    part as in ``register``): for every row the plane through the rows within ``radius`` (<= cell) of it, itself included.
+    -> (n [B,N,3] f32, curv [B,N] f32, m [B,N] i32): the unit normal pointing towards the frame's origin, lambda0 / (lambda0 + lambda1 +
+    lambda2) of the neighbourhood's covariance and the number of neighbours.  A row is VALID with m >= min_pts, a covariance that is not 0
+    and curv <= max_curv; every other row has n = 0, curv = -1 (and m = 0 where the row does not take part).  CUDA tensors only: there is
+    no CPU fallback.  Two launches after the grid build, no host synchronisation (include/deflow_amd.h)."""
+    B, N = cloud("normals", "points", points, rows_limit=1)
+    dev = points.device
+    tensor("normals", "count", count, torch.int32, (B,), dev, other="points")
+    radius, min_pts, max_curv = _normal_params("normals", ("radius", "min_pts", "max_curv"), radius, min_pts, max_curv)
+    try:
+        grid = RowGrid(B, xy_range, cell, dev)
+    except (TypeError, ValueError):
+        raise ValueError(f"normals: bad grid (xy_range {tuple(xy_range)}, cell {cell})") from None
+    _radius_fits("normals", "radius", radius, grid.cell)
+    lab = labels("normals", "mask", mask, (B, N), f"must be an integer or bool CUDA tensor of shape {(B, N)} on {dev}", dev)
+    out, m = _filed_normals(grid, grid.file(points.detach().contiguous(), count.contiguous(), lab), N, radius, min_pts, max_curv, True)
+    return out[..., :3], out[..., 3], m
+
+
 def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_d: torch.Tensor, *, init: Optional[torch.Tensor] = None,
              mask_s: Optional[torch.Tensor] = None, mask_d: Optional[torch.Tensor] = None, xy_range: Sequence[float] = DEFAULTS["xy_range"],
              cell: float = DEFAULTS["cell"], stride: int = DEFAULTS["stride"], levels=DEFAULTS["levels"], iters: int = DEFAULTS["iters"],
-             min_inliers: int = DEFAULTS["min_inliers"], planar: bool = DEFAULTS["planar"], rows: bool = False):
+             min_inliers: int = DEFAULTS["min_inliers"], planar: bool = DEFAULTS["planar"], rows: bool = False,
+             residual: str = DEFAULTS["residual"], normal_radius: float = DEFAULTS["normal_radius"],
+             normal_min_pts: int = DEFAULTS["normal_min_pts"], normal_max_curv: float = DEFAULTS["normal_max_curv"]):
     """src [B,Ns,3] f32 with count_s [B] i32 valid leading rows, dst [B,Nd,3] with count_d [B]; optional integer / bool masks [B,Ns], [B,Nd]
     (only rows with mask > 0 take part; non-finite rows never do).  init: [B,4,4] floating CUDA tensor, identity when None.
     -> (T [B,4,4] float64 with dst ~ R src + t, info).  info: ``status`` [B] i32 of the last iteration (0 updated, 2 fewer than min_inliers
     inliers, 3 singular: T was left alone in that iteration), ``log`` [B, total iterations + 1, 4] f32 = (inliers, weighted mean squared
     residual, |omega|, |v|) of every iteration and, last, of the final T; rows=True adds the final per-row ``q`` [B,Ns,3], ``idx`` [B,Ns],
     ``d2`` [B,Ns], ``w`` [B,Ns].  levels: gate distances, each run for ``iters`` iterations with kernel = distance / 3,
-    or (distance, iterations) pairs.  A fixed number of launches, no early stop, no host synchronisation."""
+    or (distance, iterations) pairs.  A fixed number of launches, no early stop, no host synchronisation.
+    residual="plane": the residual of a row is its distance to the plane of its nearest target row, n . (q - d), with the target's normals
+    estimated once (``normals`` with normal_radius <= cell, normal_min_pts, normal_max_curv); a row whose partner has no valid normal is
+    no inlier.  rows=True then adds ``e`` [B,Ns], and info has ``normals_valid`` [B] i64, the number of valid target normals.  The
+    normal_* parameters are not looked at with residual="point"."""
     if not isinstance(src, torch.Tensor) or not isinstance(dst, torch.Tensor) or src.dim() != 3 or dst.dim() != 3 or src.shape[2] != 3 or \
             dst.shape[2] != 3 or src.shape[0] != dst.shape[0]:
         raise ValueError("register: src [B,Ns,3] and dst [B,Nd,3] expected, got "
@@ -88,10 +149,18 @@ def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_
     if int(min_inliers) != min_inliers or int(min_inliers) < 0:
         raise ValueError(f"register: min_inliers must be an integer >= 0, got {min_inliers!r}")
     plan = schedule(levels, iters)
+    if residual not in RESIDUALS:
+        raise ValueError(f"register: residual must be 'point' or 'plane', got {residual!r}")
+    plane = residual == "plane"
+    if plane:
+        normal_radius, normal_min_pts, normal_max_curv = _normal_params(
+            "register", ("normal_radius", "normal_min_pts", "normal_max_curv"), normal_radius, normal_min_pts, normal_max_curv)
     try:
         grid = RowGrid(B, xy_range, cell, dev)
     except (TypeError, ValueError):
         raise ValueError(f"register: bad grid (xy_range {tuple(xy_range)}, cell {cell})") from None
+    if plane:
+        _radius_fits("register", "normal_radius", normal_radius, grid.cell)
     if init is None:
         T = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1)
     else:
@@ -116,7 +185,17 @@ def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_
     status = torch.full((B,), 2, dtype=torch.int32, device=dev)      # (no iteration at all: nothing was updated)
     s = stream()
 
-    def accumulate(max_dist, outs=(None, None, None, None)):
+    info: Dict[str, torch.Tensor] = {"status": status}
+    if plane:                                                          # the target is fixed over all iterations: its normals, once
+        nrm, _ = _filed_normals(grid, (d_rng, d_rows), Nd, normal_radius, normal_min_pts, normal_max_curv, False)
+        info["normals_valid"] = (nrm[..., 3] >= 0).sum(dim=1)
+    nouts = 5 if plane else 4
+
+    def accumulate(max_dist, outs=(None,) * nouts):
+        if plane:
+            call("df_reg_accumulate_plane", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), ptr(nrm), minx, miny, float(cell), G, B,
+                 Ns, Nd, int(stride), ptr(T), float(max_dist) ** 2, (float(max_dist) / 3.0) ** 2, ptr(partial), *(ptr(o) for o in outs), s)
+            return
         call("df_reg_accumulate", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), minx, miny, float(cell), G, B, Ns, int(stride), ptr(T),
              float(max_dist) ** 2, (float(max_dist) / 3.0) ** 2, ptr(partial), *(ptr(o) for o in outs), s)
 
@@ -126,12 +205,13 @@ def register(src: torch.Tensor, count_s: torch.Tensor, dst: torch.Tensor, count_
             accumulate(max_dist)
             call("df_reg_solve", ptr(partial), B, nblk, int(min_inliers), int(bool(planar)), ptr(T), ptr(log[it]), ptr(status), s)
             it += 1
-    info: Dict[str, torch.Tensor] = {"status": status}
-    outs = (None, None, None, None)
+    outs = (None,) * nouts
     if rows:
         outs = (torch.empty(B, Ns, 3, dtype=torch.float32, device=dev), torch.empty(B, Ns, dtype=torch.int32, device=dev),
                 torch.empty(B, Ns, dtype=torch.float32, device=dev), torch.empty(B, Ns, dtype=torch.float32, device=dev))
-        info.update(zip(("q", "idx", "d2", "w"), outs))
+        if plane:
+            outs += (torch.empty(B, Ns, dtype=torch.float32, device=dev),)
+        info.update(zip(("q", "idx", "d2", "w", "e"), outs))
     accumulate(plan[-1][0], outs)                                      # the final T's rows and log: nothing is solved
     call("df_reg_solve", ptr(partial), B, nblk, int(min_inliers), int(bool(planar)), None, ptr(log[total]), None, s)
     info["log"] = log.permute(1, 0, 2)
@@ -292,7 +372,8 @@ def sweep_pose(group, side: Optional[Dict[str, np.ndarray]], *, scene_id: str, t
 CLI_DEFAULTS: Dict[str, Any] = {"data_dir": None, "scenes": None, "overwrite": False, "ground_source": "auto", "init": "previous",
                                 **SCENE_DEFAULTS, **{k: (list(v) if isinstance(v, tuple) else v) for k, v in DEFAULTS.items()}}
 USAGE = ("usage: python -m deflow_amd.odometry data_dir=<dir> [scenes=a,b] [overwrite=false] [stride=4] [levels=2,1,0.5] [iters=8] "
-         "[planar=false] [min_inliers=50] [ground_source=auto|none] [init=previous|identity] [min_range=3] [max_range=51.2] [cell=1] "
+         "[planar=false] [min_inliers=50] [residual=point|plane] [normal_radius=1] [normal_min_pts=5] [normal_max_curv=0.05] "
+         "[ground_source=auto|none] [init=previous|identity] [min_range=3] [max_range=51.2] [cell=1] "
          "[xy_range=-51.2,-51.2,51.2,51.2]")
 
 
@@ -323,6 +404,10 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if v not in ("auto", "none"):
                     raise ValueError(v)
                 cfg[k] = v
+            elif k == "residual":
+                if v not in RESIDUALS:
+                    raise ValueError(v)
+                cfg[k] = v
             elif k == "init":
                 if v not in ("previous", "identity"):
                     raise ValueError(v)
@@ -332,14 +417,15 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if (k == "xy_range" and len(cfg[k]) != 4) or not cfg[k] or not all(math.isfinite(x) for x in cfg[k]) or \
                         (k == "levels" and not all(x > 0 for x in cfg[k])):
                     raise ValueError(v)
-            elif k in ("stride", "iters", "min_inliers"):
+            elif k in ("stride", "iters", "min_inliers", "normal_min_pts"):
                 cfg[k] = int(v)
-                lo, hi = {"stride": (1, 1024), "iters": (0, 1024), "min_inliers": (0, 2 ** 31 - 1)}[k]
+                lo, hi = {"stride": (1, 1024), "iters": (0, 1024), "min_inliers": (0, 2 ** 31 - 1), "normal_min_pts": (3, 2 ** 31 - 1)}[k]
                 if not lo <= cfg[k] <= hi:
                     raise ValueError(v)
             else:
                 cfg[k] = float(v)
-                if not math.isfinite(cfg[k]) or cfg[k] < 0 or (k == "cell" and cfg[k] == 0):
+                if not math.isfinite(cfg[k]) or cfg[k] < 0 or (k in ("cell", "normal_radius", "normal_max_curv") and cfg[k] == 0) or \
+                        (k == "normal_max_curv" and cfg[k] > 1.0 / 3.0):
                     raise ValueError(v)
         except ValueError:
             raise SystemExit(f"bad value for {k}: {v!r}")
@@ -347,6 +433,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         raise SystemExit(USAGE)
     if not cfg["min_range"] < cfg["max_range"]:
         raise SystemExit(f"bad value for min_range / max_range: {cfg['min_range']} .. {cfg['max_range']}")
+    if cfg["residual"] == "plane" and cfg["normal_radius"] > cfg["cell"]:
+        raise SystemExit(f"bad value for normal_radius / cell: the radius {cfg['normal_radius']} is larger than the cell {cfg['cell']}")
     return cfg
 
 

@@ -1205,7 +1205,43 @@ int df_refine_apply(const float* x, const float* flow, const int32_t* count, con
  * B outside 1..65535, Ns < 1, B Ns >= 2^30, Gs or G outside 1..4096, B G^2 >= 2^30, nblk < 1: DF_E_SHAPE.  NULL pointers, stride outside
  * [1, 1024], a max_dist2 / k2 / cell that is not positive and finite, minx / miny not finite, min_inliers < 0: DF_E_ARG.  src_sorted /
  * dst_sorted not 16-byte, partial / T not 8-byte aligned: DF_E_ALIGN.  No launch then.  No grid dimension comes from a device value; the
- * entries never allocate or synchronise and read nothing back. */
+ * entries never allocate or synchronise and read nothing back.
+ *
+ * POINT-TO-PLANE (UNPINNED like the rest).  A spinning sensor samples a wall or the ground at positions that move with it, so the nearest
+ * target row of a source row is "the same sample", and the point-to-point fit above is pulled towards zero motion.  The plane residual lets
+ * a row slide along the surface it lies on: one iteration = df_reg_accumulate_plane, then the SAME df_reg_solve; df_reg_ws_bytes and the
+ * slab's layout serve both residuals unchanged.  The target's normals come from df_normals, once per target.
+ *   normals      of a cloud filed by df_nn_grid_build (cell_rng, sorted), 0 < radius <= cell.  The NEIGHBOURS of a participating row p
+ *                are the participating rows v of its sample, p itself included, with d2 <= fp32(radius radius), d2 = df_chamfer_nn's
+ *                distance expression on the fp32 differences x = fp32(v - p): they lie in the 3 x 3 cells around p's own, clamped at the
+ *                grid's border -- three spans of `sorted`, walked in ascending position.  m = their number.  S1 = sum x [3] and
+ *                S2 = sum x x^T [6] are accumulated in float64 in that order; in float64 mean = S1 / m, C = S2 / m - mean mean^T.
+ *                Eigenvectors: cyclic Jacobi in float64, 8 sweeps of the rotations (0,1), (0,2), (1,2) (off-diagonal entries are at
+ *                rounding level after 5; a rotation whose off-diagonal entry is exactly 0 is skipped, so rows that share one z get the
+ *                axis (0, 0, +-1) exactly).  lambda0 <= lambda1 <= lambda2 (on equal smallest values the later axis), n = the unit
+ *                eigenvector of lambda0 rounded to fp32, curv = fp32(max(lambda0 / (lambda0 + lambda1 + lambda2), 0)).  Sign: n . p <= 0
+ *                (float64 products of the fp32 values added left to right), on n . p == 0 the first non-zero component is positive; a
+ *                zero component is +0.  VALID: m >= min_pts, lambda0 + lambda1 + lambda2 > 0 and curv <= max_curv.
+ *   plane terms  q, (d2, j) and the used rows exactly as above.  A used row is an INLIER when d2 <= max_dist2 AND the normal of target
+ *                row j is valid (its w >= 0).  n = that normal, r = fp32(q - dst[j]), e = n . r in fp32, the Geman-McClure weight acts
+ *                on the plane distance: w = fp32(u u), u = fp32(k2 / fp32(k2 + fp32(e e))) -- sliding along the surface is free, the
+ *                Euclidean gate stays on d2.  The row of the normal equations is a = (q x n, n) in fp32.
+ *   plane sums   per inlier, each formed in fp32 and accumulated in float64, in the order above; the slab's columns, unchanged:
+ *                  0..20  the upper triangle of H = sum w a a^T: fp32(fp32(w a_i) a_j), i <= j, row by row
+ *                  21..26 g = sum fp32(fp32(w a_i) e);  27 sum w;  28 sum fp32(fp32(w e) e);  29 the inliers;  30, 31: 0.
+ *                Every factor that comes from n changes sign with n and no other does, and no fma joins a term that changes sign with
+ *                one that does not: negating the fp32 normals negates a and e exactly and leaves the slab bit for bit.
+ * df_normals: cell_rng [B*G*G, 2] i32, sorted [B*N, 4] f32 and minx, miny, cell, G as df_nn_grid_build wrote and took them -> normals
+ *   [B,N,4] f32 indexed by ROW: (nx, ny, nz, curv) of a valid row, (0, 0, 0, -1) of every other row of [B,N] (padding, rows that do not
+ *   take part, rows that are not valid); m_out [B,N] i32: m, 0 for a row that does not take part.  Every element of both is written (a fill
+ *   launch on the same stream, then one thread per cell-ordered position, 256 per block, grid (ceil(N / 256), B)); no atomics.
+ * df_reg_accumulate_plane: df_reg_accumulate's arguments and, after dst_sorted, dst_normals [B*Nd, 4] f32 = df_normals' output for the
+ *   target, read at row j as one 16-byte load, and Nd after Ns (dst_sorted is [B*Nd, 4]).  -> partial as above.  The optional per-row
+ *   outputs as above, and e_out [B,Ns] f32; a row that is not used gets e = 0, and a used row that is gated out OR whose partner has no
+ *   valid normal gets its q and idx = -1, d2 = +inf, w = 0, e = 0.
+ * B outside 1..65535, N / Ns / Nd < 1, B N (B Ns, B Nd) >= 2^30, G / Gs outside 1..4096, B G^2 >= 2^30: DF_E_SHAPE.  NULL pointers (the
+ * nullable ones excepted), radius outside (0, cell], min_pts < 3, max_curv outside (0, 1/3], and df_reg_accumulate's other refusals:
+ * DF_E_ARG.  sorted / normals / dst_normals not 16-byte, m_out not 4-byte aligned: DF_E_ALIGN.  No launch then. */
 int64_t df_reg_ws_bytes(int B, int Ns);
 int df_reg_accumulate(const int32_t* src_rng, const float* src_sorted, int Gs, const int32_t* dst_rng, const float* dst_sorted, float minx,
                       float miny, float cell, int G, int B, int Ns, int stride, const double* T, float max_dist2, float k2, double* partial,
@@ -1213,6 +1249,13 @@ int df_reg_accumulate(const int32_t* src_rng, const float* src_sorted, int Gs, c
                       void* stream);
 int df_reg_solve(const double* partial, int B, int nblk, int min_inliers, int planar, double* T /*nullable*/, float* log,
                  int32_t* status /*nullable*/, void* stream);
+int df_normals(const int32_t* cell_rng, const float* sorted, float minx, float miny, float cell, int G, int B, int N, float radius,
+               int min_pts, float max_curv, float* normals, int32_t* m_out /*nullable*/, void* stream);
+int df_reg_accumulate_plane(const int32_t* src_rng, const float* src_sorted, int Gs, const int32_t* dst_rng, const float* dst_sorted,
+                            const float* dst_normals, float minx, float miny, float cell, int G, int B, int Ns, int Nd, int stride,
+                            const double* T, float max_dist2, float k2, double* partial, float* q_out /*nullable*/,
+                            int32_t* idx_out /*nullable*/, float* d2_out /*nullable*/, float* w_out /*nullable*/,
+                            float* e_out /*nullable*/, void* stream);
 
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every

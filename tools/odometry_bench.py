@@ -1,5 +1,5 @@
 """What the sweep-to-sweep registration costs on the GPU, measured: usage  python tools/odometry_bench.py [--batch 16] [--points 80000]
-[--grid 512] [--reps 20] [--out profiles/odometry_bench.json]
+[--grid 512] [--reps 20] [--out profiles/odometry_bench.json] [--plane-out profiles/odometry_plane_bench.json] [--parent-lib <libdeflow_amd.so>]
 
 At the configs[2] cloud (80 000 rows per cloud, 512 x 512; ~70 000 rows in range: the compact pc0 / pc1 of a real forward, the clouds
 tools/cluster_bench.py times), for B = 1 and B = --batch and stride 4 and 1, with device events after a warm-up (medians of --reps calls):
@@ -10,8 +10,18 @@ tools/cluster_bench.py times), for B = 1 and B = --batch and stride 4 and 1, wit
   * one df_reg_solve;
   * a whole default ``odometry.register`` (two grid builds, 24 accumulate + solve pairs, the final accumulate).
 
+The point-to-plane rows go to a file of their own (--plane-out; the rows and keys above stay as they are), same clouds, same method:
+
+  * one df_normals of pc1 at the default radius, next to ITS yardstick, a DBSCAN core pass (df_dbscan_core, the entry
+    tools/cluster_bench.py times) on the same filed cloud at eps = radius -- the same 3 x 3 walk, once stopping at min_pts rows as the
+    clustering does and once walking every row of the window;
+  * one df_reg_accumulate_plane, next to df_reg_accumulate of this library and, with --parent-lib, of the PARENT commit's library loaded
+    beside it in the same process (the ratio is reported, not fixed in advance);
+  * a whole default ``odometry.register`` with residual="point" and residual="plane".
+
 A measuring tool, not a bench.py leg; needs the GPU (no fallback)."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -21,6 +31,7 @@ import torch
 
 import deflow_amd
 from deflow_amd import chamfer, odometry
+from deflow_amd import _lib as dflib
 from deflow_amd._lib import call, ptr, stream
 from deflow_amd.synth import synth_batch
 
@@ -48,7 +59,14 @@ def main():
     ap.add_argument("--grid", type=int, default=512)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "odometry_bench.json"))
+    ap.add_argument("--plane-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                        "odometry_plane_bench.json"))
+    ap.add_argument("--parent-lib", default=None, help="the parent commit's libdeflow_amd.so: its df_reg_accumulate is the yardstick")
     a = ap.parse_args()
+    parent_acc = None
+    if a.parent_lib:
+        parent_acc = ctypes.CDLL(os.path.abspath(a.parent_lib)).df_reg_accumulate
+        parent_acc.argtypes, parent_acc.restype = dflib._SIGS["df_reg_accumulate"], ctypes.c_int
     assert torch.cuda.is_available(), "tools/odometry_bench.py measures on the GPU"
     dev = torch.device("cuda")
     H = a.grid
@@ -65,6 +83,10 @@ def main():
     cell, max_dist = odometry.DEFAULTS["cell"], odometry.LEVELS[0]
     report = {"device": torch.cuda.get_device_name(0), "cell_m": cell, "max_dist_m": max_dist, "levels": list(odometry.LEVELS),
               "iters": odometry.DEFAULTS["iters"], "reps": a.reps, "cases": []}
+    radius, min_pts, max_curv = (odometry.DEFAULTS[k] for k in ("normal_radius", "normal_min_pts", "normal_max_curv"))
+    plane_report = {"device": report["device"], "cell_m": cell, "max_dist_m": max_dist, "levels": list(odometry.LEVELS),
+                    "iters": odometry.DEFAULTS["iters"], "reps": a.reps, "normal_radius_m": radius, "normal_min_pts": min_pts,
+                    "normal_max_curv": max_curv, "parent_lib": bool(parent_acc), "cases": []}
     for B in sorted({1, a.batch}):
         pc0, pc1, c0, c1 = all0[:B].contiguous(), all1[:B].contiguous(), cnt0[:B].contiguous(), cnt1[:B].contiguous()
         Ns, Nd = pc0.shape[1], pc1.shape[1]
@@ -90,10 +112,50 @@ def main():
                     "status": info["status"].tolist()[:4], "final_log_sample0": info["log"][0, -1].tolist()}
             report["cases"].append(case)
             print(json.dumps(case), flush=True)
+        # ---- point-to-plane --------------------------------------------------------------------------------------------------------
+        nrm = torch.empty(B, Nd, 4, dtype=torch.float32, device=dev)
+        normals = lambda: call("df_normals", ptr(d_rng), ptr(d_rows), minx, miny, cell, G, B, Nd, radius, min_pts, max_curv, ptr(nrm), None,
+                               stream())
+        t_normals = timed(normals, a.reps)
+        ws = torch.empty(call("df_dbscan_ws_bytes", B, Nd), dtype=torch.uint8, device=dev)
+        core = lambda k: call("df_dbscan_core", ptr(d_rng), ptr(d_rows), B, Nd, minx, miny, cell, G, radius, k, ptr(ws), stream())
+        t_core, t_core_all = timed(lambda: core(min_pts), a.reps), timed(lambda: core(2 ** 30), a.reps)
+        normals()
+        valid = (nrm[..., 3] >= 0).sum(dim=1)
+        for stride in (4, 1):
+            acc_args = (ptr(T), max_dist ** 2, (max_dist / 3) ** 2, ptr(partial), None, None, None, None)
+            t_point = timed(lambda: call("df_reg_accumulate", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), minx, miny, cell, G, B,
+                                         Ns, stride, *acc_args, stream()), a.reps)
+            t_plane = timed(lambda: call("df_reg_accumulate_plane", ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), ptr(nrm), minx, miny,
+                                         cell, G, B, Ns, Nd, stride, *acc_args, None, stream()), a.reps)
+            call("df_reg_solve", ptr(partial), B, nblk, 50, 0, None, ptr(log), None, stream())
+            inl = log[:4, 0].tolist()
+            t_parent = None
+            if parent_acc is not None:
+                t_parent = timed(lambda: parent_acc(ptr(s_rng), ptr(s_rows), G, ptr(d_rng), ptr(d_rows), minx, miny, cell, G, B, Ns, stride,
+                                                    *acc_args, stream()), a.reps)
+            t_reg = {r: timed(lambda: odometry.register(pc0, c0, pc1, c1, xy_range=grid_range, stride=stride, residual=r), a.reps)
+                     for r in odometry.RESIDUALS}
+            _, info = odometry.register(pc0, c0, pc1, c1, xy_range=grid_range, stride=stride, residual="plane")
+            case = {"batch": B, "rows": Ns, "valid_rows": c0.tolist()[:4], "stride": stride, "normals_ms": round(t_normals, 4),
+                    "dbscan_core_eps_radius_ms": round(t_core, 4), "dbscan_core_whole_window_ms": round(t_core_all, 4),
+                    "normals_over_core_whole_window": round(t_normals / t_core_all, 3), "normals_valid": valid.tolist()[:4],
+                    "reg_accumulate_ms": round(t_point, 4), "reg_accumulate_plane_ms": round(t_plane, 4),
+                    "plane_over_point": round(t_plane / t_point, 3),
+                    "parent_reg_accumulate_ms": None if t_parent is None else round(t_parent, 4),
+                    "plane_over_parent_point": None if t_parent is None else round(t_plane / t_parent, 3),
+                    "register_point_ms": round(t_reg["point"], 3), "register_plane_ms": round(t_reg["plane"], 3),
+                    "plane_inliers_at_identity": inl, "status": info["status"].tolist()[:4],
+                    "final_log_sample0": info["log"][0, -1].tolist()}
+            plane_report["cases"].append(case)
+            print(json.dumps(case), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(report, f, indent=1)
     print("wrote", a.out)
+    with open(a.plane_out, "w") as f:
+        json.dump(plane_report, f, indent=1)
+    print("wrote", a.plane_out)
 
 
 if __name__ == "__main__":
