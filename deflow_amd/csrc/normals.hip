@@ -2,12 +2,17 @@
 // (register.hip: df_reg_accumulate_plane) reads at the matched target row.  UNPINNED -- the definition is this project's own:
 // include/deflow_amd.h, DESIGN.md section 6r.
 //
-//   df_normals   one thread per cell-ordered position.  radius <= cell, so the rows within radius of a row lie in the 3 x 3 cells around
-//                its own (clamped at the border as nn_search.h clamps: rows outside the range sit in the border cells, and clamping is a
-//                contraction) -- three contiguous spans of the cell-ordered rows, walked in ascending position.  The differences from
-//                the row itself are formed in fp32 (the distance expression is nn_ring_search's), their 3 first and 6 second moments
-//                are accumulated in float64, and the covariance's eigenvectors come from NRM_SWEEPS sweeps of cyclic Jacobi in
-//                float64.  A fill launch writes the default (0, 0, 0, -1) / m = 0 to every row first.  No atomics, no LDS.
+//   df_normals   one thread per cell-ordered position.  The rows within radius of a row lie in the cells that its clamped position
+//                +- reach covers in x and in y, reach = radius / cell + nn_ring_search's 2e-3 cell of slack for the fp32 rounding of
+//                the cell coordinates (clamped at the border as nn_search.h clamps: rows outside the range sit in the border cells,
+//                and clamping is a contraction).  NOT "the 3 x 3 cells around its own": (v - lo) * inv_cell rounds differently on the
+//                two sides of a binade edge, so at radius == cell two rows a hair less than one cell apart can be filed two cells
+//                apart.  With radius <= cell that is three cell rows, four for a row within the slack of a cell edge (and likewise
+//                three or four cells per row) -- one contiguous span of the cell-ordered rows per cell row, walked in ascending
+//                position.  The differences from the row itself are formed in fp32 (the distance expression is nn_ring_search's),
+//                their 3 first and 6 second moments are accumulated in float64, and the covariance's eigenvectors come from
+//                NRM_SWEEPS sweeps of cyclic Jacobi in float64.  A fill launch writes the default (0, 0, 0, -1) / m = 0 to every row
+//                first.  No atomics, no LDS.
 //
 // NRM_SWEEPS = 8.  A sweep is the three rotations (0,1), (0,2), (1,2).  Cyclic Jacobi converges quadratically once the off-diagonal
 // norm is below the eigenvalue gap, and a 3 x 3 matrix gets there within two or three sweeps from any start: in float64 the
@@ -56,7 +61,7 @@ __device__ __forceinline__ void nrm_rotate(double (&A)[3][3], double (&V)[3][3])
 }
 
 __global__ __launch_bounds__(256) void normals_kernel(const int32_t* __restrict__ cell_rng, const f32x4* __restrict__ sorted, int N,
-                                                      float minx, float miny, float inv_cell, int G, float r2, int min_pts,
+                                                      float minx, float miny, float inv_cell, int G, float r2, float reach, int min_pts,
                                                       float max_curv, f32x4* __restrict__ normals, int32_t* __restrict__ m_out) {
   const int b = blockIdx.y;
   const int32_t* rng = cell_rng + (int64_t)b * G * G * 2;
@@ -73,13 +78,21 @@ __global__ __launch_bounds__(256) void normals_kernel(const int32_t* __restrict_
   const int row = __builtin_bit_cast(int, mw);
   if ((unsigned)row >= (unsigned)N) return;
   float px, py;
-  const int cx = nn_cell(me.x, minx, inv_cell, G, &px), cy = nn_cell(me.y, miny, inv_cell, G, &py);
-  const int xa = cx > 0 ? cx - 1 : 0, xb = cx < G - 1 ? cx + 1 : G - 1;
+  nn_cell(me.x, minx, inv_cell, G, &px);
+  const int cy = nn_cell(me.y, miny, inv_cell, G, &py);
+  // the cells that the clamped position +- reach covers (positions lie in [0, G]: every conversion to int is in range)
+  const int top = G - 1;
+  const int xa = min((int)fmaxf(px - reach, 0.f), top), xb = min((int)fminf(px + reach, (float)G), top);
+  const int ya = min((int)fmaxf(py - reach, 0.f), top), yb = min((int)fminf(py + reach, (float)G), top);
   int m = 0;
   double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
-  for (int k = 0; k < 3; ++k) {                            // ascending cell row = ascending position
-    const int y = cy - 1 + k;
-    if (y < 0 || y > G - 1) continue;
+  // ya >= cy - 2 and yb <= cy + 2.  The cell rows are walked at a FIXED offset from the row's own, not from ya: the lanes of a wave that
+  // share a cell then walk the same cell row in the same iteration, whichever of them has a fourth one (one lane of a crowded cell
+  // that started a row early made its whole wave walk the crowd twice: 1.5 x the launch time at 640 rows in a cell)
+#pragma unroll
+  for (int k = -2; k <= 2; ++k) {                          // ascending cell row = ascending position
+    const int y = cy + k;
+    if (y < ya || y > yb) continue;
     const int32_t* rr = rng + (int64_t)y * G * 2;
     int64_t s = rr[2 * xa], e = rr[2 * xb + 1];
     if (s < s0) s = s0;
@@ -157,10 +170,12 @@ extern "C" int df_normals(const int32_t* cell_rng, const float* sorted, float mi
   DF_REQUIRE(df_aligned16(sorted) && df_aligned16(normals) && ((uintptr_t)m_out & 3u) == 0, DF_E_ALIGN);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)B * N;
+  const float inv_cell = 1.0f / cell;
   hipLaunchKernelGGL(normals_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, reinterpret_cast<f32x4*>(normals), m_out);
   DF_CHECK_LAUNCH();
   hipLaunchKernelGGL(normals_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, cell_rng, reinterpret_cast<const f32x4*>(sorted), N, minx,
-                     miny, 1.0f / cell, G, radius * radius, min_pts, max_curv, reinterpret_cast<f32x4*>(normals), m_out);
+                     miny, inv_cell, G, radius * radius, radius * inv_cell + 2e-3f, min_pts, max_curv, reinterpret_cast<f32x4*>(normals),
+                     m_out);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }

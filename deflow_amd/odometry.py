@@ -80,7 +80,7 @@ def _normal_params(fn: str, names: Tuple[str, str, str], radius, min_pts, max_cu
 def _radius_fits(fn: str, name: str, radius: float, cell: float) -> None:
     if radius > cell:
         raise ValueError(f"{fn}: {name} = {radius!r} is larger than the grid's cell = {cell!r}: the neighbours of a row are looked for in "
-                         "the 3 x 3 cells around its own only")
+                         "the cells within one cell of its position only")
 
 
 def _filed_normals(grid: RowGrid, filed, N: int, radius: float, min_pts: int, max_curv: float, want_m: bool):

@@ -1213,9 +1213,14 @@ int df_refine_apply(const float* x, const float* flow, const int32_t* count, con
  * slab's layout serve both residuals unchanged.  The target's normals come from df_normals, once per target.
  *   normals      of a cloud filed by df_nn_grid_build (cell_rng, sorted), 0 < radius <= cell.  The NEIGHBOURS of a participating row p
  *                are the participating rows v of its sample, p itself included, with d2 <= fp32(radius radius), d2 = df_chamfer_nn's
- *                distance expression on the fp32 differences x = fp32(v - p): they lie in the 3 x 3 cells around p's own, clamped at the
- *                grid's border -- three spans of `sorted`, walked in ascending position.  m = their number.  S1 = sum x [3] and
- *                S2 = sum x x^T [6] are accumulated in float64 in that order; in float64 mean = S1 / m, C = S2 / m - mean mean^T.
+ *                distance expression on the fp32 differences x = fp32(v - p).  ALL of them: the entry scans the cells that p's clamped
+ *                position, in cell units as df_nn_grid_build computes it, +- (radius / cell + 2e-3) covers in x and in y (the 2e-3 cell
+ *                is df_chamfer_nn's slack for the fp32 rounding of the cell coordinates; NOT "the 3 x 3 cells around p's own": at
+ *                radius == cell, fp32 files two rows a hair less than one cell apart two cells apart where the cell coordinate
+ *                crosses a power of two) -- one span of `sorted` per cell row, three or four of them, walked in ascending position;
+ *                a row farther than radius adds nothing, so the scanned span never shows in the result.  m = their number.
+ *                S1 = sum x [3] and S2 = sum x x^T [6] are accumulated in float64 in that order; in float64 mean = S1 / m,
+ *                C = S2 / m - mean mean^T.
  *                Eigenvectors: cyclic Jacobi in float64, 8 sweeps of the rotations (0,1), (0,2), (1,2) (off-diagonal entries are at
  *                rounding level after 5; a rotation whose off-diagonal entry is exactly 0 is skipped, so rows that share one z get the
  *                axis (0, 0, +-1) exactly).  lambda0 <= lambda1 <= lambda2 (on equal smallest values the later axis), n = the unit

@@ -34,34 +34,65 @@ def pair_margin(points, ok, radius) -> float:
     return float(np.abs(d - radius).min())
 
 
-def normals(points, count, mask=None, *, radius, min_pts, max_curv):
+def eig_sym3(C, later_axis=True):
+    """ascending eigenvalues and unit eigenvectors (columns) of the symmetric C [3,3].  An axis whose off-diagonal entries are exactly 0
+    is an exact eigenvector with its diagonal entry (the header: a rotation whose off-diagonal entry is exactly 0 is skipped), the rest
+    comes from numpy.linalg.eigh of what is left.  On exactly equal eigenvalues the later axis comes first, as the header orders them
+    (later_axis=False: the earlier one -- a deliberately wrong variant)."""
+    free = [k for k in range(3) if all(C[k, j] == 0 for j in range(3) if j != k)]
+    if len(free) == 3 or len(free) == 1:
+        rest = [k for k in range(3) if k not in free] if len(free) == 1 else []
+        lam, vec, axis = [C[k, k] for k in free], [np.eye(3)[k] for k in free], list(free)
+        if rest:
+            l2, v2 = np.linalg.eigh(C[np.ix_(rest, rest)])
+            for c in range(2):
+                v = np.zeros(3)
+                v[rest] = v2[:, c]
+                lam.append(l2[c]), vec.append(v), axis.append(-1)
+        order = sorted(range(3), key=lambda c: (lam[c], -axis[c] if later_axis else axis[c]))
+        return np.array([lam[c] for c in order]), np.stack([vec[c] for c in order], axis=1)
+    return np.linalg.eigh(C)
+
+
+def normals(points, count, mask=None, *, radius, min_pts, max_curv, diff32=False, near=None, later_axis=True, tie_break=True):
     """-> dict: n [N,3] f64 (0 where not valid), curv [N] (-1 where not valid), m [N] int, valid [N] bool, lam [N,3] the ascending
-    eigenvalues and curv_all [N] = lambda0 / trace of every row with m >= 1 and trace > 0 (nan elsewhere), whatever its validity"""
+    eigenvalues, curv_all [N] = lambda0 / trace of every row with m >= 1 and trace > 0 (nan elsewhere), whatever its validity, and
+    cov [N,3,3] the covariances.  The differences from the row are exact (float64) or, with diff32, fp32(v - p) as the header forms
+    them.  curv <= max_curv is decided on the fp32 values, as the header states it.  near: a neighbour matrix to use instead of the
+    all-pairs one (rows that do not take part must be False in it); later_axis / tie_break = False: deliberately wrong variants of the
+    header's rules, for the tests that show a case bites (without the tie-break the raw eigenvector is taken with its largest component
+    negative, which a solver is free to return, and only n . p > 0 flips it)."""
     p = np.asarray(points, dtype=np.float64)
+    p32 = np.asarray(points, dtype=np.float32)
     N = p.shape[0]
     ok = reg_ref.participating(points, count, mask)
-    near = neighbours(np.where(ok[:, None], p, 0.0), ok, radius)
+    if near is None:
+        near = neighbours(np.where(ok[:, None], p, 0.0), ok, radius)
     out = dict(n=np.zeros((N, 3)), curv=np.full(N, -1.0), m=near.sum(axis=1).astype(np.int64), valid=np.zeros(N, dtype=bool),
-               lam=np.full((N, 3), np.nan), curv_all=np.full(N, np.nan))
+               lam=np.full((N, 3), np.nan), curv_all=np.full(N, np.nan), cov=np.full((N, 3, 3), np.nan))
     for i in np.flatnonzero(ok):
-        x = p[near[i]] - p[i]
+        x = (p32[near[i]] - p32[i]).astype(np.float64) if diff32 else p[near[i]] - p[i]
+        if x.shape[0] == 0:
+            continue
         mean = x.mean(axis=0)
         C = x.T @ x / x.shape[0] - np.outer(mean, mean)
-        lam, vec = np.linalg.eigh(C)
-        out["lam"][i] = lam
+        lam, vec = eig_sym3(C, later_axis)
+        out["lam"][i], out["cov"][i] = lam, C
         trace = lam.sum()
         if not trace > 0:
             continue
         curv = max(lam[0] / trace, 0.0)
         out["curv_all"][i] = curv
-        if out["m"][i] < min_pts or not curv <= max_curv:
+        if out["m"][i] < min_pts or not np.float32(curv) <= np.float32(max_curv):
             continue
         n = vec[:, 0]
+        if not tie_break and n[np.argmax(np.abs(n))] > 0:
+            n = -n
         dot = float(n @ p[i])
         lead = n[np.flatnonzero(n != 0)[0]]
-        if dot > 0 or (dot == 0 and lead < 0):
+        if dot > 0 or (tie_break and dot == 0 and lead < 0):
             n = -n
-        out["n"][i], out["curv"][i], out["valid"][i] = n, curv, True
+        out["n"][i], out["curv"][i], out["valid"][i] = n + 0.0, curv, True          # (+ 0.0: a negated zero component is +0)
     return out
 
 
