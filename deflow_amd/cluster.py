@@ -21,9 +21,11 @@ from ._lib import call, ptr, stream
 from .args import tensor, workspace
 from .chamfer import GRID_RANGE, RowGrid
 
-# cell = max(CELL_SLACK * eps, extent / 4096): with cell >= eps the 3 x 3 cells around a row hold every row within eps.  The slack covers
-# the rounding of the cell coordinates (< 1e-3 cell at G <= 4096, the bound csrc/chamfer.hip's search uses): two rows eps apart in x never
-# land two cells apart.  The range and the cell only decide the speed, never the result.
+# cell = max(CELL_SLACK * eps, extent / 4096).  The kernels are right at any cell >= eps: they scan the cells that a row's clamped position
+# +- (eps / cell + 2e-3) covers (csrc/nn_search.h: nn_window), so two rows within eps that fp32 files two cells apart still meet.  The
+# slack decides the SPEED only: with it eps / cell + 2e-3 < 1 and that window is the 3 x 3 cells around the row for every row, while at
+# cell == eps a row within 2e-3 cell of a cell edge scans a fourth cell (row) and its wave waits for it (core pass + 10.6 %, finish + 5.9 % measured,
+# DESIGN.md section 6b).  The range and the cell never change the result.
 CELL_SLACK = 1.0025
 
 

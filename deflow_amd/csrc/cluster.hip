@@ -1,8 +1,11 @@
 // DBSCAN over a padded batch of clouds: the cluster labels of the self-supervised (SeFlow) mode computed on the GPU.  UNPINNED -- upstream
 // clusters offline on the CPU with HDBSCAN (absent submodule); this is plain DBSCAN with every choice fixed (include/deflow_amd.h,
 // DESIGN.md section 6b), so that the labels are a pure function of the input.  All three stages walk the grid of df_nn_grid_build
-// (chamfer.hip) with cell >= eps: the 3 x 3 cells around a row -- three contiguous spans of the cell-ordered rows -- hold every row
-// within eps; rows outside the range sit in the clamped border cells and still meet all their neighbours (clamping is a contraction).
+// (chamfer.hip) with cell >= eps: the cells that a row's clamped position +- (eps / cell + 2e-3) covers in x and in y (nn_search.h:
+// nn_window) -- one contiguous span of the cell-ordered rows per cell row, three of them, four for a row within the slack of a cell
+// edge -- hold every row within eps.  NOT "the 3 x 3 cells around its own": at cell == eps fp32 files two rows a hair less than one
+// cell apart two cells apart where the cell coordinate crosses a power of two.  Rows outside the range sit in the clamped border
+// cells and still meet all their neighbours (clamping is a contraction).
 //
 //   df_dbscan_core     one thread per cell-ordered row: counts the rows within eps (stops at min_points) and writes the row again with the
 //                      core flag in the top bit of its index word, so that the later passes read one 16-byte record per candidate
@@ -19,17 +22,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "nn_search.h"
 
 namespace {
 
 constexpr uint32_t CL_CORE = 0x80000000u;     // top bit of a record's index word (row indices stay below 2^30)
-
-// identical arithmetic to nn_search.h's nn_cell (the cell the grid build filed the row under)
-__device__ __forceinline__ int cl_cell(float v, float lo, float inv_cell, int G) {
-  const float f = fminf(fmaxf((v - lo) * inv_cell, 0.f), (float)G);
-  const int c = (int)f;
-  return c > G - 1 ? G - 1 : c;
-}
+constexpr int CL_ROWS = 5;                    // cell rows at the offsets -2 .. 2 from a row's own: the window covers three or four
 
 __device__ __forceinline__ uint32_t cl_bits(const f32x4& v) {
   const float w = v.w;
@@ -41,22 +39,26 @@ __device__ __forceinline__ float cl_d2(const f32x4& v, float x, float y, float z
   return dx * dx + dy * dy + dz * dz;
 }
 
-// the window of a row: for each of the (up to) three cell rows around (cx, cy) one span [s, e) of cell-ordered positions, clipped to the
-// sample's own positions [s0, e0)
+// the window of the row (x, y): for each of the cell rows at the FIXED offsets -2 .. 2 from its own one span [s, e) of cell-ordered
+// positions, clipped to the sample's own positions [s0, e0); empty for a cell row outside nn_window's ya .. yb (nn_search.h)
 struct ClWindow {
-  int s[3], e[3];
+  int s[CL_ROWS], e[CL_ROWS];
 };
-__device__ __forceinline__ ClWindow cl_window(const int32_t* __restrict__ rng, int G, int cx, int cy, int s0, int e0) {
+__device__ __forceinline__ ClWindow cl_window(const int32_t* __restrict__ rng, int G, float x, float y, float minx, float miny,
+                                              float inv_cell, float reach, int s0, int e0) {
   ClWindow w;
-  const int xa = cx > 0 ? cx - 1 : 0, xb = cx < G - 1 ? cx + 1 : G - 1;
+  float px, py;
+  nn_cell(x, minx, inv_cell, G, &px);
+  const int cy = nn_cell(y, miny, inv_cell, G, &py);
+  const NnWindow win = nn_window(px, py, reach, G);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int y = cy - 1 + k;
+  for (int k = 0; k < CL_ROWS; ++k) {
+    const int yy = cy - 2 + k;
     int s = 0, e = 0;
-    if (y >= 0 && y < G) {
-      const int32_t* rr = rng + (int64_t)y * G * 2;
-      s = max(rr[2 * xa], s0);
-      e = min(rr[2 * xb + 1], e0);
+    if (yy >= win.ya && yy <= win.yb) {
+      const int32_t* rr = rng + (int64_t)yy * G * 2;
+      s = max(rr[2 * win.xa], s0);
+      e = min(rr[2 * win.xb + 1], e0);
     }
     w.s[k] = s;
     w.e[k] = e;
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void cl_init_kernel(int N, int32_t* __restrict
 }
 
 __global__ __launch_bounds__(256) void cl_core_kernel(const int32_t* __restrict__ cell_rng, const f32x4* __restrict__ sorted, int N,
-                                                      float minx, float miny, float inv_cell, int G, float eps2, int min_points,
+                                                      float minx, float miny, float inv_cell, int G, float eps2, float reach, int min_points,
                                                       f32x4* __restrict__ rec) {
   const int b = blockIdx.y;
   const int32_t* rng = cell_rng + (int64_t)b * G * G * 2;
@@ -94,10 +96,10 @@ __global__ __launch_bounds__(256) void cl_core_kernel(const int32_t* __restrict_
   const int p = s0 + blockIdx.x * 256 + threadIdx.x;
   if (p >= e0) return;
   f32x4 me = sorted[p];
-  const ClWindow w = cl_window(rng, G, cl_cell(me.x, minx, inv_cell, G), cl_cell(me.y, miny, inv_cell, G), s0, e0);
+  const ClWindow w = cl_window(rng, G, me.x, me.y, minx, miny, inv_cell, reach, s0, e0);
   int cnt = 0;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < CL_ROWS; ++k) {
     for (int q = w.s[k]; q < w.e[k] && cnt < min_points; ++q) cnt += cl_d2(sorted[q], me.x, me.y, me.z) <= eps2 ? 1 : 0;
   }
   const uint32_t word = (cl_bits(me) & ~CL_CORE) | (cnt >= min_points ? CL_CORE : 0u);
@@ -149,7 +151,7 @@ __device__ __forceinline__ int cl_unite(int32_t* __restrict__ par, int a, int b,
 }
 
 __global__ __launch_bounds__(256) void cl_link_kernel(const int32_t* __restrict__ cell_rng, const f32x4* __restrict__ rec, int N,
-                                                      float minx, float miny, float inv_cell, int G, float eps2,
+                                                      float minx, float miny, float inv_cell, int G, float eps2, float reach,
                                                       int32_t* __restrict__ parent, int32_t* __restrict__ status) {
   const int b = blockIdx.y;
   const int32_t* rng = cell_rng + (int64_t)b * G * G * 2;
@@ -163,10 +165,10 @@ __global__ __launch_bounds__(256) void cl_link_kernel(const int32_t* __restrict_
   const int row = (int)(mw & ~CL_CORE);
   if (row >= N) return;
   int32_t* par = parent + (int64_t)b * N;
-  const ClWindow w = cl_window(rng, G, cl_cell(me.x, minx, inv_cell, G), cl_cell(me.y, miny, inv_cell, G), s0, e0);
+  const ClWindow w = cl_window(rng, G, me.x, me.y, minx, miny, inv_cell, reach, s0, e0);
   int ra = row;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < CL_ROWS; ++k) {
     for (int q = w.s[k]; q < w.e[k]; ++q) {
       const f32x4 v = rec[q];
       const uint32_t vw = cl_bits(v);
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(256) void cl_link_kernel(const int32_t* __restrict_
 
 __global__ __launch_bounds__(256) void cl_attach_kernel(const int32_t* __restrict__ cell_rng, const f32x4* __restrict__ rec,
                                                         const int32_t* __restrict__ dynamic, int N, float minx, float miny,
-                                                        float inv_cell, int G, float eps2, const int32_t* __restrict__ parent,
+                                                        float inv_cell, int G, float eps2, float reach, const int32_t* __restrict__ parent,
                                                         int32_t* __restrict__ root, int32_t* __restrict__ members,
                                                         int32_t* __restrict__ flagged, int32_t* __restrict__ status) {
   const int b = blockIdx.y;
@@ -196,10 +198,10 @@ __global__ __launch_bounds__(256) void cl_attach_kernel(const int32_t* __restric
   if (mw & CL_CORE) {
     target = row;
   } else {
-    const ClWindow w = cl_window(rng, G, cl_cell(me.x, minx, inv_cell, G), cl_cell(me.y, miny, inv_cell, G), s0, e0);
+    const ClWindow w = cl_window(rng, G, me.x, me.y, minx, miny, inv_cell, reach, s0, e0);
     float best = INFINITY;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < CL_ROWS; ++k) {
       for (int q = w.s[k]; q < w.e[k]; ++q) {
         const f32x4 v = rec[q];
         const uint32_t vw = cl_bits(v);
@@ -282,6 +284,9 @@ inline bool cl_geom_ok(float minx, float miny, float cell, float eps) {
   return isfinite(minx) && isfinite(miny) && isfinite(cell) && isfinite(eps) && eps > 0.f && cell >= eps;
 }
 
+// nn_window's reach: eps in cells plus the slack for the fp32 rounding of the cell coordinates (<= 1.002 with cell >= eps)
+inline float cl_reach(float eps, float cell) { return eps * (1.0f / cell) + 2e-3f; }
+
 // the workspace the three stages share
 struct ClWs {
   f32x4* rec;
@@ -323,7 +328,7 @@ extern "C" int df_dbscan_core(const int32_t* cell_rng, const float* sorted, int 
   hipLaunchKernelGGL(cl_init_kernel, grid, dim3(256), 0, s, N, w.parent, w.root, w.members, w.flagged);
   DF_CHECK_LAUNCH();
   hipLaunchKernelGGL(cl_core_kernel, grid, dim3(256), 0, s, cell_rng, reinterpret_cast<const f32x4*>(sorted), N, minx, miny, 1.0f / cell,
-                     G, eps * eps, min_points, w.rec);
+                     G, eps * eps, cl_reach(eps, cell), min_points, w.rec);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }
@@ -337,7 +342,7 @@ extern "C" int df_dbscan_link(const int32_t* cell_rng, int B, int N, float minx,
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const ClWs w = cl_ws(ws, B, N);
   hipLaunchKernelGGL(cl_link_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, cell_rng, w.rec, N, minx, miny, 1.0f / cell, G, eps * eps,
-                     w.parent, status);
+                     cl_reach(eps, cell), w.parent, status);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }
@@ -352,8 +357,8 @@ extern "C" int df_dbscan_finish(const int32_t* cell_rng, const int32_t* dynamic,
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const ClWs w = cl_ws(ws, B, N);
   const dim3 grid((N + 255) / 256, B);
-  hipLaunchKernelGGL(cl_attach_kernel, grid, dim3(256), 0, s, cell_rng, w.rec, dynamic, N, minx, miny, 1.0f / cell, G, eps * eps, w.parent,
-                     w.root, w.members, w.flagged, status);
+  hipLaunchKernelGGL(cl_attach_kernel, grid, dim3(256), 0, s, cell_rng, w.rec, dynamic, N, minx, miny, 1.0f / cell, G, eps * eps,
+                     cl_reach(eps, cell), w.parent, w.root, w.members, w.flagged, status);
   DF_CHECK_LAUNCH();
   hipLaunchKernelGGL(cl_filter_kernel, grid, dim3(256), 0, s, N, w.members, w.flagged, dynamic ? 1 : 0, min_cluster_size, min_dynamic_frac,
                      w.keep, w.blk_sum);

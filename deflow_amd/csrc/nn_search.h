@@ -1,6 +1,7 @@
 // The grid search of df_chamfer_nn as a device function, shared by chamfer.hip (df_chamfer_nn) and register.hip (df_reg_accumulate): the
 // cell arithmetic of df_nn_grid_build's grid and the ring walk over it.  ONE body, so that the two entries agree bit for bit on the
-// distance expression, the tie rule and the stopping rule.
+// distance expression, the tie rule and the stopping rule.  Also the window of the fixed-radius scans over the same grid (nn_window:
+// normals.hip, cluster.hip).
 #pragma once
 #include <math.h>
 
@@ -16,6 +17,30 @@ __device__ __forceinline__ int nn_cell(float v, float lo, float inv_cell, int G,
   *pos = f;
   const int c = (int)f;
   return c > G - 1 ? G - 1 : c;
+}
+
+// The cells that hold every row within a FIXED radius of a filed row: those that the row's clamped position (px, py), in cell units as
+// nn_cell gives it, +- reach covers in x and in y, reach = radius / cell + the 2e-3 cell of slack that nn_ring_search subtracts from its
+// lower bound for the fp32 rounding of the cell coordinates.  NOT "the 3 x 3 cells around the row's own": (v - lo) * inv_cell rounds
+// differently on the two sides of a binade edge, so at radius == cell two rows a hair less than one cell apart can be filed two cells
+// apart.  Rows outside the range sit in the border cells, and clamping is a contraction, so the clamped window still holds them.  With
+// radius <= cell: ya >= cy - 2 and yb <= cy + 2 (three cell rows, four for a row within the slack of a cell edge), likewise in x; one
+// cell row's cells xa .. xb are one contiguous span of the cell-ordered rows.  Positions lie in [0, G]: every conversion to int is in
+// range.  The fixed-radius scans (normals.hip, cluster.hip) use this; they walk the cell rows at a FIXED offset -2 .. 2 from the row's
+// own, not from ya, so that the lanes of a wave that share a cell walk the same cell row in the same iteration whichever of them has
+// a fourth one (one lane of a crowded cell that started a row early made its whole wave walk the crowd twice: 1.5 x the launch time
+// of df_normals at 640 rows in a cell).
+struct NnWindow {
+  int xa, xb, ya, yb;
+};
+__device__ __forceinline__ NnWindow nn_window(float px, float py, float reach, int G) {
+  const int top = G - 1;
+  NnWindow w;
+  w.xa = min((int)fmaxf(px - reach, 0.f), top);
+  w.xb = min((int)fminf(px + reach, (float)G), top);
+  w.ya = min((int)fmaxf(py - reach, 0.f), top);
+  w.yb = min((int)fminf(py + reach, (float)G), top);
+  return w;
 }
 
 // Nearest row of one sample's grid to the FINITE query (qx, qy, qz): rings of cells around the query's own cell (ring r = the cells at

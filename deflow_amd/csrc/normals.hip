@@ -80,21 +80,16 @@ __global__ __launch_bounds__(256) void normals_kernel(const int32_t* __restrict_
   float px, py;
   nn_cell(me.x, minx, inv_cell, G, &px);
   const int cy = nn_cell(me.y, miny, inv_cell, G, &py);
-  // the cells that the clamped position +- reach covers (positions lie in [0, G]: every conversion to int is in range)
-  const int top = G - 1;
-  const int xa = min((int)fmaxf(px - reach, 0.f), top), xb = min((int)fminf(px + reach, (float)G), top);
-  const int ya = min((int)fmaxf(py - reach, 0.f), top), yb = min((int)fminf(py + reach, (float)G), top);
+  const NnWindow win = nn_window(px, py, reach, G);         // (nn_search.h: the cells that the clamped position +- reach covers)
   int m = 0;
   double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
-  // ya >= cy - 2 and yb <= cy + 2.  The cell rows are walked at a FIXED offset from the row's own, not from ya: the lanes of a wave that
-  // share a cell then walk the same cell row in the same iteration, whichever of them has a fourth one (one lane of a crowded cell
-  // that started a row early made its whole wave walk the crowd twice: 1.5 x the launch time at 640 rows in a cell)
+  // ya >= cy - 2 and yb <= cy + 2; the cell rows are walked at a FIXED offset from the row's own, not from ya (nn_search.h says why)
 #pragma unroll
   for (int k = -2; k <= 2; ++k) {                          // ascending cell row = ascending position
     const int y = cy + k;
-    if (y < ya || y > yb) continue;
+    if (y < win.ya || y > win.yb) continue;
     const int32_t* rr = rng + (int64_t)y * G * 2;
-    int64_t s = rr[2 * xa], e = rr[2 * xb + 1];
+    int64_t s = rr[2 * win.xa], e = rr[2 * win.xb + 1];
     if (s < s0) s = s0;
     if (e > e0) e = e0;
     for (int64_t q = s; q < e; ++q) {

@@ -677,8 +677,13 @@ int df_chamfer_bwd(const float* query, const float* ref, const int32_t* idx, con
  * Defaults of the Python layer: eps = 0.7 and min_cluster_size = 20 are the recalled arguments of upstream's HDBSCAN call; min_points = 4
  * and min_dynamic_frac = 0.3 are this project's own choices.  All four are arguments.
  * The stages run in this order on one stream and share ws (df_dbscan_ws_bytes(B, N)), after df_nn_grid_build has filed the participating
- * rows (ref = points, rcount = count, rlabel = mask) under a grid with cell >= eps -- the 3 x 3 cells around a row then hold its whole
- * neighbourhood, rows outside the range included (clamping to the border cells is a contraction per coordinate):
+ * rows (ref = points, rcount = count, rlabel = mask) under a grid with cell >= eps.  Every stage scans the cells that a row's clamped
+ * position, in cell units as df_nn_grid_build computes it, +- (eps / cell + 2e-3) covers in x and in y (the 2e-3 cell is df_chamfer_nn's
+ * slack for the fp32 rounding of the cell coordinates) -- three cell rows, four for a row within the slack of a cell edge: they hold
+ * its whole neighbourhood, rows outside the range included (clamping to the border cells is a contraction per coordinate).  NOT "the
+ * 3 x 3 cells around the row's own": at cell == eps, fp32 files two rows a hair less than one cell apart (or exactly one cell apart)
+ * two cells apart where the cell coordinate crosses a power of two.  A row farther than eps adds nothing, so the scanned cells never
+ * show in the result: any cell >= eps gives the same labels.
  * df_dbscan_core: the core flags.   df_dbscan_link: union-find over the core rows (integer compare-and-swap / min; a root is always the
  *   lowest row of its tree, so the forest's roots do not depend on the launch order).   df_dbscan_finish: border rows, member counts
  *   (integer atomic adds), filters, numbering: labels [B,N] i32 and n_clusters [B] i32, both written completely.

@@ -13,10 +13,12 @@ import torch
 BAND = 1e-5
 
 
-def dbscan_ref(points, count=None, mask=None, dynamic=None, eps=0.7, min_points=4, min_cluster_size=1, min_dynamic_frac=0.3):
-    """one cloud: points [N,3], count = valid leading rows (default N), mask / dynamic [N] or None.
+def dbscan_ref(points, count=None, mask=None, dynamic=None, eps=0.7, min_points=4, min_cluster_size=1, min_dynamic_frac=0.3,
+               strict=False, allowed=None):
+    """one cloud: points [N,3], count = valid leading rows (default N), mask / dynamic [N] or None.  strict / allowed: the deliberately
+    WRONG variants of tests/helpers/grid_cases.py (d2 < eps2; neighbours only where the bool [N,N] ``allowed`` says), never the definition.
     -> dict: labels [N] int64, n_clusters, core [N] bool, root [N] int64 (lowest core row of the row's component, -1 = none, BEFORE the
-    filters), border [N] bool, band_pairs, border_ties"""
+    filters), border [N] bool, band_pairs, border_ties, exact_pairs (the band pairs with d2 == eps2 exactly)"""
     p = points.detach().double().cpu()
     N = p.shape[0]
     count = N if count is None else int(count)
@@ -27,7 +29,9 @@ def dbscan_ref(points, count=None, mask=None, dynamic=None, eps=0.7, min_points=
     d2 = sum((q[:, None, c] - q[None, :, c]) ** 2 for c in range(3))      # differences first, then squares
     both = part[:, None] & part[None, :]
     eps2 = float(eps) ** 2
-    near = both & (d2 <= eps2)                                  # N(i): the row itself included
+    near = both & ((d2 < eps2) if strict else (d2 <= eps2))    # N(i): the row itself included
+    if allowed is not None:
+        near &= torch.as_tensor(allowed, dtype=torch.bool)
     off_diag = ~torch.eye(N, dtype=torch.bool)
     band = both & off_diag & (d2 > eps2 * (1 - BAND)) & (d2 < eps2 * (1 + BAND))
     core = part & (near.sum(1) >= int(min_points))
@@ -73,7 +77,7 @@ def dbscan_ref(points, count=None, mask=None, dynamic=None, eps=0.7, min_points=
         k += 1
         labels[members] = k
     return {"labels": labels, "n_clusters": k, "core": core, "root": root, "border": border, "band_pairs": int(band.sum()) // 2,
-            "border_ties": ties}
+            "border_ties": ties, "exact_pairs": int((band & (d2 == eps2)).sum()) // 2}    # (exact_pairs: the band pairs AT eps2)
 
 
 def dbscan_ref_padded(points, count, mask=None, dynamic=None, **kw):

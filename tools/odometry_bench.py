@@ -13,7 +13,7 @@ tools/cluster_bench.py times), for B = 1 and B = --batch and stride 4 and 1, wit
 The point-to-plane rows go to a file of their own (--plane-out; the rows and keys above stay as they are), same clouds, same method:
 
   * one df_normals of pc1 at the default radius, next to ITS yardstick, a DBSCAN core pass (df_dbscan_core, the entry
-    tools/cluster_bench.py times) on the same filed cloud at eps = radius -- the same 3 x 3 walk, once stopping at min_pts rows as the
+    tools/cluster_bench.py times) on the same filed cloud at eps = radius -- the same window (nn_search.h: nn_window), once stopping at min_pts rows as the
     clustering does and once walking every row of the window;
   * one df_reg_accumulate_plane, next to df_reg_accumulate of this library and, with --parent-lib, of the PARENT commit's library loaded
     beside it in the same process (the ratio is reported, not fixed in advance);
