@@ -5,8 +5,9 @@ frame with it).
 UNPINNED: people with their own recordings are normally sent to an external LiDAR odometry for this.  What runs here is this project's own
 definition -- include/deflow_amd.h and DESIGN.md section 6r -- a scan-to-scan, point-to-point ICP with Geman-McClure weights in 6 degrees
 of freedom (``residual="point"``, the default) or, with ``residual="plane"``, a point-to-plane ICP against normals of the target that
-``normals`` estimates on the GPU: no map, no loop closure, no motion un-distortion, and nothing about its accuracy on real sweeps has been
-measured.  Scene flow
+``normals`` estimates on the GPU: no map by default (``target="map"`` registers every sweep against a voxel-capped local map of the sweeps
+so far instead of its predecessor: ``localmap.LocalMap``), no loop closure, no motion un-distortion, and nothing
+about its accuracy on real sweeps has been measured.  Scene flow
 needs only the relative transform of consecutive sweeps (the reference's ``ego_motion``), which is what it estimates; the poses are those
 transforms chained.
 
@@ -41,6 +42,11 @@ RESIDUALS = ("point", "plane")
 DEFAULTS: Dict[str, Any] = {"xy_range": GRID_RANGE, "cell": 1.0, "stride": 4, "levels": LEVELS, "iters": 8, "min_inliers": 50,
                             "planar": False, "residual": "point", "normal_radius": 1.0, "normal_min_pts": 5, "normal_max_curv": 0.05}
 SCENE_DEFAULTS: Dict[str, Any] = {"min_range": 3.0, "max_range": 51.2}
+TARGETS = ("scan", "map")
+# target: what a sweep is registered against -- its predecessor ("scan", the default: which is better on real sweeps is unmeasured) or a
+# local map of the sweeps so far (localmap.LocalMap).  map_*: this project's own choices, unmeasured -- the map's
+# voxel, the rows a voxel keeps, the rows the map holds
+MAP_DEFAULTS: Dict[str, Any] = {"target": "scan", "map_voxel": 0.5, "map_max_per_voxel": 4, "map_capacity": 524288}
 
 
 _tensor = functools.partial(tensor, "register", other="src")
@@ -229,15 +235,26 @@ def chain_poses(rel: Sequence[np.ndarray]) -> List[np.ndarray]:
 
 def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Optional[np.ndarray]]] = None, *, init: str = "previous",
                     min_range: float = SCENE_DEFAULTS["min_range"], max_range: float = SCENE_DEFAULTS["max_range"], device="cuda",
-                    report: Optional[dict] = None, **params) -> List[np.ndarray]:
+                    report: Optional[dict] = None, target: str = MAP_DEFAULTS["target"], map_voxel: float = MAP_DEFAULTS["map_voxel"],
+                    map_max_per_voxel: int = MAP_DEFAULTS["map_max_per_voxel"], map_capacity: int = MAP_DEFAULTS["map_capacity"],
+                    **params) -> List[np.ndarray]:
     """Relative transforms of consecutive sweeps given as arrays [N_i, >= 3], each in its own vehicle frame, in time order:
-    -> rel[k] float64 [4,4] mapping sweep k into sweep k + 1's frame, one B = 1 ``register`` per pair.  ground: per sweep None or a 0 / 1
+    -> rel[k] float64 [4,4] mapping sweep k into sweep k + 1's frame, one B = 1 ``register`` per pair.  target="scan": sweep k + 1 is the
+    target of sweep k.  target="map": sweep k + 1 is registered against a local map of the sweeps 0 .. k seen from pose_k (at most
+    map_max_per_voxel rows per voxel of map_voxel metres, map_capacity rows, a window of max_range about the sensor; DESIGN.md section
+    6t), the map is kept on the device and a failed sweep inserts nothing; rel[k] is then the inverse of that registration's result.  ground: per sweep None or a 0 / 1
     array [N_i]; ground rows do not take part.  Rows take part only at a horizontal distance from the frame's origin in
     [min_range, max_range].  The first pair starts from identity; init="previous": each later pair from the previous pair's result
     (constant velocity), "identity": every pair from identity.  A pair whose status is not 0 keeps its initial transform.
     report: a dict that receives the parameters, the failed pairs and the final inliers / residual of every pair."""
     if init not in ("previous", "identity"):
         raise ValueError(f"register_sweeps: init must be 'previous' or 'identity', got {init!r}")
+    if target not in TARGETS:
+        raise ValueError(f"register_sweeps: target must be 'scan' or 'map', got {target!r}")
+    mp = {"map_voxel": map_voxel, "map_max_per_voxel": map_max_per_voxel, "map_capacity": map_capacity}
+    positive("register_sweeps", mp, "map_voxel")
+    integer("register_sweeps", mp, "map_max_per_voxel", 1, 2 ** 31 - 1)
+    integer("register_sweeps", mp, "map_capacity", 1, 2 ** 30 - 1)
     if not (0 <= float(min_range) < float(max_range)):
         raise ValueError(f"register_sweeps: 0 <= min_range < max_range expected, got {min_range}, {max_range}")
     unknown = sorted(set(params) - set(DEFAULTS))
@@ -262,8 +279,27 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
         clouds.append((torch.from_numpy(p).to(device)[None], torch.full((1,), p.shape[0], dtype=torch.int32, device=device),
                        torch.from_numpy(keep.astype(np.int32)).to(device)[None]))
     start = torch.eye(4, dtype=torch.float64, device=device)[None]
-    Ts, stats = [], []
-    for k in range(len(clouds) - 1):
+    Ts, stats, fill = [], [], []
+    if target == "map" and clouds:
+        from .localmap import LocalMap
+        lmap = LocalMap(1, mp["map_capacity"], voxel=mp["map_voxel"], max_per_voxel=mp["map_max_per_voxel"], max_range=float(max_range),
+                        device=device)
+        pose = start.clone()
+        lmap.insert(*clouds[0][:2], pose, mask=clouds[0][2])
+        fill.append(torch.cat((lmap.count, lmap.stat[0, 3:])))
+        for ps, cs, ms in clouds[1:]:
+            dst, cd = lmap.view(pose)
+            T, info = register(ps, cs, dst, cd, init=start, mask_s=ms, **params)
+            ok = (info["status"] == 0).reshape(1, 1, 1)
+            T = torch.where(ok, T, start)                              # a failed sweep keeps its initial transform ...
+            pose = pose @ T
+            lmap.insert(ps, cs, pose, mask=ms, gate=info["status"])    # ... and inserts nothing
+            Ts.append(T)
+            stats.append(torch.cat((info["status"].to(torch.float32), info["log"][0, -1, :2])))
+            fill.append(torch.cat((lmap.count, lmap.stat[0, 3:])))
+            if init == "previous":
+                start = T
+    for k in range(len(clouds) - 1 if target == "scan" else 0):
         (ps, cs, ms), (pd, cd, md) = clouds[k], clouds[k + 1]
         T, info = register(ps, cs, pd, cd, init=start, mask_s=ms, mask_d=md, **params)
         ok = (info["status"] == 0).reshape(1, 1, 1)
@@ -277,8 +313,14 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
     else:
         rel = list(torch.cat(Ts).cpu().numpy())                        # the one read-back, after every pair was queued
         st = torch.stack(stats).cpu().numpy()
+        if target == "map":                                            # the registration maps sweep k + 1 into sweep k's frame
+            rel = [np.linalg.inv(T) for T in rel]
     if report is not None:
-        report.update(params={**DEFAULTS, **params, "min_range": float(min_range), "max_range": float(max_range), "init": init},
+        if target == "map":
+            mf = torch.stack(fill).cpu().numpy() if fill else np.zeros((0, 2), dtype=np.int32)
+            report.update(map_count=[int(c) for c in mf[:, 0]], map_overflow=[int(c) for c in mf[:, 1]])
+        report.update(params={**DEFAULTS, **params, "min_range": float(min_range), "max_range": float(max_range), "init": init,
+                              "target": target, **mp},
                       failed=[{"pair": int(k), "status": int(s[0])} for k, s in enumerate(st) if int(s[0]) != 0],
                       inliers=[float(s[1]) for s in st], residual=[float(s[2]) for s in st])
     return rel
@@ -370,11 +412,12 @@ def sweep_pose(group, side: Optional[Dict[str, np.ndarray]], *, scene_id: str, t
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
 CLI_DEFAULTS: Dict[str, Any] = {"data_dir": None, "scenes": None, "overwrite": False, "ground_source": "auto", "init": "previous",
-                                **SCENE_DEFAULTS, **{k: (list(v) if isinstance(v, tuple) else v) for k, v in DEFAULTS.items()}}
+                                **SCENE_DEFAULTS, **MAP_DEFAULTS,
+                                **{k: (list(v) if isinstance(v, tuple) else v) for k, v in DEFAULTS.items()}}
 USAGE = ("usage: python -m deflow_amd.odometry data_dir=<dir> [scenes=a,b] [overwrite=false] [stride=4] [levels=2,1,0.5] [iters=8] "
          "[planar=false] [min_inliers=50] [residual=point|plane] [normal_radius=1] [normal_min_pts=5] [normal_max_curv=0.05] "
          "[ground_source=auto|none] [init=previous|identity] [min_range=3] [max_range=51.2] [cell=1] "
-         "[xy_range=-51.2,-51.2,51.2,51.2]")
+         "[xy_range=-51.2,-51.2,51.2,51.2] [target=scan|map] [map_voxel=0.5] [map_max_per_voxel=4] [map_capacity=524288]")
 
 
 def _bool(v: str) -> bool:
@@ -408,6 +451,10 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if v not in RESIDUALS:
                     raise ValueError(v)
                 cfg[k] = v
+            elif k == "target":
+                if v not in TARGETS:
+                    raise ValueError(v)
+                cfg[k] = v
             elif k == "init":
                 if v not in ("previous", "identity"):
                     raise ValueError(v)
@@ -417,14 +464,15 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if (k == "xy_range" and len(cfg[k]) != 4) or not cfg[k] or not all(math.isfinite(x) for x in cfg[k]) or \
                         (k == "levels" and not all(x > 0 for x in cfg[k])):
                     raise ValueError(v)
-            elif k in ("stride", "iters", "min_inliers", "normal_min_pts"):
+            elif k in ("stride", "iters", "min_inliers", "normal_min_pts", "map_max_per_voxel", "map_capacity"):
                 cfg[k] = int(v)
-                lo, hi = {"stride": (1, 1024), "iters": (0, 1024), "min_inliers": (0, 2 ** 31 - 1), "normal_min_pts": (3, 2 ** 31 - 1)}[k]
+                lo, hi = {"stride": (1, 1024), "iters": (0, 1024), "min_inliers": (0, 2 ** 31 - 1), "normal_min_pts": (3, 2 ** 31 - 1),
+                          "map_max_per_voxel": (1, 2 ** 31 - 1), "map_capacity": (1, 2 ** 30 - 1)}[k]
                 if not lo <= cfg[k] <= hi:
                     raise ValueError(v)
             else:
                 cfg[k] = float(v)
-                if not math.isfinite(cfg[k]) or cfg[k] < 0 or (k in ("cell", "normal_radius", "normal_max_curv") and cfg[k] == 0) or \
+                if not math.isfinite(cfg[k]) or cfg[k] < 0 or (k in ("cell", "normal_radius", "normal_max_curv", "map_voxel") and cfg[k] == 0) or \
                         (k == "normal_max_curv" and cfg[k] > 1.0 / 3.0):
                     raise ValueError(v)
         except ValueError:
@@ -443,7 +491,7 @@ def main(argv=None) -> int:
     assert torch.cuda.is_available(), "the odometry runs on the HIP engine only"
     d = cfg["data_dir"]
     scenes = cfg["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
-    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS)}
+    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS, *MAP_DEFAULTS)}
     for sid in scenes:
         out = os.path.join(d, sid + SIDECAR_SUFFIX)
         if os.path.exists(out) and not cfg["overwrite"]:
@@ -452,7 +500,7 @@ def main(argv=None) -> int:
         rep: Dict[str, Any] = {}
         t0 = time.perf_counter()
         poses = scene_poses(os.path.join(d, sid + ".h5"), ground_source=cfg["ground_source"], init=cfg["init"], report=rep, **params)
-        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": "DESIGN.md 6r (UNPINNED)"})
+        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": "DESIGN.md 6r (UNPINNED)" if cfg["target"] == "scan" else "DESIGN.md 6r, 6t (UNPINNED)"})
         ps = list(poses.values())
         path = sum(float(np.linalg.norm(b[:3, 3] - a[:3, 3])) for a, b in zip(ps, ps[1:]))
         n = max(len(rep["inliers"]), 1)

@@ -1267,6 +1267,57 @@ int df_reg_accumulate_plane(const int32_t* src_rng, const float* src_sorted, int
                             int32_t* idx_out /*nullable*/, float* d2_out /*nullable*/, float* w_out /*nullable*/,
                             float* e_out /*nullable*/, void* stream);
 
+/* ------------------------------------------------------------------ local map (scan-to-map odometry) ----
+ * UNPINNED: this project's own definition.  The target of a scan-to-map registration: world-frame points (the
+ * world is the first sweep's frame), at most max_per_voxel = K of them per cubic voxel of edge `voxel`, inside a window of S x S voxel
+ * columns, S = 2 W + 1, about the sensor.  State per sample: map [B,cap,3] f64 and count [B] i32, the number of leading rows that hold
+ * points.  pose [B,16] f64, row-major 4 x 4 on the device: world = R s + t.  One update = df_map_keys, df_cell_sort with
+ * ncells = B S S, df_map_select, df_map_compact; df_map_view makes the dst of df_reg_accumulate's grid.
+ * ARITHMETIC: every float64 operation named below is rounded once, on its own (no fma), so numpy float64 reproduces it bit for bit.
+ *   candidates   n = cap + N rows per sample: the map's rows 0 .. cap-1 first, then the sweep's rows.  A map row TAKES PART when its
+ *                index < count[b]; a sweep row r when r < sweep_count[b], its three coordinates are finite, mask[b,r] > 0 (mask
+ *                nullable) and gate is NULL or gate[b] == 0 (gate: the status of the registration that made the pose, so a failed
+ *                registration inserts nothing, with nothing read back).
+ *   world        of a sweep row (x, y, z): a = R_i0 x; a = a + R_i1 y; a = a + R_i2 z; w_i = a + t_i.  A map row is copied.
+ *   voxel        v_i = floor(w_i / voxel).  A row with a w_i that is not finite or a |v_i| >= 2^30 on any axis does not take part (no
+ *                float-to-integer conversion is made before that check).  Anchor: a_x = floor(t_x / voxel), a_y likewise, under the
+ *                same rule; with an anchor out of range no row of the sample takes part, map rows included.
+ *   key          dx = v_x - a_x + W, dy = v_y - a_y + W; with 0 <= dx, dy <= 2 W the key is (b S + dy) S + dx, else -- and for every
+ *                row that does not take part -- B S S, which df_cell_sort drops: the window cull.  A row with the drop key has
+ *                cand = three float64 NaNs (0x7FF8000000000000) and vz = 0; every other row cand = w, vz = v_z.
+ *   select       df_cell_sort is stable: the rows of a column are in candidate order, map rows first.  For the sorted position p with
+ *                c = idx_sorted[p]: rank = the number of positions of the same column before p whose vz equals vz[c];
+ *                keep[c] = rank < K, and keep = 0 for every candidate that was dropped.  A voxel keeps its first K rows in candidate
+ *                order: older rows win, a full voxel refuses every new row, a map row inside the window is never lost.
+ *   compact      the kept rows of sample b in sorted order are rows 0 .. of map_out [B,cap,3] (NOT the buffer cand was made from: the
+ *                caller double-buffers); kept_b of them.  count_out[b] = min(kept_b, cap); every row from count_out[b] on is three
+ *                float64 NaNs.  stat [B,4] i32 = (rows in the window, kept_b, kept rows that came from the sweep -- counted before the
+ *                cut at cap --, overflow = max(0, kept_b - cap)).  Block counts, one scan of them per sample, scatter.  Sorted order
+ *                is a valid map: the voxel lattice is fixed in the world, rows that share a column always did, their order is their
+ *                age and the next stable sort keeps it.
+ *   view         d_i = w_i - t_i; o_j = (R_0j d_0 + R_1j d_1) + R_2j d_2 in float64, then rounded to fp32 (nearest even).  dst
+ *                [B,cap,3] f32; rows >= count[b] are three fp32 NaNs of pattern 0x7FC00000.
+ * Every output element is written exactly once (df_map_select: a fill launch on the same stream first).  No float atomics; no atomics
+ * at all outside df_cell_sort.  Two calls are bit-identical; sample b depends neither on B nor on the other samples.  The entries never
+ * allocate, synchronise or read back, and no grid dimension comes from a device value.
+ * df_map_ws_bytes(B, cap, N): the bytes of df_map_compact's ws = 8 B ceil((cap + N) / 256); DF_E_SHAPE (negative) for refused shapes.
+ * df_map_keys: map [B,cap,3] f64, count [B], sweep [B,N,3] f32, sweep_count [B], mask [B,N] i32, gate [B] i32, pose [B,16] f64 ->
+ *   cand [B,n,3] f64, key [B n] u32, vz [B n] i32.  One thread per candidate, grid (ceil(n / 256), B).
+ * df_map_select: key, vz as above, idx_sorted [B n] u32 and cell_rng [B S S, 2] i32 as df_cell_sort wrote them -> keep [B n] i32.
+ * df_map_compact: -> map_out [B,cap,3] f64, count_out [B] i32, stat [B,4] i32.
+ * B outside 1..65535, cap / N / n < 1, W outside 1..2047, B n >= 2^30, B S S >= 2^30: DF_E_SHAPE.  NULL pointers (the nullable ones
+ * excepted), a voxel that is not positive and finite, max_per_voxel < 1, map_out == cand: DF_E_ARG.  float64 buffers not 8-byte
+ * aligned: DF_E_ALIGN.  No launch then. */
+int64_t df_map_ws_bytes(int B, int cap, int N);
+int df_map_keys(const double* map, const int32_t* count, const float* sweep, const int32_t* sweep_count, const int32_t* mask /*nullable*/,
+                const int32_t* gate /*nullable*/, const double* pose, int B, int cap, int N, double voxel, int W, double* cand,
+                uint32_t* key, int32_t* vz, void* stream);
+int df_map_select(const uint32_t* key, const uint32_t* idx_sorted, const int32_t* cell_rng, const int32_t* vz, int B, int n, int W,
+                  int max_per_voxel, int32_t* keep, void* stream);
+int df_map_compact(const double* cand, const uint32_t* idx_sorted, const int32_t* cell_rng, const int32_t* keep, int B, int cap, int N,
+                   int W, double* map_out, int32_t* count_out, int32_t* stat, void* ws, void* stream);
+int df_map_view(const double* map, const int32_t* count, const double* pose, int B, int cap, float* dst, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */

@@ -19,6 +19,10 @@ The point-to-plane rows go to a file of their own (--plane-out; the rows and key
     beside it in the same process (the ratio is reported, not fixed in advance);
   * a whole default ``odometry.register`` with residual="point" and residual="plane".
 
+--map [--map-out profiles/localmap_bench.json] measures the local map of the scan-to-map odometry INSTEAD (the files
+above are not rewritten): the five stages of one update at the defaults on those clouds (B = 1), their sum, one df_nn_grid_build of the
+same capacity + N rows as the yardstick, and a default ``register`` against a map view next to the scan-to-scan one.
+
 A measuring tool, not a bench.py leg; needs the GPU (no fallback)."""
 import argparse
 import ctypes
@@ -52,8 +56,62 @@ def timed(fn, reps):
     return sorted(out)[len(out) // 2]
 
 
+def map_bench(a, dev, grid_range, pc0, c0, pc1, c1):
+    """--map: the five stages of one local-map update at the defaults (B = 1), their sum, the yardstick -- one df_nn_grid_build of the
+    same capacity + N rows -- and a default ``register`` against a map view of steady-state size next to the scan-to-scan one"""
+    from deflow_amd.args import workspace
+    from deflow_amd.localmap import LocalMap
+    md = odometry.MAP_DEFAULTS
+    lm = LocalMap(1, md["map_capacity"], voxel=md["map_voxel"], max_per_voxel=md["map_max_per_voxel"],
+                  max_range=odometry.SCENE_DEFAULTS["max_range"], device=dev)
+    pose = torch.eye(4, dtype=torch.float64, device=dev)[None].clone()
+    fill = []
+    for k in range(12):                                # the sensor moves 0.5 m per sweep: the window slides, voxels fill up to K
+        lm.insert(pc0 if k % 2 == 0 else pc1, c0 if k % 2 == 0 else c1, pose)
+        fill.append(int(lm.count))
+        pose[0, 0, 3] += 0.5
+    cap, N, W, K = lm.capacity, pc1.shape[1], lm.W, lm.max_per_voxel
+    n, ncells = cap + N, lm.S * lm.S
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    cand, key, vz, idx, rng, keep = torch.empty(1, n, 3, dtype=torch.float64, device=dev), i32(n), i32(n), i32(n), i32(ncells, 2), i32(n)
+    out, cnt, stat, dst = torch.empty_like(lm.points), i32(1), i32(1, 4), torch.empty(1, cap, 3, dtype=torch.float32, device=dev)
+    ws, sws = workspace("df_map_ws_bytes", (1, cap, N), dev, "shape"), workspace("df_cell_sort_ws_bytes", (ncells,), dev, "shape")
+    stages = {
+        "keys": lambda: call("df_map_keys", ptr(lm.points), ptr(lm.count), ptr(pc1), ptr(c1), None, None, ptr(pose), 1, cap, N, lm.voxel, W,
+                             ptr(cand), ptr(key), ptr(vz), stream()),
+        "cell_sort": lambda: call("df_cell_sort", ptr(key), n, ncells, ptr(idx), ptr(rng), ptr(sws), stream()),
+        "select": lambda: call("df_map_select", ptr(key), ptr(idx), ptr(rng), ptr(vz), 1, n, W, K, ptr(keep), stream()),
+        "compact": lambda: call("df_map_compact", ptr(cand), ptr(idx), ptr(rng), ptr(keep), 1, cap, N, W, ptr(out), ptr(cnt), ptr(stat),
+                                ptr(ws), stream()),
+        "view": lambda: call("df_map_view", ptr(lm.points), ptr(lm.count), ptr(pose), 1, cap, ptr(dst), stream()),
+    }
+    ms = {k: timed(f, a.reps) for k, f in stages.items()}              # in order: each stage reads what the one before wrote
+    both = torch.cat((dst, pc1), dim=1).contiguous()                  # the same capacity + N rows, as one fp32 cloud
+    grid = chamfer.RowGrid(1, grid_range, odometry.DEFAULTS["cell"], dev)
+    t_grid = timed(lambda: grid.file(both, i32(1).fill_(n)), a.reps)
+    view, vcount = lm.view(pose)
+    t_map = timed(lambda: odometry.register(pc1, c1, view, vcount, xy_range=grid_range), a.reps)
+    t_scan = timed(lambda: odometry.register(pc0, c0, pc1, c1, xy_range=grid_range), a.reps)
+    total = sum(ms.values())
+    rep = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "capacity": cap, "sweep_rows": N, "sweep_valid_rows": int(c1),
+           "voxel_m": lm.voxel, "max_per_voxel": K, "window_half_width": W, "map_rows_after_each_insert": fill,
+           "map_rows_steady_state": fill[-1], "stat_of_the_timed_update": stat[0].tolist(),
+           "stage_ms": {k: round(v, 4) for k, v in ms.items()}, "update_ms": round(total, 4),
+           "nn_grid_build_same_rows_ms": round(t_grid, 4), "update_over_grid_build": round(total / t_grid, 3),
+           "register_default_scan_ms": round(t_scan, 3), "register_default_map_view_ms": round(t_map, 3),
+           "update_over_register_scan": round(total / t_scan, 3)}
+    print(json.dumps(rep), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.map_out)), exist_ok=True)
+    with open(a.map_out, "w") as f:
+        json.dump(rep, f, indent=1)
+    print("wrote", a.map_out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--map", action="store_true", help="measure the local map of the scan-to-map odometry only (DESIGN.md section 6t)")
+    ap.add_argument("--map-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                      "localmap_bench.json"))
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--points", type=int, default=80000)
     ap.add_argument("--grid", type=int, default=512)
@@ -80,6 +138,9 @@ def main():
     all0, all1 = st["p0"].points_c.contiguous(), st["p1"].points_c.contiguous()
     cnt0, cnt1 = st["p0"].counts.contiguous(), st["p1"].counts.contiguous()
     del m, st
+    if a.map:
+        map_bench(a, dev, grid_range, all0[:1].contiguous(), cnt0[:1].contiguous(), all1[:1].contiguous(), cnt1[:1].contiguous())
+        return
     cell, max_dist = odometry.DEFAULTS["cell"], odometry.LEVELS[0]
     report = {"device": torch.cuda.get_device_name(0), "cell_m": cell, "max_dist_m": max_dist, "levels": list(odometry.LEVELS),
               "iters": odometry.DEFAULTS["iters"], "reps": a.reps, "cases": []}
