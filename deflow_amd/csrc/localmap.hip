@@ -12,6 +12,8 @@
 //   df_map_compact  block counts of the kept rows, one scan of them per sample, scatter; a row of map_out past the new count gets NaNs
 //                   from the thread of the same index.  No look-back, no atomics.
 //   df_map_view     the map's rows in the sensor's frame, fp32; NaN rows past the count.
+//   df_map_drop     df_map_compact's shape over the map's own rows: block counts of the rows whose flag is 0, one scan per sample,
+//                   scatter into the other buffer (the rows the depth cube of visibility.hip saw through).
 //
 // No float atomics, no integer atomics (df_cell_sort's are the only ones of an update), no LDS outside the 256-wide scans.
 #include <math.h>
@@ -240,6 +242,76 @@ __global__ __launch_bounds__(256) void map_view_kernel(const double* __restrict_
     o[j] = __double2float_rn(__dadd_rn(__dadd_rn(__dmul_rn(T[j], d0), __dmul_rn(T[4 + j], d1)), __dmul_rn(T[8 + j], d2)));
 }
 
+// ---- df_map_drop: the stable compaction of df_map_compact over the map's own rows, keyed by a flag instead of a sorted order ----------
+// row j of sample b stays: j < count[b] and (the sample is gated or flag[b][j] == 0)
+__device__ __forceinline__ int drop_stays(const int32_t* __restrict__ count, const int32_t* __restrict__ flag,
+                                          const int32_t* __restrict__ gate, int b, int cap, int j) {
+  int cnt = count[b];
+  cnt = cnt < 0 ? 0 : (cnt > cap ? cap : cnt);
+  if (j >= cnt) return 0;
+  if (gate && gate[b] != 0) return 1;
+  return flag[(int64_t)b * cap + j] == 0 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void drop_count_kernel(const int32_t* __restrict__ count, const int32_t* __restrict__ flag,
+                                                         const int32_t* __restrict__ gate, int cap, int32_t* __restrict__ blk) {
+  __shared__ int lds[256];
+  const int b = blockIdx.y;
+  int total;
+  map_excl_scan256(drop_stays(count, flag, gate, b, cap, blockIdx.x * 256 + threadIdx.x), lds, &total);
+  if (threadIdx.x == 0) blk[(int64_t)b * gridDim.x + blockIdx.x] = total;
+}
+
+// one block per sample: blk[b][k] becomes the number of staying rows before block k; count_out and stat of the sample
+__global__ __launch_bounds__(256) void drop_scan_kernel(const int32_t* __restrict__ count, const int32_t* __restrict__ gate, int cap,
+                                                        int nblk, int32_t* __restrict__ blk, int32_t* __restrict__ count_out,
+                                                        int32_t* __restrict__ stat) {
+  __shared__ int lds[256];
+  const int b = blockIdx.x;
+  int32_t* mine = blk + (int64_t)b * nblk;
+  int carry = 0;
+  for (int base = 0; base < nblk; base += 256) {
+    const int i = base + threadIdx.x;
+    const int v = i < nblk ? mine[i] : 0;
+    int total;
+    const int ex = map_excl_scan256(v, lds, &total);
+    if (i < nblk) mine[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    int cnt = count[b];
+    cnt = cnt < 0 ? 0 : (cnt > cap ? cap : cnt);
+    const bool gated = gate && gate[b] != 0;
+    count_out[b] = carry;
+    stat[2 * b] = gated ? 0 : cnt;
+    stat[2 * b + 1] = cnt - carry;
+  }
+}
+
+__global__ __launch_bounds__(256) void drop_scatter_kernel(const double* __restrict__ map, const int32_t* __restrict__ count,
+                                                           const int32_t* __restrict__ flag, const int32_t* __restrict__ gate,
+                                                           const int32_t* __restrict__ blk, const int32_t* __restrict__ count_out, int cap,
+                                                           double* __restrict__ map_out) {
+  __shared__ int lds[256];
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const int f = drop_stays(count, flag, gate, b, cap, j);
+  int total;
+  const int64_t at = (int64_t)blk[(int64_t)b * gridDim.x + blockIdx.x] + map_excl_scan256(f, lds, &total);
+  const double* in = map + ((int64_t)b * cap + j) * 3;
+  double* out = map_out + (int64_t)b * cap * 3;
+  if (f && at >= 0 && at < cap) {                        // rows below count_out[b]: each staying row has its own `at` <= j
+    out[at * 3] = in[0];
+    out[at * 3 + 1] = in[1];
+    out[at * 3 + 2] = in[2];
+  }
+  if (j < cap && j >= count_out[b]) {                    // rows from count_out[b] on: the thread of the same index
+    out[(int64_t)j * 3] = map_nan();
+    out[(int64_t)j * 3 + 1] = map_nan();
+    out[(int64_t)j * 3 + 2] = map_nan();
+  }
+}
+
 bool map_shape_ok(int B, int cap, int N, int W) {
   if (B < 1 || B > 65535 || cap < 1 || N < 0 || W < 1 || W > 2047) return false;
   const int64_t S = 2 * (int64_t)W + 1;
@@ -301,6 +373,29 @@ extern "C" int df_map_compact(const double* cand, const uint32_t* idx_sorted, co
   DF_CHECK_LAUNCH();
   hipLaunchKernelGGL(map_scatter_kernel, dim3(nblk, B), dim3(256), 0, s, cand, idx_sorted, cell_rng, keep, blk, count_out, cap, N, S,
                      map_out);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+extern "C" int64_t df_map_drop_ws_bytes(int B, int cap) {
+  if (!map_shape_ok(B, cap, 0, 1)) return DF_E_SHAPE;
+  return (int64_t)B * (((int64_t)cap + 255) / 256) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int df_map_drop(const double* map, const int32_t* count, const int32_t* flag, const int32_t* gate, int B, int cap,
+                           double* map_out, int32_t* count_out, int32_t* stat, void* ws, void* stream) {
+  DF_REQUIRE(map && count && flag && map_out && count_out && stat && ws, DF_E_ARG);
+  DF_REQUIRE(map_shape_ok(B, cap, 0, 1), DF_E_SHAPE);
+  DF_REQUIRE(map_aligned(map, 8) && map_aligned(map_out, 8) && map_aligned(flag, 4) && map_aligned(ws, 4), DF_E_ALIGN);
+  DF_REQUIRE(static_cast<const void*>(map) != static_cast<const void*>(map_out), DF_E_ARG);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nblk = (cap + 255) / 256;
+  int32_t* blk = reinterpret_cast<int32_t*>(ws);
+  hipLaunchKernelGGL(drop_count_kernel, dim3(nblk, B), dim3(256), 0, s, count, flag, gate, cap, blk);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(drop_scan_kernel, dim3(B), dim3(256), 0, s, count, gate, cap, nblk, blk, count_out, stat);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(drop_scatter_kernel, dim3(nblk, B), dim3(256), 0, s, map, count, flag, gate, blk, count_out, cap, map_out);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }

@@ -5,7 +5,9 @@ sweep's frame) in float64, at most ``max_per_voxel`` per cubic voxel, inside a w
 W = ceil(max_range / voxel) + 1.  Older points win: a full voxel refuses every new point, and a point that leaves the window is gone.
 
 CUDA tensors only: there is no CPU fallback.  ``insert`` is df_map_keys, df_cell_sort, df_map_select, df_map_compact and ``view`` is
-df_map_view; nothing reads a device value back, so a recording can be queued whole before its one read-back."""
+df_map_view; nothing reads a device value back, so a recording can be queued whole before its one read-back.  ``carve`` (opt-in,
+DESIGN.md section 6u) is the one way a row inside the window leaves: df_map_view, the depth cube of ``visibility`` built on the current
+sweep and tested on the view, then df_map_drop."""
 from __future__ import annotations
 
 import functools
@@ -90,6 +92,30 @@ class LocalMap:
         call("df_map_compact", ptr(cand), ptr(idx), ptr(rng), ptr(keep), B, cap, N, W, ptr(out), ptr(count_out), ptr(stat), ptr(ws), s)
         self._spare, self.points, self.count, self.stat = self.points, out, count_out, stat
         self.last = {"cand": cand, "key": key, "vz": vz, "idx_sorted": idx, "cell_rng": rng, "keep": keep}     # the stages, for tests
+
+    def carve(self, points: torch.Tensor, count: torch.Tensor, pose: torch.Tensor, *, mask: Optional[torch.Tensor] = None,
+              gate: Optional[torch.Tensor] = None, res: int, halo: int, margin: float, rel: float, near: float) -> None:
+        """drop the map rows that the sweep points [B,N,3] f32 (count, mask as in ``insert``), taken at pose [B,4,4] f64, sees through
+        (UNPINNED: DESIGN.md section 6u): ``view(pose)``, a ``visibility.DepthCube`` of ``res`` bins built on the sweep, its test on the
+        view (halo, margin, rel, near) and df_map_drop into the spare buffer.  A sample with gate != 0 drops nothing.  Replaces .points
+        and .count, sets .carve_stat [B,2] i32 = (rows tested, rows dropped) and keeps the stages in .last_carve."""
+        from .visibility import DepthCube
+        fn = "LocalMap.carve"
+        if gate is not None:
+            gate = _tensor(fn, "gate", gate, torch.int32, (self.B,), self.dev).contiguous()
+        cube = DepthCube(self.B, res, self.dev)
+        B, cap, dev = self.B, self.capacity, self.dev
+        ws = workspace("df_map_drop_ws_bytes", (B, cap), dev, f"{fn}: B = {B} samples of {cap} rows are beyond the entries' limits")
+        dst, _ = self.view(pose)
+        img = cube.build(points, count, mask)
+        flag = cube.seen_through(dst, self.count, halo=halo, margin=margin, rel=rel, near=near)
+        count_out = torch.empty(B, dtype=torch.int32, device=dev)
+        stat = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        out = self._spare
+        call("df_map_drop", ptr(self.points), ptr(self.count), ptr(flag), ptr(gate), B, cap, ptr(out), ptr(count_out), ptr(stat), ptr(ws),
+             stream())
+        self.last_carve = {"view": dst, "count": self.count, "img": img, "flag": flag}     # the stages (count: before the drop), for tests
+        self._spare, self.points, self.count, self.carve_stat = self.points, out, count_out, stat
 
     def view(self, pose: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """the map in the frame of pose [B,4,4] f64 -> (dst [B,capacity,3] f32 with NaN rows past the count, count [B] i32): the

@@ -6,7 +6,8 @@ UNPINNED: people with their own recordings are normally sent to an external LiDA
 definition -- include/deflow_amd.h and DESIGN.md section 6r -- a scan-to-scan, point-to-point ICP with Geman-McClure weights in 6 degrees
 of freedom (``residual="point"``, the default) or, with ``residual="plane"``, a point-to-plane ICP against normals of the target that
 ``normals`` estimates on the GPU: no map by default (``target="map"`` registers every sweep against a voxel-capped local map of the sweeps
-so far instead of its predecessor: ``localmap.LocalMap``), no loop closure, no motion un-distortion, and nothing
+so far instead of its predecessor: ``localmap.LocalMap``; ``map_carve=True`` drops the map rows each sweep sees
+through before it is inserted: DESIGN.md section 6u), no loop closure, no motion un-distortion, and nothing
 about its accuracy on real sweeps has been measured.  Scene flow
 needs only the relative transform of consecutive sweeps (the reference's ``ego_motion``), which is what it estimates; the poses are those
 transforms chained.
@@ -29,7 +30,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
-from .args import cloud, integer, labels, positive, tensor
+from .args import cloud, flag, integer, labels, nonneg, positive, tensor
 from .chamfer import GRID_RANGE, RowGrid
 
 SIDECAR_SUFFIX = ".pose.npz"
@@ -47,6 +48,12 @@ TARGETS = ("scan", "map")
 # local map of the sweeps so far (localmap.LocalMap).  map_*: this project's own choices, unmeasured -- the map's
 # voxel, the rows a voxel keeps, the rows the map holds
 MAP_DEFAULTS: Dict[str, Any] = {"target": "scan", "map_voxel": 0.5, "map_max_per_voxel": 4, "map_capacity": 524288}
+# map_carve: before a sweep is inserted, drop the map rows it sees through (localmap.LocalMap.carve; UNPINNED, off
+# by default).  Choices, not measurements: the depth cube's bins per face edge, the window of bins about a row's own, the absolute and the
+# relative margin by which a return must lie behind a row.  The test's ``near`` is the scene's min_range.  (Beside MAP_DEFAULTS, not in
+# it: the keys of 6t stay what they were.)
+MAP_CARVE_DEFAULTS: Dict[str, Any] = {"map_carve": False, "map_carve_res": 256, "map_carve_halo": 1, "map_carve_margin": 0.5,
+                                      "map_carve_rel": 0.02}
 
 
 _tensor = functools.partial(tensor, "register", other="src")
@@ -237,16 +244,24 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
                     min_range: float = SCENE_DEFAULTS["min_range"], max_range: float = SCENE_DEFAULTS["max_range"], device="cuda",
                     report: Optional[dict] = None, target: str = MAP_DEFAULTS["target"], map_voxel: float = MAP_DEFAULTS["map_voxel"],
                     map_max_per_voxel: int = MAP_DEFAULTS["map_max_per_voxel"], map_capacity: int = MAP_DEFAULTS["map_capacity"],
-                    **params) -> List[np.ndarray]:
+                    map_carve: bool = MAP_CARVE_DEFAULTS["map_carve"], map_carve_res: int = MAP_CARVE_DEFAULTS["map_carve_res"],
+                    map_carve_halo: int = MAP_CARVE_DEFAULTS["map_carve_halo"],
+                    map_carve_margin: float = MAP_CARVE_DEFAULTS["map_carve_margin"],
+                    map_carve_rel: float = MAP_CARVE_DEFAULTS["map_carve_rel"], **params) -> List[np.ndarray]:
     """Relative transforms of consecutive sweeps given as arrays [N_i, >= 3], each in its own vehicle frame, in time order:
     -> rel[k] float64 [4,4] mapping sweep k into sweep k + 1's frame, one B = 1 ``register`` per pair.  target="scan": sweep k + 1 is the
     target of sweep k.  target="map": sweep k + 1 is registered against a local map of the sweeps 0 .. k seen from pose_k (at most
     map_max_per_voxel rows per voxel of map_voxel metres, map_capacity rows, a window of max_range about the sensor; DESIGN.md section
     6t), the map is kept on the device and a failed sweep inserts nothing; rel[k] is then the inverse of that registration's result.  ground: per sweep None or a 0 / 1
+    map_carve=True (target="map" only; UNPINNED): between the pose of sweep k + 1 and its insertion the map rows
+    that the sweep sees through are dropped -- a depth cube of map_carve_res bins per face edge built on the sweep's participating rows,
+    a map row flagged when a return lies more than map_carve_margin + map_carve_rel x its depth behind it in the (2 map_carve_halo + 1)^2
+    bins about its own, rows nearer than min_range left alone; a failed sweep carves nothing.  ground: per sweep None or a 0 / 1
     array [N_i]; ground rows do not take part.  Rows take part only at a horizontal distance from the frame's origin in
     [min_range, max_range].  The first pair starts from identity; init="previous": each later pair from the previous pair's result
     (constant velocity), "identity": every pair from identity.  A pair whose status is not 0 keeps its initial transform.
-    report: a dict that receives the parameters, the failed pairs and the final inliers / residual of every pair."""
+    report: a dict that receives the parameters, the failed pairs and the final inliers / residual of every pair (target="map": also
+    map_count and map_overflow after every sweep, and with map_carve map_carved, the rows every later sweep dropped)."""
     if init not in ("previous", "identity"):
         raise ValueError(f"register_sweeps: init must be 'previous' or 'identity', got {init!r}")
     if target not in TARGETS:
@@ -255,6 +270,19 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
     positive("register_sweeps", mp, "map_voxel")
     integer("register_sweeps", mp, "map_max_per_voxel", 1, 2 ** 31 - 1)
     integer("register_sweeps", mp, "map_capacity", 1, 2 ** 30 - 1)
+    cp = {"map_carve": map_carve, "map_carve_res": map_carve_res, "map_carve_halo": map_carve_halo, "map_carve_margin": map_carve_margin,
+          "map_carve_rel": map_carve_rel}
+    flag("register_sweeps", cp, "map_carve")
+    if cp["map_carve"]:
+        if target != "map":
+            raise ValueError("register_sweeps: map_carve=True needs target='map': there is no map to carve with target='scan'")
+        from .visibility import HALO_MAX, RES_MAX
+        integer("register_sweeps", cp, "map_carve_res", 2, RES_MAX)
+        if cp["map_carve_res"] % 2:
+            raise ValueError(f"register_sweeps: map_carve_res must be even, got {map_carve_res!r}")
+        integer("register_sweeps", cp, "map_carve_halo", 0, HALO_MAX)
+        nonneg("register_sweeps", cp, "map_carve_margin")
+        nonneg("register_sweeps", cp, "map_carve_rel")
     if not (0 <= float(min_range) < float(max_range)):
         raise ValueError(f"register_sweeps: 0 <= min_range < max_range expected, got {min_range}, {max_range}")
     unknown = sorted(set(params) - set(DEFAULTS))
@@ -279,7 +307,7 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
         clouds.append((torch.from_numpy(p).to(device)[None], torch.full((1,), p.shape[0], dtype=torch.int32, device=device),
                        torch.from_numpy(keep.astype(np.int32)).to(device)[None]))
     start = torch.eye(4, dtype=torch.float64, device=device)[None]
-    Ts, stats, fill = [], [], []
+    Ts, stats, fill, carved = [], [], [], []
     if target == "map" and clouds:
         from .localmap import LocalMap
         lmap = LocalMap(1, mp["map_capacity"], voxel=mp["map_voxel"], max_per_voxel=mp["map_max_per_voxel"], max_range=float(max_range),
@@ -293,6 +321,10 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
             ok = (info["status"] == 0).reshape(1, 1, 1)
             T = torch.where(ok, T, start)                              # a failed sweep keeps its initial transform ...
             pose = pose @ T
+            if cp["map_carve"]:                                        # ... carves nothing ...
+                lmap.carve(ps, cs, pose, mask=ms, gate=info["status"], res=cp["map_carve_res"], halo=cp["map_carve_halo"],
+                           margin=cp["map_carve_margin"], rel=cp["map_carve_rel"], near=float(min_range))
+                carved.append(lmap.carve_stat[0, 1:])
             lmap.insert(ps, cs, pose, mask=ms, gate=info["status"])    # ... and inserts nothing
             Ts.append(T)
             stats.append(torch.cat((info["status"].to(torch.float32), info["log"][0, -1, :2])))
@@ -319,8 +351,10 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
         if target == "map":
             mf = torch.stack(fill).cpu().numpy() if fill else np.zeros((0, 2), dtype=np.int32)
             report.update(map_count=[int(c) for c in mf[:, 0]], map_overflow=[int(c) for c in mf[:, 1]])
+            if cp["map_carve"]:
+                report.update(map_carved=[int(c) for c in torch.cat(carved).cpu().numpy()] if carved else [])
         report.update(params={**DEFAULTS, **params, "min_range": float(min_range), "max_range": float(max_range), "init": init,
-                              "target": target, **mp},
+                              "target": target, **mp, **cp},
                       failed=[{"pair": int(k), "status": int(s[0])} for k, s in enumerate(st) if int(s[0]) != 0],
                       inliers=[float(s[1]) for s in st], residual=[float(s[2]) for s in st])
     return rel
@@ -412,12 +446,13 @@ def sweep_pose(group, side: Optional[Dict[str, np.ndarray]], *, scene_id: str, t
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
 CLI_DEFAULTS: Dict[str, Any] = {"data_dir": None, "scenes": None, "overwrite": False, "ground_source": "auto", "init": "previous",
-                                **SCENE_DEFAULTS, **MAP_DEFAULTS,
+                                **SCENE_DEFAULTS, **MAP_DEFAULTS, **MAP_CARVE_DEFAULTS,
                                 **{k: (list(v) if isinstance(v, tuple) else v) for k, v in DEFAULTS.items()}}
 USAGE = ("usage: python -m deflow_amd.odometry data_dir=<dir> [scenes=a,b] [overwrite=false] [stride=4] [levels=2,1,0.5] [iters=8] "
          "[planar=false] [min_inliers=50] [residual=point|plane] [normal_radius=1] [normal_min_pts=5] [normal_max_curv=0.05] "
          "[ground_source=auto|none] [init=previous|identity] [min_range=3] [max_range=51.2] [cell=1] "
-         "[xy_range=-51.2,-51.2,51.2,51.2] [target=scan|map] [map_voxel=0.5] [map_max_per_voxel=4] [map_capacity=524288]")
+         "[xy_range=-51.2,-51.2,51.2,51.2] [target=scan|map] [map_voxel=0.5] [map_max_per_voxel=4] [map_capacity=524288] "
+         "[map_carve=false] [map_carve_res=256] [map_carve_halo=1] [map_carve_margin=0.5] [map_carve_rel=0.02]")
 
 
 def _bool(v: str) -> bool:
@@ -441,7 +476,7 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 cfg[k] = v
             elif k == "scenes":
                 cfg[k] = [s for s in v.split(",") if s]
-            elif k in ("overwrite", "planar"):
+            elif k in ("overwrite", "planar", "map_carve"):
                 cfg[k] = _bool(v)
             elif k == "ground_source":
                 if v not in ("auto", "none"):
@@ -464,11 +499,13 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if (k == "xy_range" and len(cfg[k]) != 4) or not cfg[k] or not all(math.isfinite(x) for x in cfg[k]) or \
                         (k == "levels" and not all(x > 0 for x in cfg[k])):
                     raise ValueError(v)
-            elif k in ("stride", "iters", "min_inliers", "normal_min_pts", "map_max_per_voxel", "map_capacity"):
+            elif k in ("stride", "iters", "min_inliers", "normal_min_pts", "map_max_per_voxel", "map_capacity", "map_carve_res",
+                       "map_carve_halo"):
                 cfg[k] = int(v)
                 lo, hi = {"stride": (1, 1024), "iters": (0, 1024), "min_inliers": (0, 2 ** 31 - 1), "normal_min_pts": (3, 2 ** 31 - 1),
-                          "map_max_per_voxel": (1, 2 ** 31 - 1), "map_capacity": (1, 2 ** 30 - 1)}[k]
-                if not lo <= cfg[k] <= hi:
+                          "map_max_per_voxel": (1, 2 ** 31 - 1), "map_capacity": (1, 2 ** 30 - 1), "map_carve_res": (2, 2048),
+                          "map_carve_halo": (0, 4)}[k]
+                if not lo <= cfg[k] <= hi or (k == "map_carve_res" and cfg[k] % 2):
                     raise ValueError(v)
             else:
                 cfg[k] = float(v)
@@ -481,6 +518,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         raise SystemExit(USAGE)
     if not cfg["min_range"] < cfg["max_range"]:
         raise SystemExit(f"bad value for min_range / max_range: {cfg['min_range']} .. {cfg['max_range']}")
+    if cfg["map_carve"] and cfg["target"] != "map":
+        raise SystemExit("bad value for map_carve / target: map_carve=true needs target=map")
     if cfg["residual"] == "plane" and cfg["normal_radius"] > cfg["cell"]:
         raise SystemExit(f"bad value for normal_radius / cell: the radius {cfg['normal_radius']} is larger than the cell {cfg['cell']}")
     return cfg
@@ -491,7 +530,7 @@ def main(argv=None) -> int:
     assert torch.cuda.is_available(), "the odometry runs on the HIP engine only"
     d = cfg["data_dir"]
     scenes = cfg["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
-    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS, *MAP_DEFAULTS)}
+    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS, *MAP_DEFAULTS, *MAP_CARVE_DEFAULTS)}
     for sid in scenes:
         out = os.path.join(d, sid + SIDECAR_SUFFIX)
         if os.path.exists(out) and not cfg["overwrite"]:
@@ -500,7 +539,7 @@ def main(argv=None) -> int:
         rep: Dict[str, Any] = {}
         t0 = time.perf_counter()
         poses = scene_poses(os.path.join(d, sid + ".h5"), ground_source=cfg["ground_source"], init=cfg["init"], report=rep, **params)
-        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": "DESIGN.md 6r (UNPINNED)" if cfg["target"] == "scan" else "DESIGN.md 6r, 6t (UNPINNED)"})
+        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": "DESIGN.md 6r (UNPINNED)" if cfg["target"] == "scan" else "DESIGN.md 6r, 6t, 6u (UNPINNED)" if cfg["map_carve"] else "DESIGN.md 6r, 6t (UNPINNED)"})
         ps = list(poses.values())
         path = sum(float(np.linalg.norm(b[:3, 3] - a[:3, 3])) for a, b in zip(ps, ps[1:]))
         n = max(len(rep["inliers"]), 1)

@@ -1318,6 +1318,55 @@ int df_map_compact(const double* cand, const uint32_t* idx_sorted, const int32_t
                    int W, double* map_out, int32_t* count_out, int32_t* stat, void* ws, void* stream);
 int df_map_view(const double* map, const int32_t* count, const double* pose, int B, int cap, float* dst, void* stream);
 
+/* ------------------------------------------------------------------ depth cube: carving seen-through rows out of the local map ----
+ * UNPINNED: this project's own definition; every default of its callers is a choice, not a measurement.  A map
+ * row is stale when the current sweep sees through it: a return of the sweep lies well behind the row, along the same direction from
+ * the sensor.  The sweep is filed in a DEPTH CUBE about the origin of its own frame -- six faces of R x R bins, R even, img [B,6,R,R]
+ * u32 -- and the map's view (df_map_view) is tested against it; df_map_drop then compacts the flagged rows away.
+ * ARITHMETIC: no transcendental function; every fp32 operation named below is rounded once, on its own (no fma), so numpy float32
+ * reproduces every value bit for bit.
+ *   face, bin    of a row (x, y, z): ax, ay, az = the absolute values.  The major axis is 0 if ax >= ay and ax >= az, else 1 if
+ *                ay >= az, else 2 (on ties the earlier axis wins).  face = 2 axis + (the major coordinate < 0), so -0.0 is on the
+ *                positive face.  m = the absolute major coordinate: the row's DEPTH.  (uc, vc) = the other two coordinates in
+ *                ascending axis order.  u = uc / m; i = min(R - 1, (int) floor((u + 1) * (R / 2))) (one division, one addition, one
+ *                multiplication; R / 2 is exact); j likewise from vc.  The row's bin is img[b][face][j][i].
+ *   takes part   a row r with r < count[b], mask[b,r] > 0 (mask nullable), three finite coordinates and m > 0.
+ *   build        every bin = 0x7F800000 (+inf: no return), then the integer minimum of the bit patterns of m over the rows that take
+ *                part and fall into the bin (positive floats order as their bits).
+ *   test         a query row gets flag = 1 (SEEN THROUGH) exactly when it takes part (count_q; there is no mask), max(|x|, |y|) >=
+ *                near (rows the sweep's own min_range band hides are left alone), its own bin is not +inf (an empty bin is no
+ *                evidence), the whole window i - halo .. i + halo, j - halo .. j + halo lies inside 0 .. R - 1 (on the row's face:
+ *                conservative at face edges) and  (m * c) + margin < dmin,  dmin = the smallest depth of the window's bins and
+ *                c = 1 + rel in fp32, computed once on the host from the fp32 argument.  Every other row gets flag = 0.  depth_out
+ *                [B,M] f32 (nullable) = dmin for a row that takes part and whose window lies on its face, else +inf (0x7F800000).
+ * Every element of flag and depth_out is written exactly once; img by a fill launch and then by atomicMin only.  The statement of the
+ * local map section that an update runs no atomics outside df_cell_sort does NOT cover df_depth_cube_build: it is one integer atomicMin
+ * per row.  An integer minimum does not depend on the order of its operands, so two calls are still bit-identical, and sample b depends
+ * neither on B nor on the other samples.  The entries never allocate, synchronise or read back; no grid dimension comes from a device
+ * value.
+ * df_depth_cube_build: points [B,N,3] f32, count [B] i32, mask [B,N] i32 -> img [B,6,R,R] u32.  Grid (ceil(N / 256), B) after the fill.
+ * df_depth_cube_test: query [B,M,3] f32, count_q [B] i32, img -> flag [B,M] i32, depth_out [B,M] f32.  Grid (ceil(M / 256), B).
+ * B outside 1..65535, N / M < 1, B N or B M >= 2^30, R odd or outside 2..2048, 6 B R R >= 2^30: DF_E_SHAPE.  NULL pointers (the nullable
+ * ones excepted), halo outside 0..4, margin / rel / near negative or not finite: DF_E_ARG.  Buffers not 4-byte aligned: DF_E_ALIGN.
+ *
+ * df_map_drop: a stable out-of-place compaction of the map -- block counts, one scan per sample and a scatter, df_map_compact's shape.
+ *   map [B,cap,3] f64, count [B] i32, flag [B,cap] i32, gate [B] i32 (nullable) -> map_out [B,cap,3] f64 (NOT map: the caller
+ *   double-buffers), count_out [B] i32, stat [B,2] i32.  With c_b = count[b] held to 0 .. cap: the rows j < c_b with flag[b,j] == 0 are
+ *   rows 0 .. of map_out in their order (relative order is age, all the next stable sort needs: the result is a valid map under the
+ *   argument of `compact` above); count_out[b] = their number; every row from count_out[b] on is three float64 NaNs
+ *   (0x7FF8000000000000); a flag at j >= c_b is not looked at.  stat = (rows tested = c_b, rows dropped = c_b - count_out[b]).  A sample
+ *   with gate[b] != 0 keeps every row j < c_b whatever its flags and has stat = (0, 0).  No atomics; two calls are bit-identical.
+ * df_map_drop_ws_bytes(B, cap): the bytes of ws = 4 B ceil(cap / 256); DF_E_SHAPE (negative) for refused shapes.
+ * B outside 1..65535, cap < 1, B cap >= 2^30: DF_E_SHAPE.  NULL pointers (gate excepted), map_out == map: DF_E_ARG.  float64 buffers not
+ * 8-byte aligned: DF_E_ALIGN.  No launch then. */
+int df_depth_cube_build(const float* points, const int32_t* count, const int32_t* mask /*nullable*/, int B, int N, int R, uint32_t* img,
+                        void* stream);
+int df_depth_cube_test(const float* query, const int32_t* count_q, const uint32_t* img, int B, int M, int R, int halo, float margin,
+                       float rel, float near, int32_t* flag, float* depth_out /*nullable*/, void* stream);
+int64_t df_map_drop_ws_bytes(int B, int cap);
+int df_map_drop(const double* map, const int32_t* count, const int32_t* flag, const int32_t* gate /*nullable*/, int B, int cap,
+                double* map_out, int32_t* count_out, int32_t* stat, void* ws, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (A12) ----
  * torch.optim.Adam (defaults: no amsgrad, no weight decay) over ONE flat fp32 arena holding every
  * parameter; grad/exp_avg/exp_avg_sq are arenas of the same layout.  n % 4 == 0. */

@@ -1,5 +1,5 @@
 """What the sweep-to-sweep registration costs on the GPU, measured: usage  python tools/odometry_bench.py [--batch 16] [--points 80000]
-[--grid 512] [--reps 20] [--out profiles/odometry_bench.json] [--plane-out profiles/odometry_plane_bench.json] [--parent-lib <libdeflow_amd.so>]
+[--grid 512] [--reps 20] [--map | --carve] [--out profiles/odometry_bench.json] [--plane-out profiles/odometry_plane_bench.json] [--parent-lib <libdeflow_amd.so>]
 
 At the configs[2] cloud (80 000 rows per cloud, 512 x 512; ~70 000 rows in range: the compact pc0 / pc1 of a real forward, the clouds
 tools/cluster_bench.py times), for B = 1 and B = --batch and stride 4 and 1, with device events after a warm-up (medians of --reps calls):
@@ -22,6 +22,12 @@ The point-to-plane rows go to a file of their own (--plane-out; the rows and key
 --map [--map-out profiles/localmap_bench.json] measures the local map of the scan-to-map odometry INSTEAD (the files
 above are not rewritten): the five stages of one update at the defaults on those clouds (B = 1), their sum, one df_nn_grid_build of the
 same capacity + N rows as the yardstick, and a default ``register`` against a map view next to the scan-to-scan one.
+
+--carve [--carve-out profiles/localmap_carve_bench.json] measures the carving of seen-through rows INSTEAD, on the
+same clouds and the same map (B = 1, capacity 524 288, the cube and the margins at their defaults): df_map_view, df_depth_cube_build,
+df_depth_cube_test and df_map_drop one by one, the four back to back, a whole ``LocalMap.carve`` (which also allocates), and the
+yardsticks in the same process -- df_map_view over the same rows (the streaming floor of the test kernel) and the four stages of one
+insert update.
 
 A measuring tool, not a bench.py leg; needs the GPU (no fallback)."""
 import argparse
@@ -107,8 +113,75 @@ def map_bench(a, dev, grid_range, pc0, c0, pc1, c1):
     print("wrote", a.map_out)
 
 
+def carve_bench(a, dev, pc0, c0, pc1, c1):
+    """--carve: the four stages of one LocalMap.carve at the defaults (B = 1), their sequence, the wrapper, and the yardsticks"""
+    from deflow_amd.args import workspace
+    from deflow_amd.localmap import LocalMap
+    md, cd = odometry.MAP_DEFAULTS, odometry.MAP_CARVE_DEFAULTS
+    near = odometry.SCENE_DEFAULTS["min_range"]
+    lm = LocalMap(1, md["map_capacity"], voxel=md["map_voxel"], max_per_voxel=md["map_max_per_voxel"],
+                  max_range=odometry.SCENE_DEFAULTS["max_range"], device=dev)
+    pose = torch.eye(4, dtype=torch.float64, device=dev)[None].clone()
+    for k in range(12):                                # as --map: the sensor moves 0.5 m per sweep, the map reaches its steady state
+        lm.insert(pc0 if k % 2 == 0 else pc1, c0 if k % 2 == 0 else c1, pose)
+        pose[0, 0, 3] += 0.5
+    cap, N, W, K, R = lm.capacity, pc1.shape[1], lm.W, lm.max_per_voxel, cd["map_carve_res"]
+    n, ncells = cap + N, lm.S * lm.S
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    dst, img, flag = torch.empty(1, cap, 3, dtype=torch.float32, device=dev), i32(1, 6, R, R), i32(1, cap)
+    out, cnt, stat, ws = torch.empty_like(lm.points), i32(1), i32(1, 2), workspace("df_map_drop_ws_bytes", (1, cap), dev, "shape")
+    halo, margin, rel = cd["map_carve_halo"], cd["map_carve_margin"], cd["map_carve_rel"]
+    stages = {
+        "view": lambda: call("df_map_view", ptr(lm.points), ptr(lm.count), ptr(pose), 1, cap, ptr(dst), stream()),
+        "build": lambda: call("df_depth_cube_build", ptr(pc1), ptr(c1), None, 1, N, R, ptr(img), stream()),
+        "test": lambda: call("df_depth_cube_test", ptr(dst), ptr(lm.count), ptr(img), 1, cap, R, halo, margin, rel, near, ptr(flag), None,
+                             stream()),
+        "drop": lambda: call("df_map_drop", ptr(lm.points), ptr(lm.count), ptr(flag), None, 1, cap, ptr(out), ptr(cnt), ptr(stat), ptr(ws),
+                             stream()),
+    }
+    ms = {k: timed(f, a.reps) for k, f in stages.items()}              # in order: each stage reads what the one before wrote
+    t_seq = timed(lambda: [f() for f in stages.values()], a.reps)
+    dropped = stat[0].tolist()
+    state = (lm.points, lm._spare, lm.count)
+
+    def whole():                                                       # the wrapper, every call from the same map
+        lm.points, lm._spare, lm.count = state
+        lm.carve(pc1, c1, pose, res=R, halo=halo, margin=margin, rel=rel, near=near)
+
+    t_whole = timed(whole, a.reps)
+    lm.points, lm._spare, lm.count = state
+    cand, key, vz, idx, rng, keep = torch.empty(1, n, 3, dtype=torch.float64, device=dev), i32(n), i32(n), i32(n), i32(ncells, 2), i32(n)
+    cnt4, stat4 = i32(1), i32(1, 4)
+    mws, sws = workspace("df_map_ws_bytes", (1, cap, N), dev, "shape"), workspace("df_cell_sort_ws_bytes", (ncells,), dev, "shape")
+    update = {
+        "keys": lambda: call("df_map_keys", ptr(lm.points), ptr(lm.count), ptr(pc1), ptr(c1), None, None, ptr(pose), 1, cap, N, lm.voxel, W,
+                             ptr(cand), ptr(key), ptr(vz), stream()),
+        "cell_sort": lambda: call("df_cell_sort", ptr(key), n, ncells, ptr(idx), ptr(rng), ptr(sws), stream()),
+        "select": lambda: call("df_map_select", ptr(key), ptr(idx), ptr(rng), ptr(vz), 1, n, W, K, ptr(keep), stream()),
+        "compact": lambda: call("df_map_compact", ptr(cand), ptr(idx), ptr(rng), ptr(keep), 1, cap, N, W, ptr(out), ptr(cnt4), ptr(stat4),
+                                ptr(mws), stream()),
+    }
+    ums = {k: timed(f, a.reps) for k, f in update.items()}
+    total, utotal = sum(ms.values()), sum(ums.values())
+    rep = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "capacity": cap, "map_rows": int(lm.count), "sweep_rows": N,
+           "sweep_valid_rows": int(c1), "cube_res": R, "halo": halo, "margin_m": margin, "rel": rel, "near_m": near,
+           "rows_tested_dropped": dropped, "stage_ms": {k: round(v, 4) for k, v in ms.items()}, "stages_sum_ms": round(total, 4),
+           "stages_back_to_back_ms": round(t_seq, 4), "localmap_carve_call_ms": round(t_whole, 4),
+           "map_view_same_rows_ms": round(ms["view"], 4), "test_over_map_view": round(ms["test"] / ms["view"], 3),
+           "insert_update_stage_ms": {k: round(v, 4) for k, v in ums.items()}, "insert_update_ms": round(utotal, 4),
+           "carve_over_insert_update": round(total / utotal, 3)}
+    print(json.dumps(rep), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.carve_out)), exist_ok=True)
+    with open(a.carve_out, "w") as f:
+        json.dump(rep, f, indent=1)
+    print("wrote", a.carve_out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--carve", action="store_true", help="measure the carving of seen-through map rows only (DESIGN.md section 6u)")
+    ap.add_argument("--carve-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                        "localmap_carve_bench.json"))
     ap.add_argument("--map", action="store_true", help="measure the local map of the scan-to-map odometry only (DESIGN.md section 6t)")
     ap.add_argument("--map-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                       "localmap_bench.json"))
@@ -138,6 +211,9 @@ def main():
     all0, all1 = st["p0"].points_c.contiguous(), st["p1"].points_c.contiguous()
     cnt0, cnt1 = st["p0"].counts.contiguous(), st["p1"].counts.contiguous()
     del m, st
+    if a.carve:
+        carve_bench(a, dev, all0[:1].contiguous(), cnt0[:1].contiguous(), all1[:1].contiguous(), cnt1[:1].contiguous())
+        return
     if a.map:
         map_bench(a, dev, grid_range, all0[:1].contiguous(), cnt0[:1].contiguous(), all1[:1].contiguous(), cnt1[:1].contiguous())
         return
