@@ -221,6 +221,8 @@ _SIGS = {
     "df_depth_cube_test": [P, P, P, I, I, I, I, F, F, F, P, P, P],
     "df_map_drop_ws_bytes": [I, I],
     "df_map_drop": [P, P, P, P, I, I, P, P, P, P, P],
+    "df_map_near_ws_bytes": [I, I, I, I],                  # (6v; placed here for the same reason)
+    "df_map_compact_near": [P, P, P, P, P, I, I, I, I, P, P, P, P, P, P],
     "df_reg_ws_bytes": [I, I],
     "df_reg_accumulate": [P, P, I, P, P, F, F, F, I, I, I, I, P, F, F, P, P, P, P, P, P],
     "df_reg_solve": [P, I, I, I, I, P, P, P, P],
@@ -232,8 +234,8 @@ _SIGS = {
     "df_map_compact": [P, P, P, P, I, I, I, I, P, P, P, P, P],
     "df_map_view": [P, P, P, I, I, P, P],
 }
-_RESTYPE = {"df_mlp_ws_bytes": C.c_int64, "df_dt_ws_bytes": C.c_int64, "df_vox_plan_ws_bytes": C.c_int64,"df_submit_body_stride": C.c_int64, "df_sweep_compact_ws_bytes": C.c_int64, "df_flow_compose_ws_bytes": C.c_int64, "df_metrics_ws_bytes": C.c_int64,"df_cell_sort_ws_bytes": C.c_int64, "df_nn_grid_ws_bytes": C.c_int64, "df_chamfer_bwd_ws_bytes": C.c_int64, "df_dbscan_ws_bytes": C.c_int64, "df_rigid_segments_ws_bytes": C.c_int64, "df_rigid_icp_ws_bytes": C.c_int64, "df_reg_ws_bytes": C.c_int64, "df_map_ws_bytes": C.c_int64, "df_map_drop_ws_bytes": C.c_int64}
-_RAW = {"df_reg_ws_bytes", "df_map_ws_bytes", "df_map_drop_ws_bytes", "df_mlp_ws_bytes", "df_dt_ws_bytes", "df_vox_plan_ws_bytes","df_rigid_segments_ws_bytes", "df_rigid_icp_ws_bytes", "df_submit_body_stride", "df_sweep_rows_per_block", "df_sweep_compact_ws_bytes", "df_flow_compose_ws_bytes", "df_metrics_rows_per_block","df_metrics_ws_bytes", "df_dbscan_ws_bytes", "df_nn_grid_ws_bytes", "df_chamfer_bwd_ws_bytes", "df_pillar2_rows_per_band", "df_pillar2_tile", "df_version", "df_cell_sort_ws_bytes", "df_conv2d_tile_m", "df_conv2d_wgrad_splits", "df_conv2d_variant", "df_conv2d_w16_ok", "df_conv2d_x3_ok", "df_conv2d_wgrad_x3_ok", "df_conv2d_h2p_ok", "df_conv2d_wgrad_h2p_ok", "df_conv2d_wgrad_h2p_splits", "df_conv2d_wgrad1_h2_ok", "df_conv2d_wgrad1_h2_splits", "df_conv2d_wgrad_s2_h2_ok", "df_conv2d_wgrad_s2_h2_splits", "df_conv2d_last_dma", "df_gru_wgrad_splits", "df_gru_lean_partial_width"}  # return values, not status
+_RESTYPE = {"df_mlp_ws_bytes": C.c_int64, "df_dt_ws_bytes": C.c_int64, "df_vox_plan_ws_bytes": C.c_int64,"df_submit_body_stride": C.c_int64, "df_sweep_compact_ws_bytes": C.c_int64, "df_flow_compose_ws_bytes": C.c_int64, "df_metrics_ws_bytes": C.c_int64,"df_cell_sort_ws_bytes": C.c_int64, "df_nn_grid_ws_bytes": C.c_int64, "df_chamfer_bwd_ws_bytes": C.c_int64, "df_dbscan_ws_bytes": C.c_int64, "df_rigid_segments_ws_bytes": C.c_int64, "df_rigid_icp_ws_bytes": C.c_int64, "df_reg_ws_bytes": C.c_int64, "df_map_ws_bytes": C.c_int64, "df_map_drop_ws_bytes": C.c_int64, "df_map_near_ws_bytes": C.c_int64}
+_RAW = {"df_reg_ws_bytes", "df_map_ws_bytes", "df_map_drop_ws_bytes", "df_map_near_ws_bytes", "df_mlp_ws_bytes", "df_dt_ws_bytes", "df_vox_plan_ws_bytes","df_rigid_segments_ws_bytes", "df_rigid_icp_ws_bytes", "df_submit_body_stride", "df_sweep_rows_per_block", "df_sweep_compact_ws_bytes", "df_flow_compose_ws_bytes", "df_metrics_rows_per_block","df_metrics_ws_bytes", "df_dbscan_ws_bytes", "df_nn_grid_ws_bytes", "df_chamfer_bwd_ws_bytes", "df_pillar2_rows_per_band", "df_pillar2_tile", "df_version", "df_cell_sort_ws_bytes", "df_conv2d_tile_m", "df_conv2d_wgrad_splits", "df_conv2d_variant", "df_conv2d_w16_ok", "df_conv2d_x3_ok", "df_conv2d_wgrad_x3_ok", "df_conv2d_h2p_ok", "df_conv2d_wgrad_h2p_ok", "df_conv2d_wgrad_h2p_splits", "df_conv2d_wgrad1_h2_ok", "df_conv2d_wgrad1_h2_splits", "df_conv2d_wgrad_s2_h2_ok", "df_conv2d_wgrad_s2_h2_splits", "df_conv2d_last_dma", "df_gru_wgrad_splits", "df_gru_lean_partial_width"}  # return values, not status
 
 _lib: Optional[C.CDLL] = None
 

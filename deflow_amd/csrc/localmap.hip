@@ -14,8 +14,14 @@
 //   df_map_view     the map's rows in the sensor's frame, fp32; NaN rows past the count.
 //   df_map_drop     df_map_compact's shape over the map's own rows: block counts of the rows whose flag is 0, one scan per sample,
 //                   scatter into the other buffer (the rows the depth cube of visibility.hip saw through).
+//   df_map_compact_near  df_map_compact's second form (opt-in): on overflow the rows of the outermost window
+//                   rings go, not the end of the sorted order.  A fill launch, the kept rows per (sample, ring), one block per sample
+//                   that scans the ring counts into cut = (R, budget), then df_map_compact's three launches with two prefixes carried
+//                   together: the rows of rings < R and those of ring R.
 //
-// No float atomics, no integer atomics (df_cell_sort's are the only ones of an update), no LDS outside the 256-wide scans.
+// No float atomics.  The entries above run no integer atomics (df_cell_sort's are the only ones of an update) and no LDS outside the
+// 256-wide scans; df_map_compact_near alone adds an 8 KiB LDS histogram per block and integer atomicAdds into it and into its ring counts
+// in ws -- integer sums do not depend on the order of their operands, so its results are as repeatable as the others'.
 #include <math.h>
 
 #include "common.h"
@@ -312,6 +318,163 @@ __global__ __launch_bounds__(256) void drop_scatter_kernel(const double* __restr
   }
 }
 
+// ---- df_map_compact_near: df_map_compact with the window shrunk ring by ring until the kept rows fit -------------
+// ring of a kept row of sample b = max(|dx - W|, |dy - W|) of its window column, from its key (b S + dy) S + dx; a key outside the
+// sample's columns (no kept row has one: df_map_select keeps only rows of a column) is held to ring W, so every index below is in range
+__device__ __forceinline__ int near_ring(uint32_t cell, int b, int S, int W) {
+  const uint32_t cells = (uint32_t)S * (uint32_t)S;
+  const uint32_t local = cell - (uint32_t)b * cells;
+  if (local >= cells) return W;
+  const int dy = (int)(local / (uint32_t)S), dx = (int)(local - (uint32_t)dy * (uint32_t)S);
+  const int ax = dx > W ? dx - W : W - dx, ay = dy > W ? dy - W : W - dy;
+  return ax > ay ? ax : ay;
+}
+
+// hist[b][r] += the kept rows of ring r in this block of sorted positions: an LDS histogram, then one integer atomicAdd per occupied ring
+__global__ __launch_bounds__(256) void near_ring_kernel(const uint32_t* __restrict__ key, const uint32_t* __restrict__ idx_sorted,
+                                                        const int32_t* __restrict__ cell_rng, const int32_t* __restrict__ keep, int cap,
+                                                        int N, int S, int W, int32_t* __restrict__ hist) {
+  __shared__ int h[2048];
+  const int b = blockIdx.y, n = cap + N;
+  for (int r = threadIdx.x; r <= W; r += 256) h[r] = 0;
+  __syncthreads();
+  int64_t s0, e0, c;
+  map_span(cell_rng, b, S, n, (int64_t)gridDim.y * n, &s0, &e0);
+  int sw;
+  if (map_flag(idx_sorted, keep, s0 + (int64_t)blockIdx.x * 256 + threadIdx.x, e0, b, n, cap, &sw, &c))
+    atomicAdd(&h[near_ring(key[c], b, S, W)], 1);
+  __syncthreads();
+  for (int r = threadIdx.x; r <= W; r += 256) {
+    const int v = h[r];
+    if (v) atomicAdd(hist + (int64_t)b * (W + 1) + r, v);
+  }
+}
+
+// one block per sample: cut[b] = (R, budget) -- the ring r whose exclusive prefix e of the ring counts has e <= cap < e + hist[r], and
+// cap - e; (W + 1, 0) when all kept rows fit.  The prefix does not decrease, so at most one ring meets the condition.
+__global__ __launch_bounds__(256) void near_cut_kernel(const int32_t* __restrict__ hist, int cap, int W, int32_t* __restrict__ cut) {
+  __shared__ int lds[256];
+  const int b = blockIdx.x;
+  const int32_t* mine = hist + (int64_t)b * (W + 1);
+  int carry = 0;
+  for (int base = 0; base <= W; base += 256) {
+    const int r = base + threadIdx.x;
+    const int v = r <= W ? mine[r] : 0;
+    int total;
+    const int e = carry + map_excl_scan256(v, lds, &total);
+    if (v > 0 && e <= cap && e + v > cap) {
+      cut[2 * b] = r;
+      cut[2 * b + 1] = cap - e;
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0 && carry <= cap) {
+    cut[2 * b] = W + 1;
+    cut[2 * b + 1] = 0;
+  }
+}
+
+// (inner | partial << 16) of the sorted position p of sample b: kept and of a ring < R, kept and of ring R; *kept, *from_sweep, c as map_flag
+__device__ __forceinline__ int near_flag(const uint32_t* __restrict__ key, const uint32_t* __restrict__ idx_sorted,
+                                         const int32_t* __restrict__ keep, int64_t p, int64_t e0, int b, int n, int cap, int S, int W, int R,
+                                         int* kept, int* from_sweep, int64_t* c_out) {
+  *kept = map_flag(idx_sorted, keep, p, e0, b, n, cap, from_sweep, c_out);
+  if (!*kept) return 0;
+  const int ring = near_ring(key[*c_out], b, S, W);
+  return ring < R ? 1 : (ring == R ? 1 << 16 : 0);
+}
+
+// blk[b][k] = (inner, partial, kept, from the sweep) of block k of sorted positions; two counts of at most 256 share one scan
+__global__ __launch_bounds__(256) void near_count_kernel(const uint32_t* __restrict__ key, const uint32_t* __restrict__ idx_sorted,
+                                                         const int32_t* __restrict__ cell_rng, const int32_t* __restrict__ keep,
+                                                         const int32_t* __restrict__ cut, int cap, int N, int S, int W,
+                                                         int32_t* __restrict__ blk) {
+  __shared__ int lds[256];
+  const int b = blockIdx.y, n = cap + N;
+  int64_t s0, e0, c;
+  map_span(cell_rng, b, S, n, (int64_t)gridDim.y * n, &s0, &e0);
+  int f, sw;
+  const int ip = near_flag(key, idx_sorted, keep, s0 + (int64_t)blockIdx.x * 256 + threadIdx.x, e0, b, n, cap, S, W, cut[2 * b], &f, &sw, &c);
+  int both, rows;
+  map_excl_scan256(ip, lds, &both);
+  map_excl_scan256(f | (sw << 16), lds, &rows);
+  if (threadIdx.x == 0) {
+    int32_t* o = blk + ((int64_t)b * gridDim.x + blockIdx.x) * 4;
+    o[0] = both & 0xffff;
+    o[1] = both >> 16;
+    o[2] = rows & 0xffff;
+    o[3] = rows >> 16;
+  }
+}
+
+// one block per sample: blk[b][k][0], [1] become the inner and the partial rows before block k; count_out and stat of the sample
+__global__ __launch_bounds__(256) void near_scan_kernel(const int32_t* __restrict__ cell_rng, int cap, int N, int S, int nblk,
+                                                        int32_t* __restrict__ blk, int32_t* __restrict__ count_out,
+                                                        int32_t* __restrict__ stat) {
+  __shared__ int lds[256];
+  const int b = blockIdx.x, n = cap + N;
+  int32_t* mine = blk + (int64_t)b * nblk * 4;
+  int inner = 0, part = 0, kept = 0, swept = 0;
+  for (int base = 0; base < nblk; base += 256) {
+    const int i = base + threadIdx.x;
+    const bool in = i < nblk;
+    const int vi = in ? mine[4 * i] : 0, vp = in ? mine[4 * i + 1] : 0, vk = in ? mine[4 * i + 2] : 0, vs = in ? mine[4 * i + 3] : 0;
+    int ti, tp, tk, ts;
+    const int ei = map_excl_scan256(vi, lds, &ti);
+    const int ep = map_excl_scan256(vp, lds, &tp);
+    map_excl_scan256(vk, lds, &tk);
+    map_excl_scan256(vs, lds, &ts);
+    if (in) {
+      mine[4 * i] = inner + ei;
+      mine[4 * i + 1] = part + ep;
+    }
+    inner += ti;
+    part += tp;
+    kept += tk;
+    swept += ts;
+  }
+  if (threadIdx.x == 0) {
+    int64_t s0, e0;
+    map_span(cell_rng, b, S, n, (int64_t)gridDim.x * n, &s0, &e0);
+    count_out[b] = kept < cap ? kept : cap;
+    stat[4 * b] = e0 > s0 ? (int)(e0 - s0) : 0;
+    stat[4 * b + 1] = kept;
+    stat[4 * b + 2] = swept;
+    stat[4 * b + 3] = kept > cap ? kept - cap : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void near_scatter_kernel(const double* __restrict__ cand, const uint32_t* __restrict__ key,
+                                                           const uint32_t* __restrict__ idx_sorted, const int32_t* __restrict__ cell_rng,
+                                                           const int32_t* __restrict__ keep, const int32_t* __restrict__ cut,
+                                                           const int32_t* __restrict__ blk, const int32_t* __restrict__ count_out, int cap,
+                                                           int N, int S, int W, double* __restrict__ map_out) {
+  __shared__ int lds[256];
+  const int b = blockIdx.y, n = cap + N;
+  int64_t s0, e0, c;
+  map_span(cell_rng, b, S, n, (int64_t)gridDim.y * n, &s0, &e0);
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const int budget = cut[2 * b + 1];
+  int f, sw, total;
+  const int ip = near_flag(key, idx_sorted, keep, s0 + j, e0, b, n, cap, S, W, cut[2 * b], &f, &sw, &c);
+  const int ex = map_excl_scan256(ip, lds, &total);
+  const int32_t* mine = blk + ((int64_t)b * gridDim.x + blockIdx.x) * 4;
+  const int before_inner = mine[0] + (ex & 0xffff), before_part = mine[1] + (ex >> 16);
+  const bool survives = (ip & 0xffff) != 0 || ((ip >> 16) != 0 && before_part < budget);
+  const int64_t at = (int64_t)before_inner + (before_part < budget ? before_part : budget);
+  double* out = map_out + (int64_t)b * cap * 3;
+  if (survives && at >= 0 && at < cap) {                 // rows below count_out[b]: each survivor has its own `at`
+    out[at * 3] = cand[c * 3];
+    out[at * 3 + 1] = cand[c * 3 + 1];
+    out[at * 3 + 2] = cand[c * 3 + 2];
+  }
+  if (j < cap && j >= count_out[b]) {                    // rows from count_out[b] on: the thread of the same index
+    out[(int64_t)j * 3] = map_nan();
+    out[(int64_t)j * 3 + 1] = map_nan();
+    out[(int64_t)j * 3 + 2] = map_nan();
+  }
+}
+
 bool map_shape_ok(int B, int cap, int N, int W) {
   if (B < 1 || B > 65535 || cap < 1 || N < 0 || W < 1 || W > 2047) return false;
   const int64_t S = 2 * (int64_t)W + 1;
@@ -373,6 +536,40 @@ extern "C" int df_map_compact(const double* cand, const uint32_t* idx_sorted, co
   DF_CHECK_LAUNCH();
   hipLaunchKernelGGL(map_scatter_kernel, dim3(nblk, B), dim3(256), 0, s, cand, idx_sorted, cell_rng, keep, blk, count_out, cap, N, S,
                      map_out);
+  DF_CHECK_LAUNCH();
+  return DF_OK;
+}
+
+// ws of df_map_compact_near: the ring counts [B][W + 1], then (inner, partial, kept, from the sweep) per block [B][nblk][4], all i32
+extern "C" int64_t df_map_near_ws_bytes(int B, int cap, int N, int W) {
+  if (!map_shape_ok(B, cap, N, W) || N < 1) return DF_E_SHAPE;
+  return (int64_t)B * ((int64_t)W + 1 + (((int64_t)cap + N + 255) / 256) * 4) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int df_map_compact_near(const double* cand, const uint32_t* key, const uint32_t* idx_sorted, const int32_t* cell_rng,
+                                   const int32_t* keep, int B, int cap, int N, int W, double* map_out, int32_t* count_out, int32_t* stat,
+                                   int32_t* cut, void* ws, void* stream) {
+  DF_REQUIRE(cand && key && idx_sorted && cell_rng && keep && map_out && count_out && stat && cut && ws, DF_E_ARG);
+  DF_REQUIRE(map_shape_ok(B, cap, N, W) && N >= 1, DF_E_SHAPE);
+  DF_REQUIRE(map_aligned(cand, 8) && map_aligned(map_out, 8) && map_aligned(ws, 4), DF_E_ALIGN);
+  DF_REQUIRE(static_cast<const void*>(cand) != static_cast<const void*>(map_out), DF_E_ARG);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int nblk = (cap + N + 255) / 256, S = 2 * W + 1;
+  const int64_t rings = (int64_t)B * (W + 1);
+  int32_t* hist = reinterpret_cast<int32_t*>(ws);
+  int32_t* blk = hist + rings;
+  hipLaunchKernelGGL(map_fill_i32_kernel, dim3((unsigned)((rings + 255) / 256)), dim3(256), 0, s, rings, hist);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(near_ring_kernel, dim3(nblk, B), dim3(256), 0, s, key, idx_sorted, cell_rng, keep, cap, N, S, W, hist);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(near_cut_kernel, dim3(B), dim3(256), 0, s, hist, cap, W, cut);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(near_count_kernel, dim3(nblk, B), dim3(256), 0, s, key, idx_sorted, cell_rng, keep, cut, cap, N, S, W, blk);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(near_scan_kernel, dim3(B), dim3(256), 0, s, cell_rng, cap, N, S, nblk, blk, count_out, stat);
+  DF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(near_scatter_kernel, dim3(nblk, B), dim3(256), 0, s, cand, key, idx_sorted, cell_rng, keep, cut, blk, count_out, cap,
+                     N, S, W, map_out);
   DF_CHECK_LAUNCH();
   return DF_OK;
 }

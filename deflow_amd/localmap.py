@@ -7,7 +7,8 @@ W = ceil(max_range / voxel) + 1.  Older points win: a full voxel refuses every n
 CUDA tensors only: there is no CPU fallback.  ``insert`` is df_map_keys, df_cell_sort, df_map_select, df_map_compact and ``view`` is
 df_map_view; nothing reads a device value back, so a recording can be queued whole before its one read-back.  ``carve`` (opt-in,
 DESIGN.md section 6u) is the one way a row inside the window leaves: df_map_view, the depth cube of ``visibility`` built on the current
-sweep and tested on the view, then df_map_drop."""
+sweep and tested on the view, then df_map_drop.  ``evict="near"`` (opt-in, UNPINNED) makes the last call of
+``insert`` df_map_compact_near: on overflow the rows of the outermost window rings go, not the end of the sorted order."""
 from __future__ import annotations
 
 import functools
@@ -21,13 +22,18 @@ from .args import cloud, integer, labels, positive, tensor, workspace
 
 _tensor = functools.partial(tensor, other="the map is")
 W_MAX = 2047
+EVICT = ("order", "near")
 
 
 class LocalMap:
     """points [B,capacity,3] f64 (rows >= count are NaN), count [B] i32, stat [B,4] i32 of the last insert = (rows in the window, rows
-    kept, kept rows that came from the sweep, overflow = kept rows that did not fit into capacity)."""
+    kept, kept rows that came from the sweep, overflow = kept rows that did not fit into capacity).  evict: which rows an overflow loses --
+    "order": the end of the sorted order (df_map_compact); "near": the outermost rings of the window (df_map_compact_near), and then cut
+    [B,2] i32 of the last insert = (R, budget), (W + 1, 0) for a sample without overflow.  Under "order" cut is None."""
 
-    def __init__(self, B: int, capacity: int, *, voxel: float, max_per_voxel: int, max_range: float, device):
+    def __init__(self, B: int, capacity: int, *, voxel: float, max_per_voxel: int, max_range: float, device, evict: str = "order"):
+        if evict not in EVICT:
+            raise ValueError(f"LocalMap: evict must be 'order' or 'near', got {evict!r}")
         p = {"B": B, "capacity": capacity, "voxel": voxel, "max_per_voxel": max_per_voxel, "max_range": max_range}
         integer("LocalMap", p, "B", 1, 65535)
         integer("LocalMap", p, "capacity", 1, 2 ** 30 - 1)
@@ -50,6 +56,7 @@ class LocalMap:
         self._spare = torch.empty_like(self.points)
         self.count = torch.zeros(self.B, dtype=torch.int32, device=device)
         self.stat = torch.zeros(self.B, 4, dtype=torch.int32, device=device)
+        self.evict, self.cut = evict, None
 
     def _pose(self, fn: str, pose) -> torch.Tensor:
         _tensor(fn, "pose", pose, torch.float64, (self.B, 4, 4), self.dev)
@@ -59,7 +66,7 @@ class LocalMap:
                gate: Optional[torch.Tensor] = None) -> None:
         """points [B,N,3] f32 in the sensor's frame with count [B] i32 valid leading rows, pose [B,4,4] f64 (world = R s + t); optional
         integer / bool mask [B,N] (rows with mask > 0 take part) and gate [B] i32 (a sample with gate != 0 inserts nothing: the
-        ``status`` of the registration that made the pose).  Replaces .points, .count and .stat."""
+        ``status`` of the registration that made the pose).  Replaces .points, .count and .stat, and .cut under evict="near"."""
         fn = "LocalMap.insert"
         B, N = cloud(fn, "points", points)
         if B != self.B or points.device != self.dev:
@@ -72,7 +79,8 @@ class LocalMap:
         cap, W, dev = self.capacity, self.W, self.dev
         n, ncells = cap + N, B * self.S * self.S
         refused = f"{fn}: B = {B} samples of capacity + N = {n} candidate rows are beyond the entries' limits (B (capacity + N) < 2^30)"
-        ws = workspace("df_map_ws_bytes", (B, cap, N), dev, refused)
+        near = self.evict == "near"
+        ws = workspace("df_map_near_ws_bytes", (B, cap, N, W), dev, refused) if near else workspace("df_map_ws_bytes", (B, cap, N), dev, refused)
         points, count = points.detach().contiguous(), count.contiguous()
         cand = torch.empty(B, n, 3, dtype=torch.float64, device=dev)
         key = torch.empty(B * n, dtype=torch.int32, device=dev)
@@ -89,9 +97,17 @@ class LocalMap:
              self.voxel, W, ptr(cand), ptr(key), ptr(vz), s)
         call("df_cell_sort", ptr(key), B * n, ncells, ptr(idx), ptr(rng), ptr(sort_ws), s)
         call("df_map_select", ptr(key), ptr(idx), ptr(rng), ptr(vz), B, n, W, self.max_per_voxel, ptr(keep), s)
-        call("df_map_compact", ptr(cand), ptr(idx), ptr(rng), ptr(keep), B, cap, N, W, ptr(out), ptr(count_out), ptr(stat), ptr(ws), s)
+        if near:
+            cut = torch.empty(B, 2, dtype=torch.int32, device=dev)
+            call("df_map_compact_near", ptr(cand), ptr(key), ptr(idx), ptr(rng), ptr(keep), B, cap, N, W, ptr(out), ptr(count_out),
+                 ptr(stat), ptr(cut), ptr(ws), s)
+            self.cut = cut
+        else:
+            call("df_map_compact", ptr(cand), ptr(idx), ptr(rng), ptr(keep), B, cap, N, W, ptr(out), ptr(count_out), ptr(stat), ptr(ws), s)
         self._spare, self.points, self.count, self.stat = self.points, out, count_out, stat
         self.last = {"cand": cand, "key": key, "vz": vz, "idx_sorted": idx, "cell_rng": rng, "keep": keep}     # the stages, for tests
+        if near:
+            self.last["cut"] = cut
 
     def carve(self, points: torch.Tensor, count: torch.Tensor, pose: torch.Tensor, *, mask: Optional[torch.Tensor] = None,
               gate: Optional[torch.Tensor] = None, res: int, halo: int, margin: float, rel: float, near: float) -> None:

@@ -7,7 +7,8 @@ definition -- include/deflow_amd.h and DESIGN.md section 6r -- a scan-to-scan, p
 of freedom (``residual="point"``, the default) or, with ``residual="plane"``, a point-to-plane ICP against normals of the target that
 ``normals`` estimates on the GPU: no map by default (``target="map"`` registers every sweep against a voxel-capped local map of the sweeps
 so far instead of its predecessor: ``localmap.LocalMap``; ``map_carve=True`` drops the map rows each sweep sees
-through before it is inserted: DESIGN.md section 6u), no loop closure, no motion un-distortion, and nothing
+through before it is inserted: DESIGN.md section 6u; ``map_evict="near"`` makes an overflowing map lose its outermost rows instead of the
+end of its sorted order: DESIGN.md section 6v), no loop closure, no motion un-distortion, and nothing
 about its accuracy on real sweeps has been measured.  Scene flow
 needs only the relative transform of consecutive sweeps (the reference's ``ego_motion``), which is what it estimates; the poses are those
 transforms chained.
@@ -54,6 +55,11 @@ MAP_DEFAULTS: Dict[str, Any] = {"target": "scan", "map_voxel": 0.5, "map_max_per
 # it: the keys of 6t stay what they were.)
 MAP_CARVE_DEFAULTS: Dict[str, Any] = {"map_carve": False, "map_carve_res": 256, "map_carve_halo": 1, "map_carve_margin": 0.5,
                                       "map_carve_rel": 0.02}
+# map_evict: which rows the map loses when an update overflows map_capacity (localmap.LocalMap(evict=...); UNPINNED).
+# "order": the end of the sorted order, what it always was; "near": the outermost rings of the window, so that what goes is what is
+# farthest from the sensor.  Whether "near" helps on real sweeps is unmeasured.  (A dict of its own, for the reason given above.)
+MAP_EVICT_DEFAULTS: Dict[str, Any] = {"map_evict": "order"}
+MAP_EVICTS = ("order", "near")
 
 
 _tensor = functools.partial(tensor, "register", other="src")
@@ -247,7 +253,8 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
                     map_carve: bool = MAP_CARVE_DEFAULTS["map_carve"], map_carve_res: int = MAP_CARVE_DEFAULTS["map_carve_res"],
                     map_carve_halo: int = MAP_CARVE_DEFAULTS["map_carve_halo"],
                     map_carve_margin: float = MAP_CARVE_DEFAULTS["map_carve_margin"],
-                    map_carve_rel: float = MAP_CARVE_DEFAULTS["map_carve_rel"], **params) -> List[np.ndarray]:
+                    map_carve_rel: float = MAP_CARVE_DEFAULTS["map_carve_rel"],
+                    map_evict: str = MAP_EVICT_DEFAULTS["map_evict"], **params) -> List[np.ndarray]:
     """Relative transforms of consecutive sweeps given as arrays [N_i, >= 3], each in its own vehicle frame, in time order:
     -> rel[k] float64 [4,4] mapping sweep k into sweep k + 1's frame, one B = 1 ``register`` per pair.  target="scan": sweep k + 1 is the
     target of sweep k.  target="map": sweep k + 1 is registered against a local map of the sweeps 0 .. k seen from pose_k (at most
@@ -256,12 +263,15 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
     map_carve=True (target="map" only; UNPINNED): between the pose of sweep k + 1 and its insertion the map rows
     that the sweep sees through are dropped -- a depth cube of map_carve_res bins per face edge built on the sweep's participating rows,
     a map row flagged when a return lies more than map_carve_margin + map_carve_rel x its depth behind it in the (2 map_carve_halo + 1)^2
-    bins about its own, rows nearer than min_range left alone; a failed sweep carves nothing.  ground: per sweep None or a 0 / 1
+    bins about its own, rows nearer than min_range left alone; a failed sweep carves nothing.
+    map_evict="near" (target="map" only; UNPINNED): an update that overflows map_capacity loses the rows of the
+    outermost rings of the window about the sensor instead of the end of the sorted order ("order", the default).  ground: per sweep None or a 0 / 1
     array [N_i]; ground rows do not take part.  Rows take part only at a horizontal distance from the frame's origin in
     [min_range, max_range].  The first pair starts from identity; init="previous": each later pair from the previous pair's result
     (constant velocity), "identity": every pair from identity.  A pair whose status is not 0 keeps its initial transform.
     report: a dict that receives the parameters, the failed pairs and the final inliers / residual of every pair (target="map": also
-    map_count and map_overflow after every sweep, and with map_carve map_carved, the rows every later sweep dropped)."""
+    map_count and map_overflow after every sweep, with map_carve map_carved, the rows every later sweep dropped, and with
+    map_evict="near" map_cut, the pair (R, budget) of every sweep's update)."""
     if init not in ("previous", "identity"):
         raise ValueError(f"register_sweeps: init must be 'previous' or 'identity', got {init!r}")
     if target not in TARGETS:
@@ -283,6 +293,11 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
         integer("register_sweeps", cp, "map_carve_halo", 0, HALO_MAX)
         nonneg("register_sweeps", cp, "map_carve_margin")
         nonneg("register_sweeps", cp, "map_carve_rel")
+    if map_evict not in MAP_EVICTS:
+        raise ValueError(f"register_sweeps: map_evict must be 'order' or 'near', got {map_evict!r}")
+    if map_evict == "near" and target != "map":
+        raise ValueError("register_sweeps: map_evict='near' needs target='map': there is no map to evict from with target='scan'")
+    near = map_evict == "near"
     if not (0 <= float(min_range) < float(max_range)):
         raise ValueError(f"register_sweeps: 0 <= min_range < max_range expected, got {min_range}, {max_range}")
     unknown = sorted(set(params) - set(DEFAULTS))
@@ -307,14 +322,16 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
         clouds.append((torch.from_numpy(p).to(device)[None], torch.full((1,), p.shape[0], dtype=torch.int32, device=device),
                        torch.from_numpy(keep.astype(np.int32)).to(device)[None]))
     start = torch.eye(4, dtype=torch.float64, device=device)[None]
-    Ts, stats, fill, carved = [], [], [], []
+    Ts, stats, fill, carved, cuts = [], [], [], [], []
     if target == "map" and clouds:
         from .localmap import LocalMap
         lmap = LocalMap(1, mp["map_capacity"], voxel=mp["map_voxel"], max_per_voxel=mp["map_max_per_voxel"], max_range=float(max_range),
-                        device=device)
+                        device=device, **({"evict": "near"} if near else {}))
         pose = start.clone()
         lmap.insert(*clouds[0][:2], pose, mask=clouds[0][2])
         fill.append(torch.cat((lmap.count, lmap.stat[0, 3:])))
+        if near:
+            cuts.append(lmap.cut)
         for ps, cs, ms in clouds[1:]:
             dst, cd = lmap.view(pose)
             T, info = register(ps, cs, dst, cd, init=start, mask_s=ms, **params)
@@ -329,6 +346,8 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
             Ts.append(T)
             stats.append(torch.cat((info["status"].to(torch.float32), info["log"][0, -1, :2])))
             fill.append(torch.cat((lmap.count, lmap.stat[0, 3:])))
+            if near:
+                cuts.append(lmap.cut)
             if init == "previous":
                 start = T
     for k in range(len(clouds) - 1 if target == "scan" else 0):
@@ -353,8 +372,10 @@ def register_sweeps(lidars: Sequence[np.ndarray], ground: Optional[Sequence[Opti
             report.update(map_count=[int(c) for c in mf[:, 0]], map_overflow=[int(c) for c in mf[:, 1]])
             if cp["map_carve"]:
                 report.update(map_carved=[int(c) for c in torch.cat(carved).cpu().numpy()] if carved else [])
+            if near:
+                report.update(map_cut=[(int(c[0]), int(c[1])) for c in torch.cat(cuts).cpu().numpy()] if cuts else [])
         report.update(params={**DEFAULTS, **params, "min_range": float(min_range), "max_range": float(max_range), "init": init,
-                              "target": target, **mp, **cp},
+                              "target": target, **mp, **cp, "map_evict": map_evict},
                       failed=[{"pair": int(k), "status": int(s[0])} for k, s in enumerate(st) if int(s[0]) != 0],
                       inliers=[float(s[1]) for s in st], residual=[float(s[2]) for s in st])
     return rel
@@ -446,13 +467,14 @@ def sweep_pose(group, side: Optional[Dict[str, np.ndarray]], *, scene_id: str, t
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
 CLI_DEFAULTS: Dict[str, Any] = {"data_dir": None, "scenes": None, "overwrite": False, "ground_source": "auto", "init": "previous",
-                                **SCENE_DEFAULTS, **MAP_DEFAULTS, **MAP_CARVE_DEFAULTS,
+                                **SCENE_DEFAULTS, **MAP_DEFAULTS, **MAP_CARVE_DEFAULTS, **MAP_EVICT_DEFAULTS,
                                 **{k: (list(v) if isinstance(v, tuple) else v) for k, v in DEFAULTS.items()}}
 USAGE = ("usage: python -m deflow_amd.odometry data_dir=<dir> [scenes=a,b] [overwrite=false] [stride=4] [levels=2,1,0.5] [iters=8] "
          "[planar=false] [min_inliers=50] [residual=point|plane] [normal_radius=1] [normal_min_pts=5] [normal_max_curv=0.05] "
          "[ground_source=auto|none] [init=previous|identity] [min_range=3] [max_range=51.2] [cell=1] "
          "[xy_range=-51.2,-51.2,51.2,51.2] [target=scan|map] [map_voxel=0.5] [map_max_per_voxel=4] [map_capacity=524288] "
-         "[map_carve=false] [map_carve_res=256] [map_carve_halo=1] [map_carve_margin=0.5] [map_carve_rel=0.02]")
+         "[map_carve=false] [map_carve_res=256] [map_carve_halo=1] [map_carve_margin=0.5] [map_carve_rel=0.02] "
+         "[map_evict=order|near]")
 
 
 def _bool(v: str) -> bool:
@@ -490,6 +512,10 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
                 if v not in TARGETS:
                     raise ValueError(v)
                 cfg[k] = v
+            elif k == "map_evict":
+                if v not in MAP_EVICTS:
+                    raise ValueError(v)
+                cfg[k] = v
             elif k == "init":
                 if v not in ("previous", "identity"):
                     raise ValueError(v)
@@ -520,6 +546,8 @@ def parse_args(argv: List[str]) -> Dict[str, Any]:
         raise SystemExit(f"bad value for min_range / max_range: {cfg['min_range']} .. {cfg['max_range']}")
     if cfg["map_carve"] and cfg["target"] != "map":
         raise SystemExit("bad value for map_carve / target: map_carve=true needs target=map")
+    if cfg["map_evict"] == "near" and cfg["target"] != "map":
+        raise SystemExit("bad value for map_evict / target: map_evict=near needs target=map")
     if cfg["residual"] == "plane" and cfg["normal_radius"] > cfg["cell"]:
         raise SystemExit(f"bad value for normal_radius / cell: the radius {cfg['normal_radius']} is larger than the cell {cfg['cell']}")
     return cfg
@@ -530,7 +558,7 @@ def main(argv=None) -> int:
     assert torch.cuda.is_available(), "the odometry runs on the HIP engine only"
     d = cfg["data_dir"]
     scenes = cfg["scenes"] or sorted(n[:-3] for n in os.listdir(d) if n.endswith(".h5"))
-    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS, *MAP_DEFAULTS, *MAP_CARVE_DEFAULTS)}
+    params = {k: (tuple(cfg[k]) if isinstance(cfg[k], list) else cfg[k]) for k in (*DEFAULTS, *SCENE_DEFAULTS, *MAP_DEFAULTS, *MAP_CARVE_DEFAULTS, *MAP_EVICT_DEFAULTS)}
     for sid in scenes:
         out = os.path.join(d, sid + SIDECAR_SUFFIX)
         if os.path.exists(out) and not cfg["overwrite"]:
@@ -539,7 +567,9 @@ def main(argv=None) -> int:
         rep: Dict[str, Any] = {}
         t0 = time.perf_counter()
         poses = scene_poses(os.path.join(d, sid + ".h5"), ground_source=cfg["ground_source"], init=cfg["init"], report=rep, **params)
-        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": "DESIGN.md 6r (UNPINNED)" if cfg["target"] == "scan" else "DESIGN.md 6r, 6t, 6u (UNPINNED)" if cfg["map_carve"] else "DESIGN.md 6r, 6t (UNPINNED)"})
+        sections = ["6r"] + (["6t"] if cfg["target"] == "map" else []) + (["6u"] if cfg["map_carve"] else []) + \
+            (["6v"] if cfg["map_evict"] == "near" else [])
+        write_sidecar(out, poses, {**rep["params"], "failed": rep["failed"], "definition": f"DESIGN.md {', '.join(sections)} (UNPINNED)"})
         ps = list(poses.values())
         path = sum(float(np.linalg.norm(b[:3, 3] - a[:3, 3])) for a, b in zip(ps, ps[1:]))
         n = max(len(rep["inliers"]), 1)

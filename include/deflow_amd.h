@@ -1307,7 +1307,36 @@ int df_reg_accumulate_plane(const int32_t* src_rng, const float* src_sorted, int
  * df_map_compact: -> map_out [B,cap,3] f64, count_out [B] i32, stat [B,4] i32.
  * B outside 1..65535, cap / N / n < 1, W outside 1..2047, B n >= 2^30, B S S >= 2^30: DF_E_SHAPE.  NULL pointers (the nullable ones
  * excepted), a voxel that is not positive and finite, max_per_voxel < 1, map_out == cand: DF_E_ARG.  float64 buffers not 8-byte
- * aligned: DF_E_ALIGN.  No launch then. */
+ * aligned: DF_E_ALIGN.  No launch then.
+ *
+ * NEAREST-FIRST EVICTION (opt-in; UNPINNED like the rest: this project's own definition).  df_map_compact_near is
+ * a second form of the last stage of an update; keys, sort and select are the ones above.  Where kept_b > cap, `compact` loses the end
+ * of the sorted order, the columns of the largest dy: one side of the window, whatever the scene.  This form shrinks the window instead.
+ *   ring         of a kept candidate with the key (b S + dy) S + dx: r = max(|dx - W|, |dy - W|), the Chebyshev distance of its column
+ *                from the anchor column, 0 .. W.  h_b[r] = the kept candidates of ring r; kept_b = their sum.
+ *   no overflow  kept_b <= cap: map_out, count_out and stat are bit for bit `compact`'s, and cut[b] = (W + 1, 0).
+ *   overflow     R_b = the largest R in 0 .. W with sum_{r < R} h_b[r] <= cap; budget_b = cap - sum_{r < R_b} h_b[r], so
+ *                0 <= budget_b < h_b[R_b].  A kept candidate SURVIVES when its ring is < R_b, or when its ring is R_b and fewer than
+ *                budget_b kept candidates of ring R_b precede it in sorted order.  The survivors in sorted order are rows 0 .. cap-1 of
+ *                map_out; count_out[b] = cap; cut[b] = (R_b, budget_b).  Said another way: the survivors are the first cap kept
+ *                candidates under the order (ring, sorted position), emitted in sorted position.
+ *   stat, tail   stat [B,4] keeps `compact`'s four meanings exactly (kept rows from the sweep are counted before the cut; overflow =
+ *                max(0, kept_b - cap)); every row from count_out[b] on is three float64 NaNs (0x7FF8000000000000).
+ * The result is a valid map under `compact`'s argument: survivors keep their sorted order, and all rows of a column share a ring, so a
+ * column is kept whole, dropped whole or -- in ring R_b only -- cut after its oldest rows.  What stays arbitrary is the partial ring R_b:
+ * it is filled in sorted order, its smallest dy first.  The error is bounded to one ring instead of a slab of the window.
+ * Every output element is written exactly once.  No float atomics; the kept rows per (sample, ring) are counted with integer atomicAdd
+ * (an LDS histogram per block, then one add per occupied ring into ws after a fill launch), which the statement above that an update
+ * runs no atomics outside df_cell_sort does NOT cover.  An integer sum does not depend on the order of its operands, so two calls are
+ * still bit-identical, also with ws, cut and map_out pre-filled with anything; sample b depends neither on B nor on the other samples;
+ * nothing is allocated, synchronised or read back, and no grid dimension comes from a device value.
+ * df_map_compact_near: cand [B,n,3] f64, key [B n] u32, idx_sorted [B n] u32, cell_rng [B S S, 2] i32, keep [B n] i32 -> map_out
+ *   [B,cap,3] f64 (NOT the buffer cand was made from), count_out [B] i32, stat [B,4] i32, cut [B,2] i32.  Six launches: fill, ring
+ *   counts (ceil(n / 256), B), the cut (B), block counts (ceil(n / 256), B), one scan per sample (B), scatter (ceil(n / 256), B).
+ * df_map_near_ws_bytes(B, cap, N, W): the bytes of its ws = 4 B (W + 1 + 4 ceil((cap + N) / 256)): the ring counts [B][W + 1] i32, then
+ *   (rows of rings < R, rows of ring R, kept rows, kept rows from the sweep) per block [B][ceil(n / 256)][4] i32; DF_E_SHAPE (negative)
+ *   for refused shapes.
+ * Shapes, NULL pointers (cut and key included: none is nullable), map_out == cand and alignment are refused as by df_map_compact. */
 int64_t df_map_ws_bytes(int B, int cap, int N);
 int df_map_keys(const double* map, const int32_t* count, const float* sweep, const int32_t* sweep_count, const int32_t* mask /*nullable*/,
                 const int32_t* gate /*nullable*/, const double* pose, int B, int cap, int N, double voxel, int W, double* cand,
@@ -1317,6 +1346,10 @@ int df_map_select(const uint32_t* key, const uint32_t* idx_sorted, const int32_t
 int df_map_compact(const double* cand, const uint32_t* idx_sorted, const int32_t* cell_rng, const int32_t* keep, int B, int cap, int N,
                    int W, double* map_out, int32_t* count_out, int32_t* stat, void* ws, void* stream);
 int df_map_view(const double* map, const int32_t* count, const double* pose, int B, int cap, float* dst, void* stream);
+int64_t df_map_near_ws_bytes(int B, int cap, int N, int W);
+int df_map_compact_near(const double* cand, const uint32_t* key, const uint32_t* idx_sorted, const int32_t* cell_rng, const int32_t* keep,
+                        int B, int cap, int N, int W, double* map_out, int32_t* count_out, int32_t* stat, int32_t* cut, void* ws,
+                        void* stream);
 
 /* ------------------------------------------------------------------ depth cube: carving seen-through rows out of the local map ----
  * UNPINNED: this project's own definition; every default of its callers is a choice, not a measurement.  A map

@@ -1,5 +1,5 @@
 """What the sweep-to-sweep registration costs on the GPU, measured: usage  python tools/odometry_bench.py [--batch 16] [--points 80000]
-[--grid 512] [--reps 20] [--map | --carve] [--out profiles/odometry_bench.json] [--plane-out profiles/odometry_plane_bench.json] [--parent-lib <libdeflow_amd.so>]
+[--grid 512] [--reps 20] [--map | --carve | --evict] [--out profiles/odometry_bench.json] [--plane-out profiles/odometry_plane_bench.json] [--parent-lib <libdeflow_amd.so>]
 
 At the configs[2] cloud (80 000 rows per cloud, 512 x 512; ~70 000 rows in range: the compact pc0 / pc1 of a real forward, the clouds
 tools/cluster_bench.py times), for B = 1 and B = --batch and stride 4 and 1, with device events after a warm-up (medians of --reps calls):
@@ -28,6 +28,10 @@ same clouds and the same map (B = 1, capacity 524 288, the cube and the margins 
 df_depth_cube_test and df_map_drop one by one, the four back to back, a whole ``LocalMap.carve`` (which also allocates), and the
 yardsticks in the same process -- df_map_view over the same rows (the streaming floor of the test kernel) and the four stages of one
 insert update.
+
+--evict [--evict-out profiles/localmap_evict_bench.json] measures nearest-first eviction INSTEAD, in --map's setup
+(B = 1, capacity 524 288, the map full, so the timed update overflows): the stages of one update with df_map_compact_near beside
+df_map_compact -- the yardstick -- on the same stage tensors, and the update's sum with either policy.
 
 A measuring tool, not a bench.py leg; needs the GPU (no fallback)."""
 import argparse
@@ -177,8 +181,60 @@ def carve_bench(a, dev, pc0, c0, pc1, c1):
     print("wrote", a.carve_out)
 
 
+def evict_bench(a, dev, pc0, c0, pc1, c1):
+    """--evict: the stages of one overflowing local-map update at the defaults (B = 1, the map full), with df_map_compact_near beside
+    df_map_compact -- the yardstick, on the same stage tensors in the same process -- and the update's sum with either policy"""
+    from deflow_amd.args import workspace
+    from deflow_amd.localmap import LocalMap
+    md = odometry.MAP_DEFAULTS
+    lm = LocalMap(1, md["map_capacity"], voxel=md["map_voxel"], max_per_voxel=md["map_max_per_voxel"],
+                  max_range=odometry.SCENE_DEFAULTS["max_range"], device=dev)
+    pose = torch.eye(4, dtype=torch.float64, device=dev)[None].clone()
+    for k in range(12):                                # as --map: the sensor moves 0.5 m per sweep; the map is full after nine sweeps
+        lm.insert(pc0 if k % 2 == 0 else pc1, c0 if k % 2 == 0 else c1, pose)
+        pose[0, 0, 3] += 0.5
+    cap, N, W, K = lm.capacity, pc1.shape[1], lm.W, lm.max_per_voxel
+    n, ncells = cap + N, lm.S * lm.S
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    cand, key, vz, idx, rng, keep = torch.empty(1, n, 3, dtype=torch.float64, device=dev), i32(n), i32(n), i32(n), i32(ncells, 2), i32(n)
+    out, cnt, stat = torch.empty_like(lm.points), i32(1), i32(1, 4)
+    out_n, cnt_n, stat_n, cut = torch.empty_like(lm.points), i32(1), i32(1, 4), i32(1, 2)
+    ws, sws = workspace("df_map_ws_bytes", (1, cap, N), dev, "shape"), workspace("df_cell_sort_ws_bytes", (ncells,), dev, "shape")
+    nws = workspace("df_map_near_ws_bytes", (1, cap, N, W), dev, "shape")
+    stages = {
+        "keys": lambda: call("df_map_keys", ptr(lm.points), ptr(lm.count), ptr(pc1), ptr(c1), None, None, ptr(pose), 1, cap, N, lm.voxel, W,
+                             ptr(cand), ptr(key), ptr(vz), stream()),
+        "cell_sort": lambda: call("df_cell_sort", ptr(key), n, ncells, ptr(idx), ptr(rng), ptr(sws), stream()),
+        "select": lambda: call("df_map_select", ptr(key), ptr(idx), ptr(rng), ptr(vz), 1, n, W, K, ptr(keep), stream()),
+        "compact": lambda: call("df_map_compact", ptr(cand), ptr(idx), ptr(rng), ptr(keep), 1, cap, N, W, ptr(out), ptr(cnt), ptr(stat),
+                                ptr(ws), stream()),
+        "compact_near": lambda: call("df_map_compact_near", ptr(cand), ptr(key), ptr(idx), ptr(rng), ptr(keep), 1, cap, N, W, ptr(out_n),
+                                     ptr(cnt_n), ptr(stat_n), ptr(cut), ptr(nws), stream()),
+    }
+    ms = {k: timed(f, a.reps) for k, f in stages.items()}              # in order: each stage reads what the one before wrote
+    ms["compact_again"] = timed(stages["compact"], a.reps)            # the yardstick once more, after the new form: the session's spread
+    shared = ms["keys"] + ms["cell_sort"] + ms["select"]
+    assert stat.tolist() == stat_n.tolist() and cnt.tolist() == cnt_n.tolist() == [cap], "the timed update must overflow"
+    differ = int((out.view(torch.int64) != out_n.view(torch.int64)).any(dim=2).sum())
+    rep = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "capacity": cap, "sweep_rows": N, "sweep_valid_rows": int(c1),
+           "voxel_m": lm.voxel, "max_per_voxel": K, "window_half_width": W, "stat_of_the_timed_update": stat[0].tolist(),
+           "cut_of_the_timed_update": cut[0].tolist(), "map_rows_that_differ_between_the_policies": differ,
+           "stage_ms": {k: round(v, 4) for k, v in ms.items()}, "near_over_compact": round(ms["compact_near"] / ms["compact"], 3),
+           "near_launches": 6, "compact_launches": 3, "update_ms_order": round(shared + ms["compact"], 4),
+           "update_ms_near": round(shared + ms["compact_near"], 4), "cell_sort_share_of_update_near": round(ms["cell_sort"] / (shared + ms["compact_near"]), 3),
+           "near_ws_bytes": int(call("df_map_near_ws_bytes", 1, cap, N, W)), "compact_ws_bytes": int(call("df_map_ws_bytes", 1, cap, N))}
+    print(json.dumps(rep), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.evict_out)), exist_ok=True)
+    with open(a.evict_out, "w") as f:
+        json.dump(rep, f, indent=1)
+    print("wrote", a.evict_out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--evict", action="store_true", help="measure nearest-first eviction beside df_map_compact only (DESIGN.md section 6v)")
+    ap.add_argument("--evict-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                        "localmap_evict_bench.json"))
     ap.add_argument("--carve", action="store_true", help="measure the carving of seen-through map rows only (DESIGN.md section 6u)")
     ap.add_argument("--carve-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                         "localmap_carve_bench.json"))
@@ -211,6 +267,9 @@ def main():
     all0, all1 = st["p0"].points_c.contiguous(), st["p1"].points_c.contiguous()
     cnt0, cnt1 = st["p0"].counts.contiguous(), st["p1"].counts.contiguous()
     del m, st
+    if a.evict:
+        evict_bench(a, dev, all0[:1].contiguous(), cnt0[:1].contiguous(), all1[:1].contiguous(), cnt1[:1].contiguous())
+        return
     if a.carve:
         carve_bench(a, dev, all0[:1].contiguous(), cnt0[:1].contiguous(), all1[:1].contiguous(), cnt1[:1].contiguous())
         return
